@@ -15,13 +15,22 @@ Workload (config.workload): BASELINE.json configs[2], the configuration the metr
 default CLI mode (first valid order).  Every rank holds its own batch of `--batch` samples (weak scaling); the ILP
 solve is replaced by the planted .sol exactly as SURVEY.md 8c/8d prescribes.
 
+A plain run sets up, warms up, times `--steps` steps and prints the result line; the timed steps carry no per-kernel HIP
+events.  `--full` adds everything else, each part still switchable by its own option: per-kernel HIP events and the
+roofline, the check of the exchanged paths, the CPU baseline and the other legs (paths on the host, other streams,
+sharded driver, lazy tables, two batches, single sample, ILP assembly, --all).  `--dump-outputs DIR` writes what the
+last timed step computed as .npy files (see `dump_outputs`); the inputs depend on the arguments only.
+
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
 import argparse
+import atexit
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -66,7 +75,64 @@ def parse_args():
     ap.add_argument("--gather", type=int, default=-1, help="1: the timed region ends with the packing of the paths + ONE RCCL gather to "
                     "rank 0 (north star: 'a single RCCL gather over xGMI at the end'); 2: at the end of EVERY step; 0: results stay in "
                     "each GPU's HBM; -1 (default): 1 when N > 1, 0 at N = 1 where there is nothing to exchange")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (per-kernel events and roofline, "
+                    "exchange check, CPU baseline and the legs switched by the options above); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the results of the last timed step (rank 0's batch) to "
+                    "DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE_UNITS = 64    # units whose paths, breakpoints and output junctions are written in full (a fixed, seeded choice)
+DUMP_FIELDS = ("status", "bias", "n_nodes", "bkp_len", "path_len", "path_indel_len", "indel_printed", "n_out_junc", "first_forward",
+               "num_orders", "first_valid", "inv_cn_sum")
+
+
+def dump_outputs(batch, B, out_dir, all_mode):
+    """What a caller of the timed path receives after ambi_batch_download, for the last timed step:
+
+    unit_results.npy          float64 [B, 12]  per unit, the DUMP_FIELDS of ambi_unit_result_t
+    final_path_digest.npy     float64 [B, 3]   per unit, final path p (after indelBFB): len(p), sum(p), sum((i + 1) * p[i])
+    out_junc_digest.npy       float64 [B, 4]   per unit, output junctions (a, b, c): count, sum(a), sum(b), sum(c)
+    sample_units.npy          float64 [S]      DUMP_SAMPLE_UNITS units chosen with seed 0, ascending
+    sample_{path,final_path,bkp}.npy + _offsets.npy   float32 cells / float64 [S + 1] offsets: path before indelBFB, final
+                              path and breakpoints of the sampled units, concatenated
+    sample_out_juncs.npy      float32 [n, 4]   (unit, a, b, c) of the sampled units
+    all_orders_digest.npy     float64 [B, 4]   --mode all only: per pass, count and sum of the valid order indices
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    batch.download()
+    save = lambda name, a, dt: np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=dt))
+    heads = [batch.unit_result(u) for u in range(B)]
+    save("unit_results", [[float(r[k]) for k in DUMP_FIELDS] for r in heads] or np.zeros((0, len(DUMP_FIELDS))), np.float64)
+    digest = np.zeros((B, 3), np.float64)
+    jdigest = np.zeros((B, 4), np.float64)
+    for u in range(B):
+        p = batch.unit_path(u, 1).astype(np.int64)
+        digest[u] = (len(p), p.sum(), (p * np.arange(1, len(p) + 1, dtype=np.int64)).sum())
+        j = np.array(batch.unit_out_juncs(u), np.int64).reshape(-1, 3)
+        jdigest[u] = (len(j), *j.sum(axis=0))
+    save("final_path_digest", digest, np.float64)
+    save("out_junc_digest", jdigest, np.float64)
+    sample = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_SAMPLE_UNITS), replace=False))
+    save("sample_units", sample, np.float64)
+    for name, get in (("sample_path", lambda u: batch.unit_path(u, 0)), ("sample_final_path", lambda u: batch.unit_path(u, 1)),
+                      ("sample_bkp", batch.unit_bkp)):
+        parts = [get(int(u)) for u in sample]
+        save(name, np.concatenate(parts) if parts else np.zeros(0), np.float32)
+        save(name + "_offsets", np.cumsum([0] + [len(x) for x in parts]), np.float64)
+    rows = [(u, a, b, c) for u in sample for (a, b, c) in batch.unit_out_juncs(int(u))]
+    save("sample_out_juncs", np.array(rows, np.float64).reshape(-1, 4), np.float32)
+    if all_mode:
+        ad = np.zeros((B, 4), np.float64)
+        for u in range(B):
+            for pass_ in (0, 1):
+                o = batch.all_orders(u, pass_)
+                ad[u, 2 * pass_: 2 * pass_ + 2] = (len(o), o.sum())
+        save("all_orders_digest", ad, np.float64)
 
 
 def main():
@@ -100,6 +166,7 @@ def main():
     # ---- workload: B samples per rank, seeds as SURVEY.md 8d (seed = 1000*config + sample index) ----
     B = args.batch
     tmp = tempfile.mkdtemp(prefix="ambi_bench_")
+    atexit.register(shutil.rmtree, tmp, True)
     graphs, files = [], []
     batch = api.Batch(lib)
     batch.configure(target_lanes=args.target_lanes)
@@ -120,13 +187,13 @@ def main():
     bad = [r for r in res if r["status"] != 0]
     if bad:
         raise SystemExit("bench: %d units did not reconstruct: %r" % (len(bad), bad[0]))
-    from ambigram_amd.dist import RunExchange
     total_cells = sum(r["path_indel_len"] for r in res)
-    n_runs, n_cells = RunExchange.probe(batch, B, "cuda", 1, stream)
-    assert n_cells == total_cells
-    px = RunExchange(lib, B, n_runs, n_cells, "cuda", world=world, rank=rank, force_collectives=force_dist)
-
     gather_mode = (1 if (world > 1 or force_dist) else 0) if args.gather < 0 else args.gather
+    if gather_mode != 0 or args.full:      # the exchange: timed when it is part of the step, checked under --full
+        from ambigram_amd.dist import RunExchange
+        n_runs, n_cells = RunExchange.probe(batch, B, "cuda", 1, stream)
+        assert n_cells == total_cells
+        px = RunExchange(lib, B, n_runs, n_cells, "cuda", world=world, rank=rank, force_collectives=force_dist)
 
     def gather():
         # the single end-of-batch exchange of the north star: the final paths in run-length form (a few dozen runs of
@@ -151,29 +218,32 @@ def main():
         if world > 1 or force_dist:
             dist.barrier()
 
-    # Warm-up with HIP events around EVERY kernel (on the streams the kernels run on): per-kernel times of the step and
+    # --full: warm-up with HIP events around EVERY kernel (on the streams the kernels run on): per-kernel times of the step and
     # which kernel dominates.  In the timed region only that kernel keeps its events: every event pair is a marker in the
-    # stream and the twelve of a fully timed step cost ~4 % (profiles/r01_slices.md).
-    batch.set_timing(True)
+    # stream and the twelve of a fully timed step cost ~4 % (profiles/r01_slices.md).  A plain run times the steps without events.
+    if args.full:
+        batch.set_timing(True)
     for _ in range(max(args.warmup, 1)):
         step()
     if gather_mode != 0:
         gather()                           # untimed: first use of the exchange (collective setup, lazily loaded kernels)
     batch.wait()
     torch.cuda.synchronize()
-    warm_times = {k: v for k, v in batch.kernel_times().items() if v >= 0 and k != "ambi_all_kernel"}
-    warm_spans = {k: v for k, v in batch.kernel_spans().items() if v[0] >= 0 and v[1] >= 0 and k in warm_times}
-    # The roofline kernel is chosen by measured time, not by name: the largest HIP-event duration among the kernels whose duration is
-    # set by their own work.  Two spans are NOT such durations and are listed (`time_ranking`, `critical_path`) but not candidates:
-    # "ambi_finish_kernel" (lean finish + list kernel on their stream) and "ambi_finish_ext_kernel" (direct full finish) run BESIDE the
-    # order-table kernel as paced side work -- the lean kernel's grid is sized so that its few workgroups work through the batch for
-    # as long as the table is being written (HipBackend::finish_grid_for), the direct launch's workgroups wait for free slots on the
-    # CUs -- so their spans track the table kernel's by construction (0.25 / 0.10 ms when they run alone, profiles/r04_*).
-    paced = ("ambi_finish_kernel", "ambi_finish_ext_kernel")
-    own_work = {k: v for k, v in warm_times.items() if k not in paced}
-    dom = max(own_work, key=lambda k: own_work[k]) if own_work else "ambi_enumerate_kernel"
-    time_ranking = [{"kernel": k, "ms": round(v, 4), "paced_side_work": k in paced} for k, v in sorted(warm_times.items(), key=lambda kv: -kv[1])]
-    batch.set_timing_only([dom])
+    if args.full:
+        warm_times = {k: v for k, v in batch.kernel_times().items() if v >= 0 and k != "ambi_all_kernel"}
+        warm_spans = {k: v for k, v in batch.kernel_spans().items() if v[0] >= 0 and v[1] >= 0 and k in warm_times}
+        # The roofline kernel is chosen by measured time among the kernels whose duration is set by their own work: the largest
+        # HIP-event duration.  Two spans are NOT such durations and are excluded by name, listed (`time_ranking`, `critical_path`) but
+        # not candidates: "ambi_finish_kernel" (lean finish + list kernel on their stream) and "ambi_finish_ext_kernel" (direct full
+        # finish) run BESIDE the order-table kernel as paced side work -- the lean kernel's grid is sized so that its few workgroups
+        # work through the batch for as long as the table is being written (HipBackend::finish_grid_for), the direct launch's
+        # workgroups wait for free slots on the CUs -- so their spans track the table kernel's by construction (0.25 / 0.10 ms when
+        # they run alone, profiles/r04_*).
+        paced = ("ambi_finish_kernel", "ambi_finish_ext_kernel")
+        own_work = {k: v for k, v in warm_times.items() if k not in paced}
+        dom = max(own_work, key=lambda k: own_work[k]) if own_work else "ambi_enumerate_kernel"
+        time_ranking = [{"kernel": k, "ms": round(v, 4), "paced_side_work": k in paced} for k, v in sorted(warm_times.items(), key=lambda kv: -kv[1])]
+        batch.set_timing_only([dom])
     barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -187,34 +257,39 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    ktimes = dict(warm_times)
-    ktimes[dom] = batch.kernel_times().get(dom, warm_times.get(dom, float("nan")))   # the dominant kernel: measured over the timed steps
-    batch.set_timing(False)
-    # the step's critical path from the HIP-event timeline of the warm-up steps (all kernels timed): the front (everything before
-    # the first workgroup of the order-table kernel), the table kernel, and the tail (what still runs after the table is complete:
-    # the finish kernels on their side streams), all in ms from the start of the step's first kernel
-    critical = None
-    if "ambi_enumerate_kernel" in warm_spans and "ambi_prepare_kernel" in warm_spans:
-        t_a, t_b = warm_spans["ambi_enumerate_kernel"]
-        last = max(warm_spans, key=lambda k: warm_spans[k][1])
-        critical = {"front_ms": t_a, "table_ms": t_b - t_a, "tail_ms": max(0.0, warm_spans[last][1] - t_b), "last_kernel": last,
-                    "end_of_last_kernel_ms": warm_spans[last][1],
-                    "spans_ms": {k: [round(v[0], 4), round(v[1], 4)] for k, v in sorted(warm_spans.items(), key=lambda kv: kv[1][0])},
-                    "note": "HIP events on the streams the kernels run on, warm-up steps (every kernel carries events there: ~4 % slower than the timed steps); "
-                            "ambi_finish_kernel = lean finish + list kernel on their stream, ambi_finish_ext_kernel = the direct launch on its own stream: ambi_finish_edit_kernel (indelBFB on the runs of the path) + the full-stage launch for what it hands on"}
+    # what the timed path computed in its last step, before any other leg runs the batch again
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(batch, B, args.dump_outputs, args.mode == "all")
 
-    # sanity (outside the timed region): the exchanged payload, expanded again, equals the downloaded paths
-    gather()
-    torch.cuda.synchronize()
-    batch.download()
-    assert int(px.totals[1].item()) == total_cells and int(px.totals[0].item()) == n_runs
-    l_host = px.lengths.cpu().tolist()
-    assert l_host == [batch.unit_result(u)["path_indel_len"] for u in range(B)]
-    if rank == 0:
-        import numpy as np
-        mine = px.cells_all[0][:total_cells].cpu().numpy()
-        want = np.concatenate([batch.unit_path(u, 1) for u in range(B)]) if B else np.zeros(0, np.int32)
-        assert mine.shape == want.shape and bool((mine == want).all()), "expanded runs differ from the downloaded paths"
+    if args.full:
+        ktimes = dict(warm_times)
+        ktimes[dom] = batch.kernel_times().get(dom, warm_times.get(dom, float("nan")))   # the dominant kernel: measured over the timed steps
+        batch.set_timing(False)
+        # the step's critical path from the HIP-event timeline of the warm-up steps (all kernels timed): the front (everything before
+        # the first workgroup of the order-table kernel), the table kernel, and the tail (what still runs after the table is complete:
+        # the finish kernels on their side streams), all in ms from the start of the step's first kernel
+        critical = None
+        if "ambi_enumerate_kernel" in warm_spans and "ambi_prepare_kernel" in warm_spans:
+            t_a, t_b = warm_spans["ambi_enumerate_kernel"]
+            last = max(warm_spans, key=lambda k: warm_spans[k][1])
+            critical = {"front_ms": t_a, "table_ms": t_b - t_a, "tail_ms": max(0.0, warm_spans[last][1] - t_b), "last_kernel": last,
+                        "end_of_last_kernel_ms": warm_spans[last][1],
+                        "spans_ms": {k: [round(v[0], 4), round(v[1], 4)] for k, v in sorted(warm_spans.items(), key=lambda kv: kv[1][0])},
+                        "note": "HIP events on the streams the kernels run on, warm-up steps (every kernel carries events there: ~4 % slower than the timed steps); "
+                                "ambi_finish_kernel = lean finish + list kernel on their stream, ambi_finish_ext_kernel = the direct launch on its own stream: ambi_finish_edit_kernel (indelBFB on the runs of the path) + the full-stage launch for what it hands on"}
+
+        # sanity (outside the timed region): the exchanged payload, expanded again, equals the downloaded paths
+        gather()
+        torch.cuda.synchronize()
+        batch.download()
+        assert int(px.totals[1].item()) == total_cells and int(px.totals[0].item()) == n_runs
+        l_host = px.lengths.cpu().tolist()
+        assert l_host == [batch.unit_result(u)["path_indel_len"] for u in range(B)]
+        if rank == 0:
+            import numpy as np
+            mine = px.cells_all[0][:total_cells].cpu().numpy()
+            want = np.concatenate([batch.unit_path(u, 1) for u in range(B)]) if B else np.zeros(0, np.int32)
+            assert mine.shape == want.shape and bool((mine == want).all()), "expanded runs differ from the downloaded paths"
 
     if rank != 0:
         if world > 1 or force_dist:
@@ -225,63 +300,65 @@ def main():
     value = units_total * args.steps / dt
     ms_per_step = dt / args.steps * 1e3
 
-    # ---- algorithmic bytes: B = 8n + 24m + 16K + 2RK + 4EL + 4P per unit, split per kernel ----
-    n, m = args.segs, None
-    per_kernel = {"ambi_prepare_kernel": 0, "ambi_plan_kernel": 0, "ambi_blocks_build_kernel": 0, "ambi_enumerate_kernel": 0, "ambi_first_kernel": 0, "ambi_finish_kernel": 0}
-    formula = 0
-    stored_table_bytes = 0      # what the order tables occupy in the engine's own row layout (5 bits per node up to 32 nodes, csrc/ambi_orders.hpp)
-    def row_bytes(K):
-        return 4 * ((5 * K + 31) // 32) if K <= 32 else (4 * ((6 * K + 31) // 32) if K <= 63 else 128)
-    for u, r in enumerate(res):
-        mj = graphs[u].n_junc
-        K, R, E, L, P, P2 = r["n_nodes"], r["num_orders"], r["evaluated"], r["bkp_len"], r["path_len"], r["path_indel_len"]
-        per_kernel["ambi_prepare_kernel"] += 8 * n + 24 * mj + 16 * K
-        per_kernel["ambi_plan_kernel"] += 64
-        per_kernel["ambi_enumerate_kernel"] += R * K                 # every order written once (one byte per node)
-        stored_table_bytes += R * row_bytes(K)
-        per_kernel["ambi_first_kernel"] += E * K + 2 * E * L         # orders read until the first valid one, bkp written
-        # bkp read, path written; the path after indelBFB is written only when indelBFB changed it
-        per_kernel["ambi_finish_kernel"] += 2 * L + 4 * P + (4 * P2 if r["path_indel_stored"] else 0)
-        formula += 8 * n + 24 * mj + 16 * K + 2 * R * K + 4 * E * L + 4 * P
-    # every kernel is launched once per slice and step (slices run on separate streams and overlap); kernel_times() is
-    # the average duration of ONE launch, so the bytes are taken per launch as well
-    slices = max(1, batch.slices())
-    dom_ms = ktimes.get(dom, float("nan"))
-    dom_bytes = per_kernel.get(dom, 0) / slices
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms and dom_ms > 0 else None
-    # HBM traffic by the PMC counters (rocprofv3 --pmc passes of this very command, corrected as MI355X_MICROARCH.md
-    # prescribes; profiles/traffic_r04.json, written by profiles/tools/collect.sh + summarize): per launch of the dominant
-    # kernel, and summed over every kernel of a step
-    traffic, step_traffic = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic_r04.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("kernel") == dom and tj.get("batch") == B and tj.get("slices", 1) == slices and tj.get("workload") == "%d/%d/%s/K%d/sv%d" % (args.segs, args.juncs, args.tier, args.K, args.sv_every):
-                traffic = tj.get("hbm_bytes_per_launch")
-                step_traffic = tj.get("hbm_bytes_per_step_all_kernels")
-        except Exception:
-            traffic = None
-    stored = (stored_table_bytes / slices) if dom == "ambi_enumerate_kernel" else None
-    stored_rate = stored / (dom_ms * 1e-3) / 1e9 if stored and dom_ms and dom_ms > 0 else None
-    roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": (achieved / HBM_PEAK_GBPS) if achieved else None, "traffic": traffic,
-                "algorithmic_bytes_per_launch": dom_bytes, "kernel_ms": dom_ms, "launches_per_step": slices,
-                # the same launch counted in the bytes the table really has: the engine stores a row at 5 bits per node (12 bytes at
-                # K = 19 where SURVEY 8d's algorithmic figure, used for `achieved`, counts 19), so `traffic` is BELOW the algorithmic bytes
-                "stored_bytes_per_launch": stored, "stored_GBps": stored_rate, "stored_frac": (stored_rate / HBM_PEAK_GBPS) if stored_rate else None,
-                "row_layout": "5 bits per node up to 32 nodes, 6 up to 63 (lossless; ambi_batch_unit_orders unpacks), one byte per node above",
-                "algorithmic_frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
-                "dominant_by": "largest HIP-event duration among the kernels whose duration is set by their own work (warm-up steps; re-measured over the timed steps); the paced finish spans are ranked in time_ranking and sit in critical_path",
-                "time_ranking": time_ranking,
-                "critical_path": critical,
-                "all_kernels_ms": ktimes, "all_kernels_note": "%s: HIP events over the timed steps; the other kernels: over the warm-up steps" % dom,
-                "step_hbm_bytes_pmc": step_traffic,
-                "step_hbm_GBps_pmc": (step_traffic / (dt / args.steps) / 1e9) if step_traffic else None}
+    roofline = None
+    if args.full:
+        # ---- algorithmic bytes: B = 8n + 24m + 16K + 2RK + 4EL + 4P per unit, split per kernel ----
+        n, m = args.segs, None
+        per_kernel = {"ambi_prepare_kernel": 0, "ambi_plan_kernel": 0, "ambi_blocks_build_kernel": 0, "ambi_enumerate_kernel": 0, "ambi_first_kernel": 0, "ambi_finish_kernel": 0}
+        formula = 0
+        stored_table_bytes = 0      # what the order tables occupy in the engine's own row layout (5 bits per node up to 32 nodes, csrc/ambi_orders.hpp)
+        def row_bytes(K):
+            return 4 * ((5 * K + 31) // 32) if K <= 32 else (4 * ((6 * K + 31) // 32) if K <= 63 else 128)
+        for u, r in enumerate(res):
+            mj = graphs[u].n_junc
+            K, R, E, L, P, P2 = r["n_nodes"], r["num_orders"], r["evaluated"], r["bkp_len"], r["path_len"], r["path_indel_len"]
+            per_kernel["ambi_prepare_kernel"] += 8 * n + 24 * mj + 16 * K
+            per_kernel["ambi_plan_kernel"] += 64
+            per_kernel["ambi_enumerate_kernel"] += R * K                 # every order written once (one byte per node)
+            stored_table_bytes += R * row_bytes(K)
+            per_kernel["ambi_first_kernel"] += E * K + 2 * E * L         # orders read until the first valid one, bkp written
+            # bkp read, path written; the path after indelBFB is written only when indelBFB changed it
+            per_kernel["ambi_finish_kernel"] += 2 * L + 4 * P + (4 * P2 if r["path_indel_stored"] else 0)
+            formula += 8 * n + 24 * mj + 16 * K + 2 * R * K + 4 * E * L + 4 * P
+        # every kernel is launched once per slice and step (slices run on separate streams and overlap); kernel_times() is
+        # the average duration of ONE launch, so the bytes are taken per launch as well
+        slices = max(1, batch.slices())
+        dom_ms = ktimes.get(dom, float("nan"))
+        dom_bytes = per_kernel.get(dom, 0) / slices
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms and dom_ms > 0 else None
+        # HBM traffic by the PMC counters (rocprofv3 --pmc passes of this very command, corrected as profiles/README.md
+        # describes; profiles/traffic_r04.json, written by profiles/tools/collect.sh + summarize): per launch of the dominant
+        # kernel, and summed over every kernel of a step
+        traffic, step_traffic = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic_r04.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("kernel") == dom and tj.get("batch") == B and tj.get("slices", 1) == slices and tj.get("workload") == "%d/%d/%s/K%d/sv%d" % (args.segs, args.juncs, args.tier, args.K, args.sv_every):
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    step_traffic = tj.get("hbm_bytes_per_step_all_kernels")
+            except Exception:
+                traffic = None
+        stored = (stored_table_bytes / slices) if dom == "ambi_enumerate_kernel" else None
+        stored_rate = stored / (dom_ms * 1e-3) / 1e9 if stored and dom_ms and dom_ms > 0 else None
+        roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": (achieved / HBM_PEAK_GBPS) if achieved else None, "traffic": traffic,
+                    "algorithmic_bytes_per_launch": dom_bytes, "kernel_ms": dom_ms, "launches_per_step": slices,
+                    # the same launch counted in the bytes the table really has: the engine stores a row at 5 bits per node (12 bytes at
+                    # K = 19 where SURVEY 8d's algorithmic figure, used for `achieved`, counts 19), so `traffic` is BELOW the algorithmic bytes
+                    "stored_bytes_per_launch": stored, "stored_GBps": stored_rate, "stored_frac": (stored_rate / HBM_PEAK_GBPS) if stored_rate else None,
+                    "row_layout": "5 bits per node up to 32 nodes, 6 up to 63 (lossless; ambi_batch_unit_orders unpacks), one byte per node above",
+                    "algorithmic_frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
+                    "dominant_by": "largest HIP-event duration among the kernels whose duration is set by their own work (warm-up steps; re-measured over the timed steps); the paced finish spans are ranked in time_ranking and sit in critical_path",
+                    "time_ranking": time_ranking,
+                    "critical_path": critical,
+                    "all_kernels_ms": ktimes, "all_kernels_note": "%s: HIP events over the timed steps; the other kernels: over the warm-up steps" % dom,
+                    "step_hbm_bytes_pmc": step_traffic,
+                    "step_hbm_GBps_pmc": (step_traffic / (dt / args.steps) / 1e9) if step_traffic else None}
 
     # ---- CPU baseline: the oracle (a single-thread port of the reference path) on this box's host cores ----
     cpu = None
-    if args.cpu_seconds > 0 and world == 1:      # rank 0 at N = 1 only
+    if args.full and args.cpu_seconds > 0 and world == 1:      # rank 0 at N = 1 only
         from oracle import oracle_py
         oracle_py.build(ref=False)
         spent, recon, whole, cnt = 0.0, 0.0, 0.0, 0
@@ -328,7 +405,7 @@ def main():
     # computes; the host waits for step i-1's slot while step i runs.  A sampled subset is expanded on the host and compared with
     # the downloaded paths.
     host_paths = None
-    if world == 1 and args.host_paths:
+    if args.full and world == 1 and args.host_paths:
         def host_loop(k):
             for i in range(k):
                 batch.run(0, stream); batch.runs_to_host(1, i % 2, stream)
@@ -358,7 +435,7 @@ def main():
     # DESIGN.md section 7): a stream of the caller's own from torch's pool; and, in a child process, the legacy default stream behind
     # a one-rank RCCL group (init_process_group + one all_reduce first), which is what every rank of an N > 1 job looks like.
     streams_leg = None
-    if world == 1 and args.streams_leg:
+    if args.full and world == 1 and args.streams_leg:
         own = torch.cuda.Stream()
         for _ in range(max(args.warmup, 1)):
             batch.run(0, own.cuda_stream)
@@ -394,7 +471,7 @@ def main():
     # The host-side cost per call and the loss against one share are the figures that carry over to N devices (where the shares do not
     # compete for one GPU); no scaling curve is claimed from this.
     sharded = None
-    if world == 1 and args.sharded_leg:
+    if args.full and world == 1 and args.sharded_leg:
         sharded = {}
         for k in (1, 2, 4):
             sb = api.Batch(lib)
@@ -422,7 +499,7 @@ def main():
     # every topological order (LGM.cpp:3380-3409) and so does the headline step; in default mode nothing reads that table
     # (the scan reads the first orders the lattice stage unranks), so this is what the reconstructions alone cost.
     lazy = None
-    if world == 1 and args.lazy:
+    if args.full and world == 1 and args.lazy:
         for _ in range(max(args.warmup, 1)):
             batch.run(api.FLAG_LAZY_ORDERS, stream)
         batch.wait(); torch.cuda.synchronize()
@@ -442,7 +519,7 @@ def main():
     # run under the HBM-bound enumerate kernel of the other.  Reported beside the headline value, which stays the plain
     # one-batch-after-the-other measurement; same units, every step a complete pass over one batch.
     pipelined = None
-    if args.pipelined and world == 1:
+    if args.full and args.pipelined and world == 1:
         other = api.Batch(lib)
         other.configure(target_lanes=args.target_lanes)
         for g, (lh, sols) in zip(graphs, files):
@@ -471,7 +548,7 @@ def main():
     # the same with the upload of the unit and the download of its path included; the CPU figure is the oracle on the
     # SAME sample (stages #7,#8,#11-#16,#20), so the ratio compares like with like.
     single = None
-    if args.single_reps > 0 and world == 1:
+    if args.full and args.single_reps > 0 and world == 1:
         one = api.Batch(lib)
         one.add_chromosome_sol(graphs[0], 0, files[0][1][0])
         # The one-sample batch runs on a stream of the caller's own, not on the legacy default stream: its implicit ordering
@@ -580,7 +657,7 @@ def main():
     # reference spends its non-solver time (O(n * numPat^2) coefficient loop, 313 s at 256 segments);
     # here the same rows come from the closed form: on the host (O(nnz), one core) or written by ambi_ilp_fill_kernel.
     ilp = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             prep = batch.unit_prepare(0, args.segs)
             g0 = graphs[0]
@@ -606,7 +683,7 @@ def main():
     # ---- --all (LGM.cpp:3672-3695): every order of every sample evaluated -- the mode in which the enumeration is consumed.
     # Fused unrank + evaluate kernel over all (sample, 64-order chunk) work items, one launch per orientation pass.
     all_mode = None
-    if args.all_steps > 0 and world == 1:
+    if args.full and args.all_steps > 0 and world == 1:
         batch.set_timing(True)
         batch.run(api.FLAG_ALL, stream); batch.wait()          # untimed: bitmap allocation
         torch.cuda.synchronize()
@@ -631,7 +708,7 @@ def main():
     out = {
         "metric": "BFB reconstructions/sec (synthetic .lh, 256 seg) at 1/2/4/8 MI355X",
         "value": value, "unit": "reconstructions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": args.full,
         "dtype": "u8/int16 (node ids, stored as 5-bit fields of the order table / breakpoint cells; f64 copy numbers)", "data": "synthetic",
         "config": {"workload": "synthetic %d-seg/%d-junc .lh, %s DAG tier K=%d, planted .sol, %s; every %s sample carries 2 deletions + 1 duplication that edit the path (indelBFB with edits inside the timed region); %d samples per GPU resident in HBM"
                                % (args.segs, args.juncs, args.tier, args.K, "--all mode" if args.mode == "all" else "default CLI mode",

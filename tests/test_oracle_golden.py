@@ -45,12 +45,15 @@ def test_reader_against_reference_fixture(oracle, name, lh):
     assert oracle.graph_dump(os.path.join(ROOT, lh)) == gold
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference sources only exist in the build container")
 def test_reader_against_live_reference(oracle):
-    for lh in ["tests/data/readme6.lh", "tests/data/quirks.lh", "tests/golden/syn24.lh"]:
+    """The reader against the reference graph model: its live output where build() compiled it (oracle/_ref), else its
+    output recorded in tests/golden/graph_*.json."""
+    for name, lh in [("readme6", "tests/data/readme6.lh"), ("quirks", "tests/data/quirks.lh"), ("syn24", "tests/golden/syn24.lh")]:
         p = os.path.join(ROOT, lh)
         ref = oracle.ref_graph_dump(p)
-        assert ref is not None and ref["ok"]
+        if ref is None:
+            ref = json.load(open(os.path.join(GOLD, "graph_%s.json" % name)))
+        assert ref["ok"]
         assert oracle.graph_dump(p) == ref
 
 
