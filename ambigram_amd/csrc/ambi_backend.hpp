@@ -17,7 +17,6 @@ struct EngineConfig {
     int32_t block_scratch_lds = 16384;   // LDS of the image-build kernel (automaton copy; env AMBI_BLOCK_SCRATCH_LDS overrides)
     int32_t block_max = 256;         // largest suffix block in rows (env AMBI_BLOCK_MAX overrides; rows of a byte per node: 128 / 192 / 256 / 320 measure the same, profiles/r01_slices.md; 5-bit rows: 64 / 96 / 128 / 192 / 256 / 320 / 384 / 512 = 1.47 / 1.01 / 0.918 / 0.92 / 0.900 / 0.903 / 0.914 / 1.00 ms per step, profiles/r03_notes.md; an image that does not fit the LDS budget sends the unit down the general path)
     int32_t target_lanes = 524288;   // enumerate kernel: rows of the batch are spread over about this many lanes
-    int32_t slices = 0;              // unit ranges run on separate streams (0: automatic; env AMBI_SLICES overrides)
 };
 
 struct KernelTime { const char* name; float ms; float start_ms = -1.f, end_ms = -1.f; };   // start / end: from the start of the run's first kernel (mean over the timed runs; -1: not known)
@@ -68,7 +67,7 @@ class Backend {
     virtual const std::vector<KernelTime>& kernel_times() = 0;
     virtual int64_t order_bytes_written() const = 0;
     virtual size_t object_bytes() const = 0;   // sizeof the concrete backend (diagnostics: ambi_batch_destroy's quarantine mode)
-    virtual int slice_count() const { return 1; }   // launches of every kernel per run
+    virtual int slice_count() const { return 1; }   // launches of every kernel per run (ambi_batch_slices: always one)
     // --all (run with FLAG_ALL, after wait): valid orders of pass 0 (first orientation) / pass 1 (flipped orientation,
     // empty unless the last order of pass 0 is invalid), and the paths of a range of them (cells: count x stride int32)
     virtual int all_count(int unit, int pass, int64_t* count) = 0;

@@ -94,13 +94,13 @@ AMBI_HD UnitLayout unit_layout(int n, int bkp_cap, int path_cap, int out_cap) {
 }
 
 // kernel argument block (device pointers)
-// A batch is run as one or more SLICES (contiguous unit ranges) whose kernel chains are issued on different HIP streams,
-// so that the HBM-bound enumerate kernel of one slice overlaps the latency-bound kernels of the others.  Per-unit
-// arrays are indexed by the GLOBAL unit index  unit_base + local index; blk_off / orders_needed are per slice.
+// A launch covers the units [unit_base, unit_base + n_units) and the order arena from arena_base on; per-unit arrays are
+// indexed by the GLOBAL unit index  unit_base + local index.  The engine launches every kernel over the whole batch
+// (unit_base = 0, arena_base = 0).
 struct BatchArgs {
-    int32_t n_units;             // units of this slice
-    int32_t unit_base;           // first unit of this slice
-    int64_t arena_base;          // byte offset of this slice's region inside the order arena
+    int32_t n_units;             // units of this launch
+    int32_t unit_base;           // first unit of this launch
+    int64_t arena_base;          // byte offset of this launch's region inside the order arena
     uint32_t flags;
     int32_t first_budget;        // orders the first-valid kernel tries per orientation before declaring PENDING
     int32_t target_lanes;        // enumerate kernel: lanes to spread the rows of the batch over (sets rows per lane)
@@ -140,15 +140,15 @@ struct BatchArgs {
     // order table
     uint8_t* first_rows;         // [U][first_budget][kFirstRowStride] the first orders of every unit, unranked by the prepare stage (nullptr: the scan reads the order table)
     uint8_t* order_arena;
-    int64_t order_arena_bytes;   // bytes of this slice's region
-    int64_t* blk_off;            // [n_units+1] enumerate work-block prefix of this slice (local index)
+    int64_t order_arena_bytes;   // bytes of this launch's region
+    int64_t* blk_off;            // [n_units+1] enumerate work-block prefix of this launch (local index)
     int32_t* rows_per_lane;      // [U]   T of the unit (global index)
     int32_t* n_pending;          // [1]   whole batch
-    int64_t* orders_needed;      // [1] bytes the order tables of this slice need (for arena sizing)
+    int64_t* orders_needed;      // [1] bytes the order tables of this launch need (for arena sizing)
     // scratch for indel grouping (per unit: sv[m], grp[2m+4] ints, taken[m] bytes)
     int32_t* scratch_i32;
     int64_t* scratch_off;        // [U] offset (ints) into scratch_i32
-    // single-slice runs hand the two host-visible scalars over without copy commands: the prepare kernel zeroes
+    // a run hands the two host-visible scalars over without copy commands: the prepare kernel zeroes
     // n_pending, the plan kernel stores orders_needed and the finish kernel n_pending straight into pinned host memory
     int32_t zero_pending;        // 1: block 0 of the prepare kernel zeroes *n_pending
     int32_t* host_pending;       // device address of a pinned host int32 (nullptr: the host copies n_pending itself)

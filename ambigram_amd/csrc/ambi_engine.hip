@@ -4,7 +4,7 @@
 //   ambi_prepare_kernel           1 wave  / unit   junction ends staged into LDS; getJuncCN, bias, getIndelBias,
 //                                                  targetCN, constructDAG; order-ideal lattice (level-synchronous
 //                                                  search in LDS), completion counts, frozen automaton; R
-//   ambi_plan_kernel              1 block / slice  64-bit scans: order-table offsets, enumerate work blocks
+//   ambi_plan_kernel              1 block / batch  64-bit scans: order-table offsets, enumerate work blocks
 //   ambi_blocks_build_kernel      1 block / unit   block-emission image (block directory + suffix rows) -> HBM
 //   ambi_enumerate_blocks_kernel  1 block / work block: image -> LDS, rows streamed block by block with fully
 //                                                  coalesced 16-byte stores                       <- HBM-bound
@@ -723,7 +723,7 @@ __global__ __launch_bounds__(64) void ambi_order_paths_kernel(BatchArgs A, int u
     if (g.tid() == 0) lengths[j] = P;
 }
 
-// Full finish stage.  unit_list == nullptr: every unit of the slice (one workgroup each).  With a list: the listed units;
+// Full finish stage.  unit_list == nullptr: every unit of the batch (one workgroup each).  With a list: the listed units;
 // list_count == nullptr: one workgroup per entry (host-built list of the slow path), else the list is the one the lean
 // kernel in front of this launch filled on the device (refin_list / refin_count) and the workgroups share it in strides
 // -- no host round trip between the two kernels.
@@ -768,7 +768,7 @@ __global__ __launch_bounds__(256) AMBI_EDIT_ATTR void ambi_finish_edit_kernel(Ba
     }
 }
 
-// Lean finish (ambi_stages.hpp: stage_finish_lean): every unit of the slice; units it cannot take are counted in
+// Lean finish (ambi_stages.hpp: stage_finish_lean): every unit of the batch; units it cannot take are counted in
 // n_pending with status ST_REFINISH.  The last workgroup to finish reports n_pending to the host.
 __global__ __launch_bounds__(256) AMBI_LEAN_ATTR void ambi_finish_lean_kernel(BatchArgs A, const int32_t* unit_list = nullptr, int list_count = 0) {
     __shared__ int scratch[40];
@@ -794,25 +794,6 @@ __global__ __launch_bounds__(256) AMBI_LEAN_ATTR void ambi_finish_lean_kernel(Ba
                 *A.host_pending = atomicAdd(A.n_pending, 0);
                 *A.blocks_done = 0;
             }
-        }
-    }
-}
-
-// The lean stage with ONE WAVEFRONT per unit: the stage is a chain of short dependent phases (offsets, SV collection, look-ups,
-// output junctions) in which the 256 threads of the workgroup form mostly wait for each other at barriers -- a CU gets through one
-// unit per ~10 us whether one or five such workgroups are resident (profiles/r04_notes.md).  A lone wavefront has no barriers, a
-// quarter of the registers and the same group memory per unit, so several units per CU are in flight beside the order-table kernel.
-__global__ __launch_bounds__(64) AMBI_LEAN_ATTR void ambi_finish_lean_wave_kernel(BatchArgs A) {
-    WaveGroup g;
-    for (int i = (int)blockIdx.x; i < A.n_units; i += (int)gridDim.x) {
-        stage_finish_lean(g, A, A.unit_base + i, ambi_lds);
-        g.sync();
-    }
-    if (A.host_pending && threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(A.blocks_done, 1) == (int)gridDim.x - 1) {
-            *A.host_pending = atomicAdd(A.n_pending, 0);
-            *A.blocks_done = 0;
         }
     }
 }
@@ -983,7 +964,9 @@ struct PinnedWords {                    // what kernels write into host memory (
 struct TimingEvents { const char* name; hipEvent_t a, b; };
 struct Lease {
     int device = 0;
-    hipStream_t side[3][3] = {};        // [back, full, first][default, lowest, highest priority], created on first use
+    // side streams, created on first use: lean finish, direct full finish, scan for the first valid order (highest dispatch
+    // priority), lattice kernel of a small batch
+    hipStream_t back_stream = nullptr, full_stream = nullptr, first_stream = nullptr, lattice_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_prep = nullptr, ev_back = nullptr, ev_first = nullptr, ev_full = nullptr, ev_plan = nullptr, ev_express = nullptr, ev_lat = nullptr, ev_tail = nullptr;
     PinnedWords* h_words = nullptr; PinnedWords* dh_words = nullptr;
     uint8_t* d_block = nullptr; int64_t d_block_bytes = 0;      // inputs + working set + result blob of the batch
@@ -998,7 +981,6 @@ struct Lease {
     hipStream_t run_stream = nullptr;   // own_stream(): for callers without a stream (ambi_batch_run_sharded's shares)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
     std::vector<TimingEvents> evs;
-    std::vector<hipStream_t> slice_streams; std::vector<hipEvent_t> slice_events;     // AMBI_SLICES experiments
     long uses = 0;
     int32_t seq = 0;   // run sequence numbers (the kernels report completion by storing the run's number into a pinned word)
 };
@@ -1046,26 +1028,19 @@ class DevicePool {
         free_.push_back(L);
     }
 };
-// a side stream of the lease: kind 0 lean finish / scan, 1 direct full finish, 2 scan ahead; prio 0 default, 1 lowest, 2 highest
-static int lease_stream(Lease* L, int kind, int prio, hipStream_t* out) {
-    static const bool shared = [] { const char* e = ambi_env("AMBI_SHARE_STREAMS"); return e && atoi(e) != 0; }();
-    if (shared && L->device >= 0 && L->device < 16) {
-        // experiment: one set of side streams per DEVICE, used by every lease (several resident batches then need no more hardware queues than one)
-        static std::recursive_mutex mu; static Lease* holder[16] = {};
-        std::lock_guard<std::recursive_mutex> lk(mu);
-        if (!holder[L->device]) holder[L->device] = L;
-        if (holder[L->device] != L) { const int rc = lease_stream(holder[L->device], kind, prio, out); if (!rc) L->side[kind][prio] = *out; return rc; }
-    }
-    if (!L->side[kind][prio]) {
+// a side stream of the lease (one of its members): created on first use, with the device's highest dispatch priority if `highest`
+// and the device has priorities
+static int lease_stream(hipStream_t* side, bool highest, hipStream_t* out) {
+    if (!*side) {
         int least = 0, greatest = 0;
-        if (prio != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-            HIP_CK(hipStreamCreateWithPriority(&L->side[kind][prio], hipStreamNonBlocking, prio == 1 ? least : greatest));
+        if (highest && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
+            HIP_CK(hipStreamCreateWithPriority(side, hipStreamNonBlocking, greatest));
         } else {
-            if (prio != 0) { (void)hipGetLastError(); return lease_stream(L, kind, 0, out); }   // no priorities on this device
-            HIP_CK(hipStreamCreateWithFlags(&L->side[kind][0], hipStreamNonBlocking));
+            if (highest) (void)hipGetLastError();   // no priorities on this device
+            HIP_CK(hipStreamCreateWithFlags(side, hipStreamNonBlocking));
         }
     }
-    *out = L->side[kind][prio];
+    *out = *side;
     return 0;
 }
 // ---- side streams that really run beside the caller's stream ----
@@ -1236,8 +1211,6 @@ class HipBackend : public Backend {
     BatchArgs A_{};
     int lds_prepare_ = 0, lds_first_ = 0, lds_finish_ = 0, lds_finish_lean_ = 0, lds_enum_ = 0;
     bool lean_finish_ = true;   // env AMBI_LEAN_FINISH=0: every unit through the full finish stage
-    int lean_threads_ = 256;   // env AMBI_LEAN_THREADS (128 / 256): threads per workgroup of the lean finish kernel
-    int lean_wave_ = 0, lean_wave_grid_ = 0;   // env AMBI_LEAN_WAVE=1: the lean stage on one wavefront per unit; AMBI_LEAN_WAVE_GRID: its wavefronts
     int finish_grid_ = 0;       // workgroups of the lean finish kernel; 0 = sized per run (env AMBI_FINISH_GRID overrides)
     int32_t* d_blocks_done_ = nullptr; int32_t* d_refin_list_ = nullptr; int32_t* d_refin_count_ = nullptr;
     uint32_t* d_anblk_ = nullptr; uint8_t* d_adepth_ = nullptr;
@@ -1249,16 +1222,8 @@ class HipBackend : public Backend {
     int general_path_ = -1;   // units that take the general enumerate path: -1 unknown (first run), else the count (inputs are immutable)
     int shared_units_ = -1;   // units whose table is written by several workgroups: -1 unknown, else the count
     long timed_runs_ = 0;
-    // slices: contiguous unit ranges whose kernel chains run on different streams (see BatchArgs)
-    static constexpr int kMaxSlices = 16;
-    int n_slices_ = 1;
-    std::vector<int> slice_lo_;                        // [n_slices_+1]
-    std::vector<int64_t> slice_base_, slice_bytes_;    // arena regions
-    std::vector<hipStream_t> side_;                    // n_slices_-1 internal streams (slice 0 runs on the caller's); owned by the lease
     hipEvent_t ev_fork_ = nullptr;
-    std::vector<hipEvent_t> ev_join_, ev_stage_;
-    bool stagger_ = true;
-    // overlap of [first valid order, finish] with the enumerate kernel (one slice, arena sized): own stream + two events (the lease's)
+    // overlap of [first valid order, finish] with the enumerate kernel: own stream + two events (the lease's)
     bool overlap_back_ = false, want_overlap_ = true;
     hipStream_t back_stream_ = nullptr;
     hipEvent_t ev_prep_ = nullptr, ev_back_ = nullptr, ev_first_ = nullptr, ev_full_ = nullptr;
@@ -1269,15 +1234,15 @@ class HipBackend : public Backend {
     int full_threads_ = 1024;  // env AMBI_FULL_THREADS: threads per workgroup of the direct full-finish launch (256 / 512 / 1024)
     bool classed_ = true;              // env AMBI_STREAM_CLASSES=0: side streams by creation order (rounds 1-3) instead of by observed dispatch class
     hipStream_t classed_for_ = (hipStream_t)-1; hipStream_t classed_streams_[3] = {nullptr, nullptr, nullptr};
-    bool want_back_ = false, want_full_ = false, want_first_ = false, want_lattice_ = false;
-    hipStream_t first_stream_ = nullptr; int first_ahead_ = 3;   // env AMBI_FIRST_AHEAD: 1 the enumerate kernel waits for the scan, 2 the scan on a highest-priority stream beside it
+    hipStream_t first_stream_ = nullptr;   // the scan for the first valid order, started beside the plan kernel (launch_front)
     int32_t* d_direct_list_ = nullptr; int direct_n_ = 0, direct_grid_ = 1024;
     int32_t* d_edit_list_ = nullptr; bool direct_edit_ = true; int lds_finish_edit_ = 0, edit_grid_ = 1024;   // env AMBI_DIRECT_EDIT: these units through stage_finish_edit first (ambi_finish_edit_kernel), the ext launch behind it for what that hands on
     // express path (small batches): one kernel reconstructs every unit whose first order assembles; results are complete at ev_express_
-    int express_threads_ = 512;   // env AMBI_EXPRESS_THREADS (256 / 512 / 1024): the serial stages use three wavefronts, the finish stage and the mailbox copy all of them
+    // (measured, one 256-segment sample: 256 / 512 / 1024 threads = 79.7 / 76.8 / 79.2 us run -> results)
+    static constexpr int kExpressThreads = 512;   // the serial stages use three wavefronts, the finish stage and the mailbox copy all of them
     int express_units_ = 32, lds_express_ = 0, lds_lattice_ = 0, lds_lattice_own_ = 0;
     bool lazy_ = false, tables_written_ = false;   // FLAG_LAZY_ORDERS: the run leaves the order tables out; they are written on demand
-    bool side_lattice_ = false, flushed_ = false; hipStream_t lattice_stream_ = nullptr;   // env AMBI_SIDE_LATTICE=0: the lattice kernel behind the express kernel (round 2)
+    bool side_lattice_ = false, flushed_ = false; hipStream_t lattice_stream_ = nullptr;   // small batches: the lattice kernel beside the express kernel
     uint64_t* d_lat_R_ = nullptr; int32_t* d_lat_status_ = nullptr; int64_t* d_lat_sum_ = nullptr;
     bool express_ = false;
     hipEvent_t ev_express_ = nullptr;
@@ -1303,7 +1268,7 @@ class HipBackend : public Backend {
     bool emit_lds_auto_ = true;
     bool emit_lds_tight_ = true;   // env AMBI_EMIT_LDS_TIGHT=0: the whole 160 KB / k share
     double avg_path_ = 0;
-    int enum_threads_ = 256;  // threads per workgroup of the block-emission kernel (env AMBI_ENUM_THREADS: 256 / 512 / 1024)
+    static constexpr int kEnumThreads = 256;   // threads per workgroup of the block-emission kernel (512 / 1024 measured slower)
     std::chrono::steady_clock::time_point t_run_; double t_launched_ = 0;   // env AMBI_DEBUG_LATENCY
     bool debug_ = false;      // env AMBI_DEBUG: budgets and grids chosen; guard words of the direct path areas checked at wait()
 
@@ -1313,8 +1278,7 @@ class HipBackend : public Backend {
     void sync_all() {
         if (!lease_) return;
         if (inflight_) { (void)hipStreamSynchronize(stream_); inflight_ = false; }
-        for (auto& kind : lease_->side) for (hipStream_t s : kind) if (s) (void)hipStreamSynchronize(s);
-        for (hipStream_t s : lease_->slice_streams) (void)hipStreamSynchronize(s);
+        for (hipStream_t s : {lease_->back_stream, lease_->full_stream, lease_->first_stream, lease_->lattice_stream}) if (s) (void)hipStreamSynchronize(s);
         if (lease_->copy_stream) (void)hipStreamSynchronize(lease_->copy_stream);
         if (lease_->run_stream) (void)hipStreamSynchronize(lease_->run_stream);
         for (hipStream_t s : classed_streams_) if (s) (void)hipStreamSynchronize(s);
@@ -1395,7 +1359,7 @@ class HipBackend : public Backend {
         c.take(&d_ilvl_off_, U * (kMaxNodes + 3)); c.take(&d_icounter_, 2 * U); c.take(&d_ipos_, (size_t)H.ideal_slots);
         c.take(&d_aavail_, (size_t)H.ideal_slots / 2 + 1); c.take(&d_acnt_, (size_t)H.ideal_slots / 2 + 1); c.take(&d_acbase_, (size_t)H.ideal_slots / 2 + U + 1);
         c.take(&d_achild_, (size_t)H.ideal_slots * 4 + 8); c.take(&d_anblk_, (size_t)H.ideal_slots / 2 + 1); c.take(&d_adepth_, (size_t)H.ideal_slots / 2 + 8);
-        c.take(&d_edit_list_, direct_list.size()); c.take(&d_blk_off_, U + kMaxSlices + 1); c.take(&d_rows_, U); c.take(&d_needed_, kMaxSlices); c.take(&d_lat_R_, U); c.take(&d_lat_status_, U);
+        c.take(&d_edit_list_, direct_list.size()); c.take(&d_blk_off_, U + 1); c.take(&d_rows_, U); c.take(&d_needed_, 1); c.take(&d_lat_R_, U); c.take(&d_lat_status_, U);
         c.take(&d_scratch_, (size_t)H.scratch_ints + 8); c.take(&d_pack_off_, U + 1); c.take(&d_refin_list_, U);
         c.take(&d_first_rows_, U * (size_t)(cfg_.first_budget > 0 ? cfg_.first_budget : 1) * kFirstRowStride);
         const size_t img_stride = (size_t)std::max(block_lds_, ((160 * 1024) / 3) & ~15);   // (the budget per workgroup may be re-chosen after the first run)
@@ -1459,10 +1423,6 @@ class HipBackend : public Backend {
         lds_finish_lean_ = (int)finish_lean_work_bytes(H.max_n, H.max_m, H.max_bkp);
         { const char* e = ambi_env("AMBI_LEAN_FINISH"); lean_finish_ = e ? atoi(e) != 0 : true; }
         { const char* e = ambi_env("AMBI_FINISH_GRID"); finish_grid_ = e ? atoi(e) : 0; if (finish_grid_ < 0) finish_grid_ = 0; }
-        { const char* e = ambi_env("AMBI_LEAN_WAVE"); lean_wave_ = e ? atoi(e) : 0; }
-        // (measured, lean grid re-tuned for each: 128 threads 0.94-1.00, 256 threads 0.90 ms per step on one box)
-        { const char* e = ambi_env("AMBI_LEAN_THREADS"); lean_threads_ = e ? atoi(e) : 256; if (lean_threads_ != 128) lean_threads_ = 256; }
-        { const char* e = ambi_env("AMBI_LEAN_WAVE_GRID"); lean_wave_grid_ = e ? atoi(e) : 0; if (lean_wave_grid_ < 0) lean_wave_grid_ = 0; }
         {   // the general enumerate kernel serves ordinary units only (wide ones have their own table kernel): its per-lane stacks are
             // sized by the largest ORDINARY unit -- with the wide units' node count they outgrew a CU's group memory at 255 nodes
             int mk = 1;
@@ -1489,7 +1449,7 @@ class HipBackend : public Backend {
             std::lock_guard<std::mutex> lk(mu);
             if (!((done >> (L->device & 63)) & 1ull)) {
                 const void* fns[] = {(const void*)ambi_blocks_build_kernel, (const void*)ambi_prepare_kernel, (const void*)ambi_first_kernel, (const void*)ambi_resolve_kernel,
-                                     (const void*)ambi_finish_kernel, (const void*)ambi_finish_ext_kernel, (const void*)ambi_finish_edit_kernel, (const void*)ambi_finish_lean_kernel, (const void*)ambi_finish_lean_wave_kernel,
+                                     (const void*)ambi_finish_kernel, (const void*)ambi_finish_ext_kernel, (const void*)ambi_finish_edit_kernel, (const void*)ambi_finish_lean_kernel,
                                      (const void*)ambi_enumerate_kernel<0>, (const void*)ambi_enumerate_kernel<1>, (const void*)ambi_enumerate_kernel<2>,
                                      (const void*)ambi_enumerate_blocks_kernel<0>, (const void*)ambi_enumerate_blocks_kernel<1>, (const void*)ambi_enumerate_blocks_kernel<2>,
                                      (const void*)ambi_express_kernel, (const void*)ambi_lattice_kernel, (const void*)ambi_lattice_own_kernel, (const void*)ambi_search_kernel, (const void*)ambi_all_kernel,
@@ -1504,63 +1464,35 @@ class HipBackend : public Backend {
         avg_path_ = 0;
         for (const UnitIn& un : H.units) avg_path_ += un.path_cap;
         avg_path_ /= (double)(U > 0 ? U : 1);
-        // slices: env AMBI_SLICES or the configuration; 0 = automatic (4 when the batch is large enough to fill the
-        // chip four times over, else 1)
-        {
-            const char* env = ambi_env("AMBI_SLICES");
-            int want = env ? atoi(env) : cfg.slices;
-            // Measured on MI355X (profiles/r01_slices.md): the per-unit kernels already fill the issue slots of the chip,
-            // so slicing brings nothing on this workload (2 slices: +3 %, 4 staggered slices: -17 %); default 1.
-            if (want <= 0) want = 1;
-            if (want > kMaxSlices) want = kMaxSlices;
-            if (want > (int)U) want = (int)U > 0 ? (int)U : 1;
-            n_slices_ = want;
-            slice_lo_.assign(n_slices_ + 1, 0);
-            for (int s = 0; s <= n_slices_; s++) slice_lo_[s] = (int)((int64_t)U * s / n_slices_);
-            slice_base_.assign(n_slices_, 0); slice_bytes_.assign(n_slices_, 0);
-            // (streams and events of the slices belong to the lease: created once, reused by every later batch)
-            while ((int)L->slice_streams.size() < n_slices_ - 1) { hipStream_t st; HIP_CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); L->slice_streams.push_back(st); }
-            while ((int)L->slice_events.size() < 2 * (n_slices_ - 1)) { hipEvent_t e; HIP_CK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); L->slice_events.push_back(e); }
-            side_.assign(L->slice_streams.begin(), L->slice_streams.begin() + (n_slices_ - 1));
-            ev_join_.assign(L->slice_events.begin(), L->slice_events.begin() + (n_slices_ - 1));
-            ev_stage_.assign(L->slice_events.begin() + (n_slices_ - 1), L->slice_events.begin() + 2 * (n_slices_ - 1));
-            { const char* e2 = ambi_env("AMBI_STAGGER"); stagger_ = e2 ? atoi(e2) != 0 : true; }
-            { const char* e4 = ambi_env("AMBI_ENUM_THREADS"); enum_threads_ = e4 ? atoi(e4) : 256; if (enum_threads_ != 512 && enum_threads_ != 1024) enum_threads_ = 256; }
-            { const char* e3 = ambi_env("AMBI_ENUM_GRID"); enum_grid_ = e3 ? atoi(e3) : 16384; if (enum_grid_ < 1) enum_grid_ = 1; }   // >= work blocks: one block per workgroup, the rest exit (measured: 2048 -> 16384 workgroups = -8 % kernel time)
-        }
+        { const char* e3 = ambi_env("AMBI_ENUM_GRID"); enum_grid_ = e3 ? atoi(e3) : 16384; if (enum_grid_ < 1) enum_grid_ = 1; }   // >= work blocks: one block per workgroup, the rest exit (measured: 2048 -> 16384 workgroups = -8 % kernel time)
         { const char* e9 = ambi_env("AMBI_BUILD_IN_EMIT"); build_in_emit_ = e9 ? (atoi(e9) != 0) : 1; }
         { const char* e9 = ambi_env("AMBI_BLOCK_DFS"); block_dfs_ = e9 ? (atoi(e9) != 0) : 1; }
         { const char* e9 = ambi_env("AMBI_EMIT_INTERLEAVE"); emit_interleave_ = e9 ? (atoi(e9) != 0) : 1; }
         { const char* e5 = ambi_env("AMBI_OVERLAP_BACK"); want_overlap_ = e5 ? atoi(e5) != 0 : true; }
         back_stream_ = nullptr; full_stream_ = nullptr; first_stream_ = nullptr; direct_n_ = 0; d_direct_cells_ = nullptr; direct_slots_ = 0;
-        want_back_ = want_full_ = want_first_ = want_lattice_ = false;
         { const char* e = ambi_env("AMBI_STREAM_CLASSES"); classed_ = e ? atoi(e) != 0 : true; }
         std::vector<int32_t> dl;
-        if (want_overlap_ && n_slices_ == 1) {
-            // the stream of the lean finish kernel: default dispatch priority (AMBI_BACK_PRIORITY=1: lowest, round 1's setting
-            // -- with the scan out of the way early the finish kernels have the whole enumerate kernel to hide behind, and
-            // holding them back only lengthens the tail after it: 1.185 -> 1.168 ms per step, four interleaved runs)
-            { const char* e8 = ambi_env("AMBI_BACK_PRIORITY"); const bool low = e8 ? atoi(e8) != 0 : false;
-              if ((rc = lease_stream(L, 0, low ? 1 : 0, &back_stream_))) return rc; want_back_ = !low; }
-            { const char* e = ambi_env("AMBI_FIRST_AHEAD"); first_ahead_ = e ? atoi(e) : 3; }
+        if (want_overlap_) {
+            // the stream of the lean finish kernel: default dispatch priority (the lowest, round 1's setting, measured slower: with
+            // the scan out of the way early the finish kernels have the whole enumerate kernel to hide behind, and holding them
+            // back only lengthens the tail after it: 1.185 -> 1.168 ms per step, four interleaved runs)
+            if ((rc = lease_stream(&L->back_stream, false, &back_stream_))) return rc;
             // (direct full-stage launch: 512 threads with the path cells in device memory, 1024 with the cells in group memory --
             // measured, four interleaved runs: cells in group memory 1.151 ms per step; in device memory 256 / 512 / 1024
             // threads = 1.133 / 1.110 / 1.200)
             { const char* ee = ambi_env("AMBI_DIRECT_EXT"); direct_ext_ = ee ? atoi(ee) != 0 : true; }
             { const char* e = ambi_env("AMBI_FULL_THREADS"); full_threads_ = e ? atoi(e) : (direct_ext_ ? 512 : 1024); if (full_threads_ != 256 && full_threads_ != 512 && full_threads_ != 1024) full_threads_ = direct_ext_ ? 512 : 1024; }
-            if (first_ahead_ >= 2) { if ((rc = lease_stream(L, 2, 2, &first_stream_))) return rc; want_first_ = true; }
+            if ((rc = lease_stream(&L->first_stream, true, &first_stream_))) return rc;
             {   // units that go straight to the full finish stage (env AMBI_DIRECT_FULL=0: none, they pass through the lean stage first)
                 const char* e7 = ambi_env("AMBI_DIRECT_FULL"); const bool on = e7 ? atoi(e7) != 0 : true;
                 const char* e8 = ambi_env("AMBI_DIRECT_GRID"); direct_grid_ = e8 ? atoi(e8) : 1024; if (direct_grid_ < 1) direct_grid_ = 1;   // one workgroup per unit up to 1024 (measured: 64 / 128 / 256 / 512 workgroups for 512 units = 1.63 / 1.37 / 1.25 / 1.23 ms per step; without this launch 1.30)
                 if (on && lean_finish_) for (size_t u2 = 0; u2 < U; u2++) if (H.units[u2].direct_full) dl.push_back((int32_t)u2);
                 direct_n_ = (int)dl.size();
                 if (direct_n_ > 0) {
-                    // the direct full-finish stream: default priority, or the lowest (AMBI_FULL_PRIORITY=1: a few per cent on some
-                    // boxes).  The stream belongs to the lease and is never destroyed -- with round 2's per-batch create / destroy of
-                    // this priority stream a long soak showed stray writes into host memory.
-                    const char* e9 = ambi_env("AMBI_FULL_PRIORITY"); const int fp = e9 ? atoi(e9) : 0;   // 0 default, 1 lowest, 2 highest priority
-                    if ((rc = lease_stream(L, 1, fp == 1 ? 1 : (fp == 2 ? 2 : 0), &full_stream_))) return rc;
-                    want_full_ = fp == 0;
+                    // the direct full-finish stream: default priority.  The stream belongs to the lease and is never destroyed -- with
+                    // round 2's per-batch create / destroy of a priority stream here a long soak showed stray writes into host memory
+                    // (DESIGN.md 8b).
+                    if ((rc = lease_stream(&L->full_stream, false, &full_stream_))) return rc;
                     if (direct_ext_) lds_finish_ext_ = (int)finish_work_bytes(H.max_n, H.max_m, H.max_bkp, 0, H.max_out);
                     { const char* ed = ambi_env("AMBI_DIRECT_EDIT"); direct_edit_ = (ed ? atoi(ed) != 0 : true) && direct_ext_; }
                     { const char* eg = ambi_env("AMBI_EDIT_GRID"); edit_grid_ = eg ? atoi(eg) : 1024; if (edit_grid_ < 1) edit_grid_ = 1; }
@@ -1568,25 +1500,18 @@ class HipBackend : public Backend {
                     if (lds_finish_edit_ > kLdsLimit) direct_edit_ = false;
                 }
             }
-            // AMBI_ENUM_LDS_FLOOR (experiments): make the enumerate kernel ask for more LDS than its image needs, i.e. fewer
-            // of its workgroups per CU.  Measured (profiles/r01_slices.md): no floor is best -- the scan / finish
-            // workgroups slip in as enumerate workgroups retire.
-            { const char* e6 = ambi_env("AMBI_ENUM_LDS_FLOOR"); const int floor_lds = e6 ? atoi(e6) : 0; if (lds_blocks_ < floor_lds && floor_lds <= kLdsLimit) lds_blocks_ = floor_lds; }
         }
         {   // express path: small batches only, and only if a unit's whole working set fits one workgroup's group memory
             const char* e9 = ambi_env("AMBI_EXPRESS_UNITS"); express_units_ = e9 ? atoi(e9) : 32;
-            { const char* et = ambi_env("AMBI_EXPRESS_THREADS"); express_threads_ = et ? atoi(et) : 512; if (express_threads_ != 256 && express_threads_ != 1024) express_threads_ = 512; }   // (measured, one 256-segment sample: 256 / 512 / 1024 threads = 79.7 / 76.8 / 79.2 us run -> results)
             lds_express_ = (int)express_work_bytes(H.max_n, H.max_m, H.max_k, H.max_bkp, finish_path_cells_, H.max_out) + 64;
             lds_lattice_ = (int)(64 * 8 + kPrepLatticeBytes + 64);
             lds_lattice_own_ = (int)lattice_own_bytes(H.max_k) + 64;
-            const char* e8 = ambi_env("AMBI_SIDE_LATTICE");
-            side_lattice_ = (e8 ? atoi(e8) != 0 : true) && (int)U <= express_units_ && n_slices_ == 1;
-            if (side_lattice_ && (rc = lease_stream(L, 2, 0, &lattice_stream_))) return rc;
-            want_lattice_ = side_lattice_;
+            side_lattice_ = (int)U <= express_units_;
+            if (side_lattice_ && (rc = lease_stream(&L->lattice_stream, false, &lattice_stream_))) return rc;
         }
         // result mailbox in pinned host memory: batches that can take the express path, while the slots stay small
         mail_off_.assign(U, 0); mail_bytes_ = 0; mail_on_ = false; mail_valid_ = false;
-        if ((int)U <= express_units_ && n_slices_ == 1) {
+        if ((int)U <= express_units_) {
             for (size_t u2 = 0; u2 < U; u2++) { mail_off_[u2] = mail_bytes_; mail_bytes_ += mail_layout(H.units[u2].path_cap, H.units[u2].out_cap).total; }
             mail_on_ = mail_bytes_ <= kKeepMail;
             if (mail_on_ && (rc = lease_pinned_block(&L->h_mail, &L->dh_mail, &L->h_mail_bytes, mail_bytes_))) return rc;
@@ -1610,7 +1535,6 @@ class HipBackend : public Backend {
           if (capped && arena_bytes_ > atoll(cap)) arena_bytes_ = atoll(cap); }
         if ((rc = lease_device_block(&L->d_arena, &L->d_arena_bytes, arena_bytes_))) return rc;
         d_arena_ = L->d_arena;
-        for (int s = 0; s < n_slices_; s++) { slice_base_[s] = (arena_bytes_ / n_slices_ * s) & ~int64_t(order_align_ - 1); slice_bytes_[s] = (arena_bytes_ / n_slices_) & ~int64_t(order_align_ - 1); }
         // input image: same layout as the front of the device block; pinned staging (one asynchronous copy, queued by the
         // first run ahead of its kernels) or, for large batches, a plain buffer copied at once
         uint8_t* img;
@@ -1664,7 +1588,7 @@ class HipBackend : public Backend {
         return 0;
     }
 
-    // whole-batch argument block (pack kernels, slow path); slice_args() narrows it to one slice
+    // whole-batch argument block (pack kernels, slow path); args() adds what a run's kernels take on top
     void bind(uint32_t flags) {
         A_.n_units = (int32_t)hb().units.size(); A_.unit_base = 0; A_.arena_base = 0;
         A_.flags = flags; A_.first_budget = cfg_.first_budget; A_.target_lanes = cfg_.target_lanes;
@@ -1692,48 +1616,33 @@ class HipBackend : public Backend {
         A_.plan_seq = &lease_->dh_words->plan_seq; A_.late_flag = &lease_->dh_words->late_flag; A_.run_seq = run_seq_;
         A_.all_bits = d_all_bits_; A_.all_off = d_all_off_; A_.all_count = d_all_count_; A_.all_flags = d_all_flags_; A_.all_rank = all_rank_; A_.all_world = all_world_; { const char* e = ambi_env("AMBI_ALL_TABLE"); A_.all_rows_from_table = (e && atoi(e) != 0) ? 1 : 0; }
     }
-    BatchArgs slice_args(int s) const {
+    // the order arena as the tables use it: whole alignment units
+    int64_t arena_usable() const { return arena_bytes_ & ~int64_t(order_align_ - 1); }
+    BatchArgs args() const {   // the argument block of a run's kernels
         BatchArgs A = A_;
-        A.unit_base = slice_lo_[s]; A.n_units = slice_lo_[s + 1] - slice_lo_[s];
-        A.arena_base = slice_base_[s]; A.order_arena_bytes = slice_bytes_[s];
-        A.blk_off = d_blk_off_ + slice_lo_[s] + s;        // n_units + 1 private entries
-        A.orders_needed = d_needed_ + s;
-        // the rows of the WHOLE batch are spread over target_lanes lanes: a slice gets its share
-        A.target_lanes = cfg_.target_lanes / n_slices_ > 0 ? cfg_.target_lanes / n_slices_ : 1;
+        A.order_arena_bytes = arena_usable();
+        A.target_lanes = cfg_.target_lanes > 0 ? cfg_.target_lanes : 1;
         return A;
     }
-    hipStream_t slice_stream(int s) const { return s == 0 ? stream_ : side_[s - 1]; }
 
-    // Per-kernel HIP events on the stream of the slice.  A ring of kTimingSlots event sets lets a timed region of many
+    // Per-kernel HIP events on the caller's stream (or `on`).  A ring of kTimingSlots event sets lets a timed region of many
     // runs be averaged without a host sync per run: run r records into slot r % kTimingSlots.
     static constexpr int kTimingSlots = 64, kTimedKernels = 7;
-    void tick(const char* name, int slice, size_t idx, bool begin, hipStream_t on = (hipStream_t)-1) {
+    void tick(const char* name, size_t idx, bool begin, hipStream_t on = (hipStream_t)-1) {
         if (!timing_ || !((timing_mask_ >> idx) & 1u)) return;
         const size_t slot = (size_t)(timed_runs_ % kTimingSlots);
-        const size_t at = (slot * n_slices_ + slice) * kTimedKernels + idx;
+        const size_t at = slot * kTimedKernels + idx;
         while (evs().size() <= at) {
             Ev e{name, nullptr, nullptr};
             (void)hipEventCreate(&e.a); (void)hipEventCreate(&e.b);
             evs().push_back(e);
         }
         evs()[at].name = name;
-        (void)hipEventRecord(begin ? evs()[at].a : evs()[at].b, on == (hipStream_t)-1 ? slice_stream(slice) : on);
+        (void)hipEventRecord(begin ? evs()[at].a : evs()[at].b, on == (hipStream_t)-1 ? stream_ : on);
     }
 
-    void fork() {   // the side streams start behind everything already queued on the caller's stream
-        if (n_slices_ <= 1) return;
-        (void)hipEventRecord(ev_fork_, stream_);
-        for (auto st : side_) (void)hipStreamWaitEvent(st, ev_fork_, 0);
-    }
-    void join() {   // the caller's stream continues after all side streams
-        for (int s = 1; s < n_slices_; s++) {
-            (void)hipEventRecord(ev_join_[s - 1], side_[s - 1]);
-            (void)hipStreamWaitEvent(stream_, ev_join_[s - 1], 0);
-        }
-    }
-
-    void launch_front(int s, const BatchArgs& A) {   // prepare + plan of one slice
-        hipStream_t st = slice_stream(s);
+    void launch_front(const BatchArgs& A) {   // prepare + plan
+        hipStream_t st = stream_;
         first_launched_ = false;
         if (express_) {
             // express kernel (whole reconstruction of the units whose first order assembles; results complete at ev_express_),
@@ -1752,11 +1661,11 @@ class HipBackend : public Backend {
                 if (flushed_) (void)hipEventRecord(ev_fork_, st);
                 (void)hipStreamWaitEvent(lattice_stream_, flushed_ ? ev_fork_ : lease_->ev_tail, 0);
             }
-            tick("ambi_express_kernel", s, 0, true);
-            hipLaunchKernelGGL(ambi_express_kernel, dim3(A.n_units), dim3(express_threads_), lds_express_, st, Ax);
-            tick("ambi_express_kernel", s, 0, false);
+            tick("ambi_express_kernel", 0, true);
+            hipLaunchKernelGGL(ambi_express_kernel, dim3(A.n_units), dim3(kExpressThreads), lds_express_, st, Ax);
+            tick("ambi_express_kernel", 0, false);
             (void)hipEventRecord(ev_express_, st);
-            tick("ambi_plan_kernel", s, 1, true);
+            tick("ambi_plan_kernel", 1, true);
             if (side) {   // the lattice beside the express kernel, on a stream of its own; the plan kernel behind both
                 hipLaunchKernelGGL(ambi_lattice_own_kernel, dim3(A.n_units), dim3(64), lds_lattice_own_, lattice_stream_, A);
                 (void)hipEventRecord(lease_->ev_lat, lattice_stream_);
@@ -1764,56 +1673,36 @@ class HipBackend : public Backend {
             } else
             hipLaunchKernelGGL(ambi_lattice_kernel, dim3(A.n_units), dim3(64), lds_lattice_, st, A);
         } else {
-            tick("ambi_prepare_kernel", s, 0, true);
+            tick("ambi_prepare_kernel", 0, true);
             hipLaunchKernelGGL(ambi_prepare_kernel, dim3(A.n_units), dim3(64), lds_prepare_, st, A);
-            tick("ambi_prepare_kernel", s, 0, false);
+            tick("ambi_prepare_kernel", 0, false);
             // The scan for the first valid order reads what the prepare stage left (first rows, DAG) and rewrites the status;
-            // the plan stage reads and writes UnitOut::order_off only.  With first_ahead_ == 3 the scan therefore starts HERE,
-            // beside the plan kernel (one workgroup, 25 us during which the chip is otherwise idle) and the ramp of the
-            // enumerate kernel, instead of queueing behind 4096 enumerate workgroups for group memory.
-            first_launched_ = false;
-            static const bool one_event = [] { const char* e = ambi_env("AMBI_ONE_FRONT_EVENT"); return e && atoi(e) != 0; }();   // experiment: see below
-            if (overlap_back_ && first_ahead_ == 3 && !(one_event && !lazy_)) {
+            // the plan stage reads and writes UnitOut::order_off only.  With overlap the scan therefore starts HERE, beside the
+            // plan kernel (one workgroup, 25 us during which the chip is otherwise idle) and the ramp of the enumerate kernel,
+            // instead of queueing behind 4096 enumerate workgroups for group memory.
+            if (overlap_back_) {
                 (void)hipEventRecord(ev_prep_, st);
-                hipStream_t sf = first_stream_ ? first_stream_ : back_stream_;
-                (void)hipStreamWaitEvent(sf, ev_prep_, 0);
-                tick("ambi_first_kernel", s, 4, true, sf);
-                hipLaunchKernelGGL(ambi_first_kernel, dim3(A.n_units), dim3(64), lds_first_, sf, A);
-                tick("ambi_first_kernel", s, 4, false, sf);
-                (void)hipEventRecord(ev_first_, sf);
+                (void)hipStreamWaitEvent(first_stream_, ev_prep_, 0);
+                tick("ambi_first_kernel", 4, true, first_stream_);
+                hipLaunchKernelGGL(ambi_first_kernel, dim3(A.n_units), dim3(64), lds_first_, first_stream_, A);
+                tick("ambi_first_kernel", 4, false, first_stream_);
+                (void)hipEventRecord(ev_first_, first_stream_);
                 first_launched_ = true;
             }
-            tick("ambi_plan_kernel", s, 1, true);
+            tick("ambi_plan_kernel", 1, true);
         }
         if (lazy_) {}   // no tables in this run: nothing to plan
         else if (express_ && side_lattice_) hipLaunchKernelGGL(ambi_plan_kernel, dim3(1), dim3(1024), 0, st, A);
         else { BatchArgs Ap = A; Ap.lat_R = nullptr; hipLaunchKernelGGL(ambi_plan_kernel, dim3(1), dim3(1024), 0, st, Ap); }
-        tick("ambi_plan_kernel", s, 1, false);
+        tick("ambi_plan_kernel", 1, false);
         // (express chain: the lattice kernel reads the status, so the scan of the units the express kernel left stays behind
         // the plan kernel there)
-        {
-            static const bool one_event = [] { const char* e = ambi_env("AMBI_ONE_FRONT_EVENT"); return e && atoi(e) != 0; }();
-            if (one_event && !express_ && !lazy_ && overlap_back_ && first_ahead_ == 3) {
-                // experiment: ONE event on the caller's stream between prepare and the order-table kernel (behind the plan kernel) instead
-                // of one on either side of the plan kernel; the scan then starts behind the plan kernel
-                (void)hipEventRecord(ev_plan_, st);
-                hipStream_t sf = first_stream_ ? first_stream_ : back_stream_;
-                (void)hipStreamWaitEvent(sf, ev_plan_, 0);
-                tick("ambi_first_kernel", s, 4, true, sf);
-                hipLaunchKernelGGL(ambi_first_kernel, dim3(A.n_units), dim3(64), lds_first_, sf, A);
-                tick("ambi_first_kernel", s, 4, false, sf);
-                (void)hipEventRecord(ev_first_, sf);
-                first_launched_ = true;
-                return;
-            }
-        }
         if (overlap_back_) (void)hipEventRecord(first_launched_ ? ev_plan_ : ev_prep_, st);
     }
-    void launch_build(int s, const BatchArgs& A) {   // block-emission images
-        hipStream_t st = slice_stream(s);
-        tick("ambi_blocks_build_kernel", s, 2, true);
-        hipLaunchKernelGGL(ambi_blocks_build_kernel, dim3(A.n_units), dim3(256), lds_build_, st, A);
-        tick("ambi_blocks_build_kernel", s, 2, false);
+    void launch_build(const BatchArgs& A) {   // block-emission images
+        tick("ambi_blocks_build_kernel", 2, true);
+        hipLaunchKernelGGL(ambi_blocks_build_kernel, dim3(A.n_units), dim3(256), lds_build_, stream_, A);
+        tick("ambi_blocks_build_kernel", 2, false);
     }
     // Workgroups of the lean finish kernel.  Beside a long enumerate kernel the finish stage only has to be done when the
     // table is: the fewer of its workgroups are resident, the less they take from the enumerate workgroups (issue slots,
@@ -1850,44 +1739,42 @@ class HipBackend : public Backend {
         if (grid < 32) grid = 32;
         return grid < U ? (int)grid : U;
     }
-    void launch_back(int s, const BatchArgs& A) {    // enumerate, first valid order, finish
-        hipStream_t st = slice_stream(s);
+    void launch_back(const BatchArgs& A) {    // enumerate, first valid order, finish
+        hipStream_t st = stream_;
         const int U = A.n_units;
         const int grid = enum_grid_;
         // The scan for the first valid order (reads the first rows the prepare stage left, not the table).  Beside a long
-        // enumerate kernel it is launched AHEAD of it (first_ahead_): behind the enumerate kernel in launch order its 4096
-        // one-wave workgroups only get group memory as enumerate workgroups retire (0.06 ms alone, 0.5-0.6 ms beside), and
-        // the finish kernels behind it then start half-way through the table and end after it.
+        // enumerate kernel it is launched AHEAD of it: behind the enumerate kernel in launch order its 4096 one-wave
+        // workgroups only get group memory as enumerate workgroups retire (0.06 ms alone, 0.5-0.6 ms beside), and the
+        // finish kernels behind it then start half-way through the table and end after it.
         hipStream_t sb = overlap_back_ ? back_stream_ : st;
         auto launch_first = [&]() {
-            if (first_launched_) {   // started beside the plan kernel (launch_front): the finish kernels wait for both
-                (void)hipStreamWaitEvent(sb, ev_first_, 0); (void)hipStreamWaitEvent(sb, ev_plan_, 0);
-                if (full_stream_) (void)hipStreamWaitEvent(full_stream_, ev_plan_, 0);
-                return;
-            }
-            hipStream_t sf = (first_ahead_ == 2 && overlap_back_ && first_stream_) ? first_stream_ : sb;
-            if (overlap_back_) (void)hipStreamWaitEvent(sf, ev_prep_, 0);
-            tick("ambi_first_kernel", s, 4, true, sf);
-            hipLaunchKernelGGL(ambi_first_kernel, dim3(U), dim3(64), lds_first_, sf, A);
-            tick("ambi_first_kernel", s, 4, false, sf);
-            if (overlap_back_) { (void)hipEventRecord(ev_first_, sf); if (sf != sb) (void)hipStreamWaitEvent(sb, ev_first_, 0); }
+            tick("ambi_first_kernel", 4, true, sb);
+            hipLaunchKernelGGL(ambi_first_kernel, dim3(U), dim3(64), lds_first_, sb, A);
+            tick("ambi_first_kernel", 4, false, sb);
         };
-        const bool ahead = (first_ahead_ > 0 && overlap_back_) || first_launched_;
-        if (ahead) { launch_first(); if (first_ahead_ == 1) (void)hipStreamWaitEvent(st, ev_first_, 0); }
-        tick("ambi_enumerate_kernel", s, 3, true);
+        if (first_launched_) {   // started beside the plan kernel (launch_front): the finish kernels wait for both
+            (void)hipStreamWaitEvent(sb, ev_first_, 0); (void)hipStreamWaitEvent(sb, ev_plan_, 0);
+            if (full_stream_) (void)hipStreamWaitEvent(full_stream_, ev_plan_, 0);
+        } else if (overlap_back_) {   // (express chain) on the back stream behind the plan kernel, ahead of the enumerate launch
+            (void)hipStreamWaitEvent(sb, ev_prep_, 0);
+            launch_first();
+            (void)hipEventRecord(ev_first_, sb);
+        }
+        tick("ambi_enumerate_kernel", 3, true);
         const int lds_emit = lds_blocks_;
         if (lazy_) {}   // the tables are written on demand (materialise_tables)
         else {
-        if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(enum_threads_), lds_emit, st, A);
-        if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(enum_threads_), lds_emit, st, A);
-        if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(enum_threads_), lds_emit, st, A);
+        if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
+        if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
+        if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
         if ((enum_classes_ & 1) && general_path_ != 0) hipLaunchKernelGGL(ambi_enumerate_kernel<0>, dim3(grid), dim3(256), lds_enum_, st, A);
         if ((enum_classes_ & 2) && general_path_ != 0) hipLaunchKernelGGL(ambi_enumerate_kernel<1>, dim3(grid), dim3(256), lds_enum_, st, A);
         if ((enum_classes_ & 4) && general_path_ != 0) hipLaunchKernelGGL(ambi_enumerate_kernel<2>, dim3(grid), dim3(256), lds_enum_, st, A);
         if (n_wide_ > 0) hipLaunchKernelGGL(ambi_enumerate_wide_kernel, dim3(64, n_wide_), dim3(256), 0, st, A, (const int32_t*)d_wide_units_, n_wide_);
         }
-        tick("ambi_enumerate_kernel", s, 3, false);
-        if (!ahead) launch_first();
+        tick("ambi_enumerate_kernel", 3, false);
+        if (!overlap_back_) launch_first();   // behind the enumerate kernel on the caller's stream
         // units with deletion / duplication candidates go straight to the full finish stage, on a stream of their own beside
         // the lean kernel (both behind the scan, both beside the enumerate kernel); few workgroups, each taking units in turn
         if (direct_n_ > 0 && overlap_back_ && full_stream_) {
@@ -1902,7 +1789,7 @@ class HipBackend : public Backend {
                 lds_direct = (int)finish_work_bytes(hb().max_n, hb().max_m, hb().max_bkp, direct_cells_, hb().max_out);
             }
             direct_retry_ = Ad.finish_retry != 0;
-            tick("ambi_finish_ext_kernel", s, 6, true, full_stream_);
+            tick("ambi_finish_ext_kernel", 6, true, full_stream_);
             if (direct_ext_ && d_direct_cells_ && direct_edit_) {
                 // the edits of lone SVs on the runs of the path; what that stage hands on (chaining SVs, lists that outgrow their room)
                 // to the launch with the path cells in device memory, over the list the first one leaves on the device
@@ -1917,18 +1804,14 @@ class HipBackend : public Backend {
                 hipLaunchKernelGGL(ambi_finish_ext_kernel, dim3(dgrid), dim3(full_threads_), lds_finish_ext_, full_stream_, A, (const int32_t*)d_direct_list_, direct_n_, d_direct_cells_, direct_stride_);
             } else
             hipLaunchKernelGGL(ambi_finish_kernel, dim3(dgrid), dim3(full_threads_), lds_direct, full_stream_, Ad, (const int32_t*)d_direct_list_, (const int32_t*)nullptr, direct_n_);
-            tick("ambi_finish_ext_kernel", s, 6, false, full_stream_);
+            tick("ambi_finish_ext_kernel", 6, false, full_stream_);
             (void)hipEventRecord(ev_full_, full_stream_);
         }
-        tick("ambi_finish_kernel", s, 5, true, sb);
+        tick("ambi_finish_kernel", 5, true, sb);
         const int fgrid = finish_grid_for(U);
         if (debug_) fprintf(stderr, "ambigram_hip: lean finish grid %d, image budget %d, mean path capacity %.0f, order bytes %lld\n", fgrid, block_lds_, avg_path_, (long long)last_needed_);
         if (lean_finish_) {
-            if (lean_wave_) {
-                const int wg = lean_wave_grid_ > 0 ? (lean_wave_grid_ < U ? lean_wave_grid_ : U) : (fgrid < U ? std::min(U, 4 * fgrid) : U);
-                hipLaunchKernelGGL(ambi_finish_lean_wave_kernel, dim3(wg), dim3(64), lds_finish_lean_, sb, A);
-            } else
-            hipLaunchKernelGGL(ambi_finish_lean_kernel, dim3(fgrid), dim3(lean_threads_), lds_finish_lean_, sb, A, (const int32_t*)nullptr, 0);
+            hipLaunchKernelGGL(ambi_finish_lean_kernel, dim3(fgrid), dim3(256), lds_finish_lean_, sb, A, (const int32_t*)nullptr, 0);
             // units whose SVs chain or edit the path: the full stage right behind, over the list the lean kernel left on the
             // device (an empty list costs one launch of workgroups that exit at once)
             if (hb().any_sv) {
@@ -1936,7 +1819,7 @@ class HipBackend : public Backend {
                 hipLaunchKernelGGL(ambi_finish_kernel, dim3(U < 256 ? U : 256), dim3(256), lds_finish_, sb, A, (const int32_t*)d_refin_list_, (const int32_t*)d_refin_count_, -1);   // (at most one such workgroup fits a CU: more than 256 gain nothing)
             }
         } else hipLaunchKernelGGL(ambi_finish_kernel, dim3(U), dim3(256), lds_finish_, sb, A, (const int32_t*)nullptr, (const int32_t*)nullptr, -1);
-        tick("ambi_finish_kernel", s, 5, false, sb);
+        tick("ambi_finish_kernel", 5, false, sb);
         if (overlap_back_) {
             (void)hipEventRecord(ev_back_, sb); (void)hipStreamWaitEvent(st, ev_back_, 0);
             if (direct_n_ > 0 && full_stream_) (void)hipStreamWaitEvent(st, ev_full_, 0);
@@ -1946,7 +1829,7 @@ class HipBackend : public Backend {
     // Everything of one run, queued on the caller's stream and the lease's side streams.  The FIRST run of a batch takes what
     // arena the lease has: the plan kernel reports what the tables need, and wait() grows the arena and runs the batch again
     // if that was not enough (round 2 ran prepare + plan, synchronised, sized the arena and only then queued the run --
-    // two host round trips in front of every fresh batch).  AMBI_SLICES > 1 (an experiment) keeps the sizing pass.
+    // two host round trips in front of every fresh batch).
     int64_t epoch_ = 0;
     int64_t results_epoch() const override { return epoch_; }
     void* own_stream() override {
@@ -1961,10 +1844,9 @@ class HipBackend : public Backend {
         if (!uploaded_) return -32;
         if (ran_ && !tuned_ && tables_written_) { if (int rc = tune_after_first_run()) return rc; }
         stream_ = (hipStream_t)stream;
-        if (classed_ && (want_back_ || want_full_ || want_first_ || want_lattice_)) {
+        if (classed_ && (back_stream_ || side_lattice_)) {
             // side streams that dispatch beside THIS caller's stream (learnt once per stream and device: a few probe launches; a
             // stream seen before costs a look-up)
-            static const bool first_prio = [] { const char* e = ambi_env("AMBI_FIRST_PRIORITY"); return e && atoi(e) != 0; }();
             if (stream_ != classed_for_) {
                 hipStream_t sd[3] = {nullptr, nullptr, nullptr};
                 const int rc = classified_side_streams(device_, stream_, (int)(lease_->uses & 1), sd);
@@ -1972,11 +1854,11 @@ class HipBackend : public Backend {
                 for (int k = 0; k < 3; k++) classed_streams_[k] = rc == 0 ? sd[k] : nullptr;   // (rc 1: keep the lease's streams, rounds 1-3's choice)
                 classed_for_ = stream_;
             }
-            if (want_back_ && classed_streams_[0]) back_stream_ = classed_streams_[0];
-            if (want_full_ && classed_streams_[1]) full_stream_ = classed_streams_[1];
-            static const bool first_on_back = [] { const char* e = ambi_env("AMBI_FIRST_ON_BACK"); return e && atoi(e) != 0; }();   // experiment: the scan on the lean finish kernel's stream (no event between the two)
-            if (want_first_ && !first_prio && classed_streams_[2]) first_stream_ = first_on_back ? classed_streams_[0] : classed_streams_[2];
-            if (want_lattice_ && classed_streams_[2]) lattice_stream_ = classed_streams_[2];
+            // (each replaces a stream of the lease that this batch uses)
+            if (back_stream_ && classed_streams_[0]) back_stream_ = classed_streams_[0];
+            if (full_stream_ && classed_streams_[1]) full_stream_ = classed_streams_[1];
+            if (first_stream_ && classed_streams_[2]) first_stream_ = classed_streams_[2];
+            if (side_lattice_ && classed_streams_[2]) lattice_stream_ = classed_streams_[2];
         }
         t_run_ = std::chrono::steady_clock::now();
         flushed_ = upload_pending_;
@@ -1987,55 +1869,21 @@ class HipBackend : public Backend {
         bind(flags);
         all_done_ = false;
         const int U = A_.n_units;
-        lazy_ = (flags & FLAG_LAZY_ORDERS) != 0 && n_slices_ == 1;
-        // one slice: no copy commands around the kernels (see BatchArgs::zero_pending)
-        const bool direct = n_slices_ == 1 && dh_npending_ && dh_needed_;
-        if (!direct) { HIP_CK(hipMemsetAsync(d_npending_, 0, sizeof(int32_t), stream_)); HIP_CK(hipMemsetAsync(d_refin_count_, 0, 2 * sizeof(int32_t), stream_)); }
-        if (!arena_checked_ && n_slices_ > 1) {
-            // first run of a sliced batch: size the arena regions of the slices from what their order tables need
-            for (int s = 0; s < n_slices_; s++) launch_front(0, slice_args(s));   // all on the caller's stream
-            HIP_CK(hipGetLastError());
-            HIP_CK(hipMemcpyAsync(h_needed_, d_needed_, sizeof(int64_t) * n_slices_, hipMemcpyDeviceToHost, stream_));
-            HIP_CK(hipStreamSynchronize(stream_));
-            int64_t total = 0;
-            for (int s = 0; s < n_slices_; s++) {
-                slice_base_[s] = total;
-                slice_bytes_[s] = (h_needed_[s] + (h_needed_[s] >> 4) + 4096 + order_align_ - 1) & ~int64_t(order_align_ - 1);
-                total += slice_bytes_[s];
-            }
-            if (total > arena_bytes_) {
-                (void)grow_arena(total);
-                if (arena_bytes_ < total)
-                    for (int s = 0; s < n_slices_; s++) { slice_base_[s] = (arena_bytes_ / n_slices_ * s) & ~int64_t(order_align_ - 1); slice_bytes_[s] = (arena_bytes_ / n_slices_) & ~int64_t(order_align_ - 1); }
-                bind(flags);
-            }
-            arena_checked_ = true;
-        }
-        overlap_back_ = want_overlap_ && back_stream_ != nullptr && n_slices_ == 1;
+        lazy_ = (flags & FLAG_LAZY_ORDERS) != 0;
+        overlap_back_ = want_overlap_ && back_stream_ != nullptr;
         A_.direct_full_on = (overlap_back_ && direct_n_ > 0 && full_stream_ != nullptr) ? 1 : 0;
-        express_ = n_slices_ == 1 && U <= express_units_ && lds_express_ <= kLdsMaxDynamic && dh_express_left_ != nullptr && direct && n_wide_ == 0;
-        if (direct) { A_.zero_pending = 1; A_.host_pending = dh_npending_; A_.host_needed = dh_needed_; }
-        // Software pipeline over the slices: slice s starts its latency-bound front (prepare, plan, image build) when
-        // slice s-1 has finished its own and moves on to the HBM-bound enumerate kernel, so the two kinds of work
-        // share the chip instead of alternating.
-        fork();
-        for (int s = 0; s < n_slices_; s++) {
-            const BatchArgs A = slice_args(s);
-            if (A.n_units <= 0) continue;
-            if (s > 0 && stagger_) (void)hipStreamWaitEvent(slice_stream(s), ev_stage_[s - 1], 0);
-            launch_front(s, A);
-            if (lazy_) { tick("ambi_blocks_build_kernel", s, 2, true); tick("ambi_blocks_build_kernel", s, 2, false); }
-            else if (!(build_in_emit_ && shared_units_ == 0)) launch_build(s, A);
-            else { tick("ambi_blocks_build_kernel", s, 2, true); tick("ambi_blocks_build_kernel", s, 2, false); }   // nothing to build
-            if (s + 1 < n_slices_) (void)hipEventRecord(ev_stage_[s], slice_stream(s));
-            launch_back(s, A);
+        express_ = U <= express_units_ && lds_express_ <= kLdsMaxDynamic && dh_express_left_ != nullptr && n_wide_ == 0;
+        // no copy commands around the kernels: they zero their counters and store the two words the host reads into pinned
+        // memory themselves (see BatchArgs::zero_pending)
+        A_.zero_pending = 1; A_.host_pending = dh_npending_; A_.host_needed = dh_needed_;
+        const BatchArgs A = args();
+        if (A.n_units > 0) {
+            launch_front(A);
+            if (lazy_ || (build_in_emit_ && shared_units_ == 0)) { tick("ambi_blocks_build_kernel", 2, true); tick("ambi_blocks_build_kernel", 2, false); }   // nothing to build
+            else launch_build(A);
+            launch_back(A);
         }
         HIP_CK(hipGetLastError());
-        join();
-        if (!direct) {
-            HIP_CK(hipMemcpyAsync(h_npending_, d_npending_, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-            HIP_CK(hipMemcpyAsync(h_needed_, d_needed_, sizeof(int64_t) * n_slices_, hipMemcpyDeviceToHost, stream_));
-        }
         if (side_lattice_) (void)hipEventRecord(lease_->ev_tail, stream_);   // where the NEXT run's side lattice kernel may start
         tables_written_ = !lazy_;
         ran_ = true; inflight_ = true;
@@ -2068,15 +1916,15 @@ class HipBackend : public Backend {
     int materialise_tables() {
         if (tables_written_ || !ran_) return 0;
         for (int attempt = 0; attempt < 2; attempt++) {
-            BatchArgs A = slice_args(0);
+            BatchArgs A = args();
             A.zero_pending = 1; A.host_pending = dh_npending_; A.host_needed = dh_needed_; A.lat_R = nullptr; A.plan_seq = nullptr; A.late_flag = nullptr;
             hipLaunchKernelGGL(ambi_plan_reset_kernel, dim3((A.n_units + 255) / 256), dim3(256), 0, stream_, A);
             hipLaunchKernelGGL(ambi_plan_kernel, dim3(1), dim3(1024), 0, stream_, A);
             hipLaunchKernelGGL(ambi_blocks_build_kernel, dim3(A.n_units), dim3(256), lds_build_, stream_, A);
             const int grid = enum_grid_;
-            if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(enum_threads_), lds_blocks_, stream_, A);
-            if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(enum_threads_), lds_blocks_, stream_, A);
-            if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(enum_threads_), lds_blocks_, stream_, A);
+            if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(kEnumThreads), lds_blocks_, stream_, A);
+            if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(kEnumThreads), lds_blocks_, stream_, A);
+            if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(kEnumThreads), lds_blocks_, stream_, A);
             if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_kernel<0>, dim3(grid), dim3(256), lds_enum_, stream_, A);
             if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_kernel<1>, dim3(grid), dim3(256), lds_enum_, stream_, A);
             if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_kernel<2>, dim3(grid), dim3(256), lds_enum_, stream_, A);
@@ -2084,10 +1932,9 @@ class HipBackend : public Backend {
             HIP_CK(hipGetLastError());
             HIP_CK(hipStreamSynchronize(stream_));
             const int64_t need = h_needed_[0];
-            if (need <= slice_bytes_[0] || attempt == 1) break;
+            if (need <= arena_usable() || attempt == 1) break;
             const int64_t total = (need + (need >> 4) + 4096 + order_align_ - 1) & ~int64_t(order_align_ - 1);
             if (!grow_arena(total)) break;
-            slice_base_[0] = 0; slice_bytes_[0] = arena_bytes_ & ~int64_t(order_align_ - 1);
             bind(A_.flags);
         }
         tables_written_ = true;
@@ -2097,12 +1944,10 @@ class HipBackend : public Backend {
     int settle_first_run() {
         if (arena_checked_) return 0;
         arena_checked_ = true;
-        if (n_slices_ != 1) return 0;
         const int64_t need = h_needed_[0];
         if (need > arena_bytes_) {
             const int64_t total = (need + (need >> 4) + 4096 + order_align_ - 1) & ~int64_t(order_align_ - 1);
             if (grow_arena(total)) {   // the whole batch again, now with room for every table (prepare resets what the first pass refused)
-                slice_base_[0] = 0; slice_bytes_[0] = arena_bytes_ & ~int64_t(order_align_ - 1);
                 lease_->h_words->late_flag = 0;
                 ran_ = false;   // (the run below is still this batch's FIRST complete one: nothing is tuned from the refused pass)
                 const bool t = timing_; timing_ = false;
@@ -2145,39 +1990,37 @@ class HipBackend : public Backend {
             }
             // ... and whether any unit's table is shared by several workgroups (only those go through the build kernel
             // when single-block units build their image in the enumerate workgroup): if none, later runs do not launch it
-            if (n_slices_ == 1) {
-                std::vector<int64_t> bo(hb().units.size() + 1);
-                HIP_CK(hipMemcpy(bo.data(), d_blk_off_, bo.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-                shared_units_ = 0;
-                for (size_t u2 = 0; u2 + 1 < bo.size(); u2++) shared_units_ += (bo[u2 + 1] - bo[u2] > 1) ? 1 : 0;
-                // Group memory per enumerate workgroup for the runs to come.  k workgroups share a CU's 160 KB and its store
-                // bandwidth, so W work blocks take about ceil(W / (CUs * k)) * k "slot rounds": pick the k in 3..5 with the
-                // fewest, among those whose budget 160 KB / k still holds every image of this batch (measured on the bench
-                // batch, 4096 work blocks on 256 CUs: k = 3 (48 KB) 0.92-0.95 ms, k = 4 (40 KB) 0.86-0.87 ms).
-                if (emit_lds_auto_ && general_path_ == 0 && bo.back() > 0) {
-                    std::vector<int32_t> hd(hb().units.size() * 8);
-                    HIP_CK(hipMemcpy(hd.data(), d_blk_hdr_, hd.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-                    int need = 0;
-                    for (size_t u2 = 0; u2 < hb().units.size(); u2++) if (hd[8 * u2] > 0 && hd[8 * u2 + 3] > need) need = hd[8 * u2 + 3];
-                    int ncu = 256;
-                    { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
-                    const int64_t W = bo.back();
-                    int best_k = 0; int64_t best = 0;
-                    for (int k = 3; k <= 5; k++) {
-                        const int budget = ((160 * 1024) / k) & ~15;
-                        if (need <= 0 || need > budget) continue;
-                        const int64_t rounds = ((W + (int64_t)ncu * k - 1) / ((int64_t)ncu * k)) * k;
-                        if (!best_k || rounds < best) { best_k = k; best = rounds; }
-                    }
-                    if (debug_) fprintf(stderr, "ambigram_hip: image need %d bytes, %lld work blocks on %d CUs -> %d workgroups per CU\n", need, (long long)W, ncu, best_k);
-                    // ... and ask for no more than the images need (512-byte granules): what the k enumerate workgroups leave of
-                    // the CU's group memory is where the scan / finish workgroups run WITHOUT pushing an enumerate workgroup out
-                    if (best_k) {
-                        block_lds_ = ((160 * 1024) / best_k) & ~15;
-                        const int tight = (need + 511) & ~511;
-                        if (emit_lds_tight_ && tight < block_lds_) block_lds_ = tight;
-                        lds_blocks_ = block_lds_;
-                    }
+            std::vector<int64_t> bo(hb().units.size() + 1);
+            HIP_CK(hipMemcpy(bo.data(), d_blk_off_, bo.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+            shared_units_ = 0;
+            for (size_t u2 = 0; u2 + 1 < bo.size(); u2++) shared_units_ += (bo[u2 + 1] - bo[u2] > 1) ? 1 : 0;
+            // Group memory per enumerate workgroup for the runs to come.  k workgroups share a CU's 160 KB and its store
+            // bandwidth, so W work blocks take about ceil(W / (CUs * k)) * k "slot rounds": pick the k in 3..5 with the
+            // fewest, among those whose budget 160 KB / k still holds every image of this batch (measured on the bench
+            // batch, 4096 work blocks on 256 CUs: k = 3 (48 KB) 0.92-0.95 ms, k = 4 (40 KB) 0.86-0.87 ms).
+            if (emit_lds_auto_ && general_path_ == 0 && bo.back() > 0) {
+                std::vector<int32_t> hd(hb().units.size() * 8);
+                HIP_CK(hipMemcpy(hd.data(), d_blk_hdr_, hd.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+                int need = 0;
+                for (size_t u2 = 0; u2 < hb().units.size(); u2++) if (hd[8 * u2] > 0 && hd[8 * u2 + 3] > need) need = hd[8 * u2 + 3];
+                int ncu = 256;
+                { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
+                const int64_t W = bo.back();
+                int best_k = 0; int64_t best = 0;
+                for (int k = 3; k <= 5; k++) {
+                    const int budget = ((160 * 1024) / k) & ~15;
+                    if (need <= 0 || need > budget) continue;
+                    const int64_t rounds = ((W + (int64_t)ncu * k - 1) / ((int64_t)ncu * k)) * k;
+                    if (!best_k || rounds < best) { best_k = k; best = rounds; }
+                }
+                if (debug_) fprintf(stderr, "ambigram_hip: image need %d bytes, %lld work blocks on %d CUs -> %d workgroups per CU\n", need, (long long)W, ncu, best_k);
+                // ... and ask for no more than the images need (512-byte granules): what the k enumerate workgroups leave of
+                // the CU's group memory is where the scan / finish workgroups run WITHOUT pushing an enumerate workgroup out
+                if (best_k) {
+                    block_lds_ = ((160 * 1024) / best_k) & ~15;
+                    const int tight = (need + 511) & ~511;
+                    if (emit_lds_tight_ && tight < block_lds_) block_lds_ = tight;
+                    lds_blocks_ = block_lds_;
                 }
             }
         }
@@ -2262,7 +2105,7 @@ class HipBackend : public Backend {
         inflight_ = false;
         if (tables_written_) { if (int rc = settle_first_run()) return rc; }
         if (check_guards("wait")) return -31;
-        if (tables_written_) { last_needed_ = 0; for (int s = 0; s < n_slices_; s++) last_needed_ += h_needed_[s]; }
+        if (tables_written_) last_needed_ = *h_needed_;
         late_refusal_ = lease_->h_words->late_flag != 0;
         if (*h_npending_ > 0) {
             if (int rc = materialise_tables()) return rc;   // (FLAG_LAZY_ORDERS: the parallel search reads the tables)
@@ -2278,8 +2121,7 @@ class HipBackend : public Backend {
         // the mailbox of a small batch holds what the express kernel published; nothing behind it changed a header
         mail_valid_ = express_ && mail_on_ && !(A_.flags & FLAG_ALL) && *(volatile int32_t*)h_express_left_ == 0 && !late_refusal_;
         if (timing_ && timed_runs_ > 0) {
-            // average duration of ONE launch of every kernel over the slices and the slots filled since timing was
-            // switched on (every run launches each kernel once per slice)
+            // average duration of ONE launch of every kernel over the slots filled since timing was switched on
             const long filled = timed_runs_ < kTimingSlots ? timed_runs_ : kTimingSlots;
             times_.clear();
             static const char* const kKernelNames[kTimedKernels] = {"ambi_prepare_kernel", "ambi_plan_kernel", "ambi_blocks_build_kernel",
@@ -2288,18 +2130,16 @@ class HipBackend : public Backend {
                 double sum = 0, s0 = 0, s1 = 0; int cnt = 0, cnt_span = 0; const char* nm = kKernelNames[k];
                 if (!((timing_mask_ >> k) & 1u)) { times_.push_back({nm, -1.0f}); continue; }
                 for (long sl = 0; sl < filled; sl++) {
-                    for (int sc = 0; sc < n_slices_; sc++) {
-                        size_t at = ((size_t)sl * n_slices_ + sc) * kTimedKernels + k;
-                        if (at >= evs().size() || !evs()[at].a) continue;
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, evs()[at].a, evs()[at].b) == hipSuccess) { sum += ms; cnt++; nm = evs()[at].name; }
-                        // where the kernel sits in its run: from the event in front of the run's first kernel (the events of one slot
-                        // belong to one run; they sit on different streams of one device)
-                        const size_t at0 = ((size_t)sl * n_slices_ + sc) * kTimedKernels;
-                        float a = 0, b = 0;
-                        if ((timing_mask_ & 1u) && at0 < evs().size() && evs()[at0].a && hipEventElapsedTime(&a, evs()[at0].a, evs()[at].a) == hipSuccess &&
-                            hipEventElapsedTime(&b, evs()[at0].a, evs()[at].b) == hipSuccess) { s0 += a; s1 += b; cnt_span++; }
-                    }
+                    const size_t at = (size_t)sl * kTimedKernels + k;
+                    if (at >= evs().size() || !evs()[at].a) continue;
+                    float ms = 0;
+                    if (hipEventElapsedTime(&ms, evs()[at].a, evs()[at].b) == hipSuccess) { sum += ms; cnt++; nm = evs()[at].name; }
+                    // where the kernel sits in its run: from the event in front of the run's first kernel (the events of one slot
+                    // belong to one run; they sit on different streams of one device)
+                    const size_t at0 = (size_t)sl * kTimedKernels;
+                    float a = 0, b = 0;
+                    if ((timing_mask_ & 1u) && at0 < evs().size() && evs()[at0].a && hipEventElapsedTime(&a, evs()[at0].a, evs()[at].a) == hipSuccess &&
+                        hipEventElapsedTime(&b, evs()[at0].a, evs()[at].b) == hipSuccess) { s0 += a; s1 += b; cnt_span++; }
                 }
                 KernelTime kt{nm, cnt ? (float)(sum / cnt) : -1.0f};
                 if (cnt_span) { kt.start_ms = (float)(s0 / cnt_span); kt.end_ms = (float)(s1 / cnt_span); }
@@ -2340,7 +2180,7 @@ class HipBackend : public Backend {
                 seen = false;
                 for (int spin = 0; spin < 400000 && !(seen = (*pseq == run_seq_)); spin++) __builtin_ia32_pause();
                 const bool fine = side_lattice_ ? *(volatile int32_t*)&lease_->h_words->lat_unsure == 0
-                                                : (*(volatile int32_t*)&lease_->h_words->late_flag == 0 && *(volatile int64_t*)h_needed_ <= slice_bytes_[0]);
+                                                : (*(volatile int32_t*)&lease_->h_words->late_flag == 0 && *(volatile int64_t*)h_needed_ <= arena_usable());
                 if (seen && fine) {
                     arena_checked_ = true;     // every table of this batch fits the arena: true for all its runs
                     mail_valid_ = mail_on_;
@@ -2563,7 +2403,6 @@ class HipBackend : public Backend {
     const std::vector<KernelTime>& kernel_times() override { return times_; }
     int64_t order_bytes_written() const override { return last_needed_; }
     size_t object_bytes() const override { return sizeof(HipBackend); }
-    int slice_count() const override { return n_slices_; }
 
     // ---- --all (LGM.cpp:3672-3695): every valid order of every unit, in the reference's print order ----
     // pass 0 = the first orientation (forward unless --reversed), pass 1 = the flipped one, run only for units whose LAST

@@ -399,7 +399,7 @@ AMBI_HD void plan_serial(const BatchArgs& A) {
         if (out->order_off == kOrderOffWanted && out->num_orders < (int64_t)kCountSat) total_rows += out->num_orders;
     }
     const int T = rows_per_lane_for(total_rows, A.target_lanes);
-    int64_t off = 0, blk = 0;   // off: relative to the slice's arena region
+    int64_t off = 0, blk = 0;   // off: relative to the launch's arena region
     for (int i = 0; i < A.n_units; i++) {
         const int u = A.unit_base + i;
         UnitOut* out = unit_out(A.results, u);

@@ -312,9 +312,8 @@ int ambi_batch_unit_orders(ambi_batch_t* b, int32_t unit, int64_t first, int64_t
 
 /* Per-kernel timing (HIP events on the streams the kernels are launched on, milliseconds): the average duration of
  * ONE launch of the kernel over the runs since timing was enabled; names are static strings.  A run launches every
- * kernel once per slice (ambi_batch_slices: contiguous unit ranges whose kernel chains run on separate HIP streams so
- * that the HBM-bound and the latency-bound kernels overlap; set with the environment variable AMBI_SLICES, default
- * automatic).  Enable with ambi_batch_set_timing(b, 1) before run. */
+ * kernel once (ambi_batch_slices: launches of every kernel per run, always 1; kept for compatibility).  Enable with
+ * ambi_batch_set_timing(b, 1) before run. */
 int ambi_batch_slices(const ambi_batch_t* b);
 int ambi_batch_set_timing(ambi_batch_t* b, int32_t on);
 /* The same for a subset of the kernels: bit k of `mask` = kernel index k of ambi_batch_kernel_time (0 prepare, 1 plan,
