@@ -1715,12 +1715,15 @@ class HipBackend : public Backend {
         if (finish_grid_ > 0) return U < finish_grid_ ? U : finish_grid_;          // env AMBI_FINISH_GRID
         if (!overlap_back_ || lazy_) return U;   // (no order table being written: nothing to hide behind, every unit its own workgroup)
         // order-table bytes of the previous run at the rate the enumerate kernel reaches: an optimistic 5.2 TB/s for rows of a byte
-        // per node; rows of 5 bits per node (up to 32 nodes) leave at ~3.5 TB/s -- fewer bytes per row for the same work per row
-        // (measured on the bench batch, 12-byte rows: 160 / 176 / 192 / 208 / 240 / 272 workgroups = 0.92-0.93 / 0.916-0.938 /
+        // per node; packed rows of up to 32 nodes leave slower -- fewer bytes per row for the same work per row
+        // (measured on the bench batch, 12-byte rows of 5 bits per node: 160 / 176 / 192 / 208 / 240 / 272 workgroups = 0.92-0.93 / 0.916-0.938 /
         // 0.903-0.919 / 0.914-0.933 / 0.93-0.94 / 0.95 ms per step with the 16-byte-group emission; with one row per lane the
         // table is done earlier and the finish kernels want more room: 192 / 208 / 224 / 256 / 288 = 0.887 / 0.864 / 0.857 / 0.876 /
-        // 0.885 (means of 3-6 runs, the build before: 0.867); this rule gives 210 -> 224)
-        const double enum_us = (double)last_needed_ / ((enum_classes_ & 3) ? 4.1e6 : 5.2e6);
+        // 0.885 (means of 3-6 runs, the build before: 0.867); this rule gives 210 -> 224).  Lehmer rows (8 bytes at K = 19 instead of
+        // 12) carry the same work per row in two thirds of the bytes: 224 / 288 / 352 / 416 workgroups = 0.709-0.710 / 0.657-0.670 /
+        // 0.635-0.653 / 0.684-0.685 ms per step, two runs each on one box; at 4.1e6 the rule gave 400 (0.666-0.713), at 3.6e6 it gives 352
+        // (profiles/r05_notes.md)
+        const double enum_us = (double)last_needed_ / ((enum_classes_ & 3) ? 3.6e6 : 5.2e6);
         const double unit_us = 4.0 + avg_path_ / 900.0 + hb().max_m / 64.0;          // one unit through the lean finish stage (mean path capacity of the batch)
         if (enum_us < 8.0 * unit_us) return U;
         // (measured with the SV-carrying bench batch, 40 KB images: 160 / 192 / 256 / 320 workgroups = 1.24 / 1.17 / 1.20 / 1.24 ms
@@ -2375,12 +2378,12 @@ class HipBackend : public Backend {
         UnitOut h;
         HIP_CK(hipMemcpy(&h, d_results_ + sizeof(UnitOut) * (size_t)unit, sizeof(UnitOut), hipMemcpyDeviceToHost));
         if (h.order_off < 0 || first < 0 || first + count > h.num_orders) return ST_ERR_BAD_INPUT;
-        // rows are Kpad bytes apart on the device; the caller gets count x K
+        // rows are row_stride(K) bytes apart on the device; the caller gets count x K
         const int stride = row_stride(h.K);
         std::vector<uint8_t> tmp((size_t)(count * stride));
         HIP_CK(hipMemcpy(tmp.data(), d_arena_ + h.order_off + first * stride, tmp.size(), hipMemcpyDeviceToHost));
-        // (5 bits per node up to 32 nodes, a byte above: row_node unpacks either)
-        for (int64_t r = 0; r < count; r++) for (int d = 0; d < h.K; d++) out[r * h.K + d] = (uint8_t)row_node(tmp.data() + r * stride, h.K, d);
+        // (Lehmer codes up to 63 nodes, a byte per node above: row_unpack decodes either)
+        for (int64_t r = 0; r < count; r++) row_unpack(tmp.data() + r * stride, h.K, out + r * h.K);
         return 0;
     }
     int copy_dag(int unit, Dag* out) override {

@@ -7,8 +7,9 @@
 //
 // Built ONCE per unit (build_block_image, one workgroup, ambi_blocks_build_kernel) into a position-independent
 // image that is parked in HBM and copied into LDS by every emitting workgroup:
-//   * suffix rows: for every possible root J the cnt[J] completions of J as FULL-WIDTH rows (NW dwords, bytes < |J|
-//     zero, bytes >= K 0xFF), in lexicographic order;
+//   * suffix rows: for every possible root J the cnt[J] completions of J as FULL-WIDTH rows (NW dwords, the fields of
+//     positions < |J| zero, the bits behind the last field ones; the fields are Lehmer digits, ambi_orders.hpp: ranks
+//     among the nodes outside J, so they depend on J and the suffix only), in lexicographic order;
 //   * directory: for every block b in table order  { first row, LDS offset of its root's suffix rows, prefix words }.
 //     Block b is found by unranking b over "blocks below an ideal" counts, its first row by summing the 64-bit
 //     completion counts of the skipped siblings -- every block independently, so the directory is filled in parallel.
@@ -69,9 +70,9 @@ struct BlockImageHeader { int32_t fits, nB, suf_words, image_bytes, nI, nC, bloc
 // Image layout (dwords): directory entries of S dwords  { row0, soff, pw[..] }  for b = 0..nB-1, one
 // sentinel dword (= R) in the row0 slot of entry nB, padding to 16 bytes, then the suffix rows.  pw[x] = prefix word
 // x % NW, so that the four words a lane needs, pw[k .. k+3] with k < NW, are consecutive.
-// S = NW + 5 with the three wrap copies of the prefix words the 16-byte-group emission reads; rows of up to five dwords leave one
-// row per lane (emit_piece_rows), which reads pw[0 .. NW) only: S = NW + 2 (K = 19: 20 instead of 32 bytes per block, 2.9 KB of
-// a 27.8 KB image -- room on the CU for a second finish workgroup beside five enumerate workgroups).
+// S = NW + 5 with the three wrap copies of the prefix words the 16-byte-group emission reads; rows of up to five dwords (up to 33
+// nodes) leave one row per lane (emit_piece_rows), which reads pw[0 .. NW) only: S = NW + 2 (K = 19, 2-dword rows: 16 bytes per
+// block, one aligned 16-byte entry).
 AMBI_HD constexpr int dir_stride(int NW) { return (kEmitRows && NW <= 5) ? NW + 2 : NW + 5; }
 AMBI_HD int64_t dir_words(int nB, int NW) { return ((int64_t)nB * dir_stride(NW) + 1 + 3) & ~int64_t(3); }
 
@@ -122,7 +123,6 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
     BuildTables B;
     if (carve_build_tables(scratch, nI, nC, B) > scratch_bytes) return false;
     const int S = dir_stride(NW);
-    const int fb = row_bits(K);     // bits per node of a row
     uint32_t* img = reinterpret_cast<uint32_t*>(image);
     // automaton, levels and blocks-below counts as the prepare stage left them (ideal_build_and_count)
     for (int i = g.tid(); i < nI; i += g.size()) {
@@ -191,7 +191,8 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
         uint32_t rem = (uint32_t)b;
         uint64_t row = 0;
         uint32_t w0 = 0, w1 = 0, w2 = 0;   // the first three prefix words (wrap copies)
-        RowBits rb;                        // the prefix fields, fb bits each (ambi_orders.hpp: 5 up to 32 nodes, else 8)
+        RowBits rb;                        // the prefix fields (ambi_orders.hpp: Lehmer digits)
+        uint64_t free_nodes = all_nodes(K);
         auto flush = [&](int wi, uint32_t w) { e[2 + wi] = w; if (wi == 0) w0 = w; else if (wi == 1) w1 = w; else if (wi == 2) w2 = w; };
         while (B.cnt16[i] > block_max) {
             uint64_t av = B.avail[i];
@@ -206,7 +207,8 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
                 rem -= nb;
                 row += B.cnt64[nxt];
             }
-            rb.put((uint32_t)chosen, fb, flush);
+            rb.put(lehmer_digit(free_nodes, chosen), row_field_bits(K, d), flush);
+            free_nodes &= ~(1ull << chosen);
             i = nxt; d++;
         }
         {   // the partial word and the all-zero words behind the prefix
@@ -220,6 +222,29 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
     }
     if (with_directory && g.tid() == 0) img[nB * S] = (uint32_t)R;
     clk_mark(g, clk, 29);
+    // The nodes still free at every block root (the complement of its ideal = the nodes of any completion, here the one along
+    // first children): a suffix row's digits are ranks among them.  Parked in a table the rest of the build no longer reads --
+    // nblk (32-bit masks, up to 32 nodes) or, with a directory, cnt64; without a directory above 32 nodes (cnt64 is read at
+    // emission) every suffix row walks its root's first completion itself.
+    const bool free32 = K <= 32, free64 = !free32 && with_directory;
+    g.sync();                                                   // (the directory loop above reads nblk / cnt64)
+    auto first_completion = [&](int p) {
+        uint64_t m = 0;
+        for (int j = p, d = B.depth[p]; d < K; d++) {
+            const uint64_t av = B.avail[j];
+            if (!av) break;
+            m |= av & (0ull - av);
+            j = B.child[B.cbase[j]];
+        }
+        return m;
+    };
+    if (free32 || free64) {
+        for (int q = g.tid(); q < nRoots; q += g.size()) {
+            const int p = B.roots[q];
+            const uint64_t m = first_completion(p);
+            if (free32) B.nblk[p] = (uint32_t)m; else B.cnt64[p] = m;
+        }
+    }
     // Node records for the walks below (round 4): { available nodes, first link, second link, index of the first link } of every ideal in ONE
     // 16-byte word, so that a level of a walk is one round trip to group memory where it was two or three (mask and link base, then the
     // links one after the other; the wide tier's ideals have at most two children).  The records overlay the 64-bit masks and counts at the
@@ -228,7 +253,7 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
     // (they are put together in the suffix-row area of the image, which is written only afterwards, and copied over the tables behind a barrier)
     const bool fast_rows = with_directory && K <= 32 && 4ll * nI <= suf_words;
     if (fast_rows) {
-        g.sync();                                               // (the directory loop above reads avail / cnt64)
+        g.sync();                                               // (the loops above read avail / cnt64)
         for (int i = g.tid(); i < nI; i += g.size()) {
             const uint32_t av = (uint32_t)B.avail[i];
             const int k0 = B.cbase[i], nch = __builtin_popcount(av);
@@ -241,9 +266,9 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
             load4(suf + 4 * i, a, b, c, d);
             store4(rec + 4 * i, a, b, c, d);
         }
-        g.sync();
     }
-    // ---- suffix rows: row r of root p = r-th completion of p in lexicographic order, bytes in their final positions ----
+    g.sync();
+    // ---- suffix rows: row r of root p = r-th completion of p in lexicographic order, fields in their final positions ----
     const int total_rows = (int)B.root_row[nRoots];
     for (int f = g.tid(); f < total_rows; f += g.size()) {
         int q = 0;
@@ -253,10 +278,12 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
         uint32_t* dst = suf + B.soff[p] + rr * NW;
         const int D = B.depth[p];
         RowBits rb;                           // fields < D stay zero
-        rb.start(D * fb);
+        rb.start(row_field_off(K, D));
         for (int x = 0; x < rb.wi; x++) dst[x] = 0;
         auto flush = [&](int wi, uint32_t w) { dst[wi] = w; };
         int j = p, d = D;
+        uint64_t free_nodes = free32 ? (uint64_t)B.nblk[p] : (free64 ? B.cnt64[p] : first_completion(p));
+        uint32_t free_lo = (uint32_t)free_nodes;   // (up to 32 nodes)
         if (fast_rows) {
             const uint32_t* rec = reinterpret_cast<const uint32_t*>(B.avail);
             for (; d < K; d++) {
@@ -281,7 +308,8 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
                         }
                     }
                 }
-                rb.put((uint32_t)chosen, fb, flush);
+                rb.put(lehmer_digit32(free_lo, chosen), row_field_bits(K, d), flush);
+                free_lo &= ~(1u << chosen);
                 j = nxt;
             }
         } else
@@ -300,7 +328,8 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
                     if (rr < cc) { chosen = v; break; }
                     rr -= cc;
                 }
-                rb.put((uint32_t)chosen, fb, flush);
+                rb.put(lehmer_digit32(free_lo, chosen), row_field_bits(K, d), flush);
+                free_lo &= ~(1u << chosen);
                 j = nxt;
             }
         }
@@ -317,7 +346,8 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
                 if (rr < cc) { chosen = v; break; }
                 rr -= cc;
             }
-            rb.put((uint32_t)chosen, fb, flush);
+            rb.put(lehmer_digit(free_nodes, chosen), row_field_bits(K, d), flush);
+            free_nodes &= ~(1ull << chosen);
             j = nxt;
         }
         rb.finish(NW, flush);                 // ones behind the K nodes
@@ -331,7 +361,7 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
 // One piece of the table: rows [cur, end) of the block whose first row is r0, whose suffix rows start at dword `so` of
 // `suf` and whose prefix words (with three wrap copies) are pp[0 .. NW+2].  lane_lo/lane_hi: the lanes this call
 // stands for ([lane, lane+1) on the GPU, [0, 64) in the host simulation).
-// Narrow rows (up to five dwords: the packed rows of up to 32 nodes): one ROW per lane and step instead of one 16-byte group --
+// Narrow rows (up to five dwords: the packed rows of up to 33 nodes): one ROW per lane and step instead of one 16-byte group --
 // the prefix words are the same for every row of the piece and stay in registers, a row is NW suffix dwords ORed with them and
 // stored as one NW-dword store; consecutive lanes write consecutive rows, so a wavefront's store covers 64 * 4 NW contiguous bytes.
 template <int NW>
@@ -425,20 +455,20 @@ AMBI_HD void emit_blocks_dfs_wave(const BuildTables& B, const uint32_t* suf, int
     if (rlo >= rhi) return;
     // every lane of the wave runs this bookkeeping with identical values; the stores to the wave's own stack / pw slots
     // are the same from all of them
-    const int fb = row_bits(K);     // bits per node of a row (a field may straddle two words)
-    const uint32_t fmask = (1u << fb) - 1u;
+    // prefix field d = the Lehmer digit of the node taken at depth d (ambi_orders.hpp); `free_nodes` = the nodes not on the
+    // prefix above the current depth, so that the node taken at a depth p of the path is the one node of avail(stack[p]) that
+    // is not free below it
     auto put_word = [&](int wi, uint32_t w) { pw[wi] = w; if (wi < 3) pw[NW + wi] = w; };
-    auto set_byte = [&](int d, uint32_t v) {
-        const int bit = d * fb, wi = bit >> 5, sh = bit & 31;
+    auto set_field = [&](int d, uint32_t v) {
+        const int fb = row_field_bits(K, d);
+        if (fb == 0) return;
+        const uint32_t fmask = (1u << fb) - 1u;
+        const int bit = row_field_off(K, d), wi = bit >> 5, sh = bit & 31;
         put_word(wi, (uniu(pw[wi]) & ~(fmask << sh)) | (v << sh));
         if (sh > 32 - fb) put_word(wi + 1, (uniu(pw[wi + 1]) & ~(fmask >> (32 - sh))) | (v >> (32 - sh)));
     };
-    auto get_byte = [&](int d) {
-        const int bit = d * fb, wi = bit >> 5, sh = bit & 31;
-        uint32_t v = uniu(pw[wi]) >> sh;
-        if (sh > 32 - fb) v |= uniu(pw[wi + 1]) << (32 - sh);
-        return (int)(v & fmask);
-    };
+    uint64_t free_nodes = all_nodes(K);
+    auto take = [&](int d, int v) { set_field(d, lehmer_digit(free_nodes, v)); free_nodes &= ~(1ull << v); };
     for (int x = 0; x < NW + 3; x++) pw[x] = 0;
     int i = 0, d = 0;
     uint64_t rem = rlo;
@@ -454,7 +484,7 @@ AMBI_HD void emit_blocks_dfs_wave(const BuildTables& B, const uint32_t* suf, int
             rem -= cc;
         }
         stack[d] = (uint16_t)i;
-        set_byte(d, (uint32_t)chosen);
+        take(d, chosen);
         i = nxt; d++;
     }
     uint32_t cur = rlo;
@@ -470,25 +500,26 @@ AMBI_HD void emit_blocks_dfs_wave(const BuildTables& B, const uint32_t* suf, int
         while (d > 0) {
             d--;
             const int p = uni(stack[d]);
-            const int v = get_byte(d);                                                  // the node taken at depth d
             const uint64_t av = uniu64(B.avail[p]);
+            const int v = ctz64(av & ~free_nodes);                                      // the node taken at depth d
+            free_nodes |= 1ull << v;
             const uint64_t rest = v >= 63 ? 0ull : (av & ~((2ull << v) - 1ull));       // nodes behind it
             if (rest) {
                 const int v2 = ctz64(rest);
                 const int k = uni(B.cbase[p]) + popc64(av & ((1ull << v2) - 1ull));
-                set_byte(d, (uint32_t)v2);
+                take(d, v2);
                 nxt = uni(B.child[k]);
                 d++;
                 break;
             }
-            set_byte(d, 0u);                                                            // bytes behind the prefix stay zero
+            set_field(d, 0u);                                                           // fields behind the prefix stay zero
         }
         if (nxt < 0) break;                     // no further block (cur < rhi <= R should not get here)
         i = nxt;
         while (uni(B.cnt16[i]) > block_max) {
             const uint64_t av = uniu64(B.avail[i]);
             stack[d] = (uint16_t)i;
-            set_byte(d, (uint32_t)ctz64(av));
+            take(d, ctz64(av));
             i = uni(B.child[uni(B.cbase[i])]);
             d++;
         }

@@ -12,9 +12,9 @@
 //   2. gives every lane a contiguous block of ranks: the lane UNRANKS its first order by walking the automaton
 //      (order_unrank) and then steps through its block with the lexicographic successor, keeping the current row
 //      packed in registers and per-depth (ideal, avail, node) stacks in LDS  (enumerate_rows),
-//   3. writes the R x Kpad uint8 table with 16-byte stores straight from registers (4 rows per store group).
-// Row r of the table = r-th order the reference pushes; columns K..Kpad-1 are 0xFF padding (Kpad = K rounded up
-// to a multiple of 4 so that rows are dword aligned).
+//   3. writes the table straight from registers: packed rows (below) one dword at a time up to 63 nodes, byte rows
+//      in 16-byte groups above.
+// Row r of the table = r-th order the reference pushes.  The fast path (ambi_enum_blocks.hpp) writes the same rows by blocks.
 #pragma once
 #include "ambi_common.hpp"
 #include "ambi_group.hpp"
@@ -25,24 +25,81 @@ constexpr uint64_t kEmptyKey = ~0ull;     // K <= 63, so no ideal mask equals th
 constexpr uint64_t kCountSat = 1ull << 62;
 constexpr int kFirstRowStride = 64;       // bytes between the pre-unranked first orders of a unit (K <= 63)
 
-// Row of the order table.  row_bits(K) bits per node -- 5 up to 32 nodes, 6 up to 63 -- node d in bits [d * bits, (d + 1) * bits) of
-// the row's dwords (little end first: a field may straddle two dwords), the bits behind the K-th field all ones, rows a whole
-// number of dwords: 12 bytes for K = 19 where rounds 1-3 wrote 20, 32 for K = 41 instead of 48.  The table is the reference's
-// `orders` (LGM.cpp:3380-3409) in the engine's own layout: nothing but the engine's kernels and ambi_batch_unit_orders (which
-// unpacks) ever reads it, and the block emission (ambi_enum_blocks.hpp) ORs prefix and suffix DWORDS, whatever the fields inside
-// them are.  64..255 nodes (wide units, ambi_wide.hpp): one byte per node, 128 bytes up to 127 nodes, 256 above.
-AMBI_HD int row_bits(int K) { return K <= 32 ? 5 : (K <= 63 ? 6 : 8); }
+AMBI_HD int ctz64(uint64_t x) { return __builtin_ctzll(x); }
+AMBI_HD int popc64(uint64_t x) { return __builtin_popcountll(x); }
+
+// Row of the order table (K <= 63 nodes): the order's LEHMER CODE.  Field d holds the rank of node d of the order among the
+// nodes not yet placed (node ids ascending), a value below K - d, in row_field_bits(K, d) = ceil(log2(K - d)) bits at bit
+// row_field_off(K, d) of the row's dwords (little end first: a field may straddle two dwords).  The row is
+// sum_{m=1..K} ceil(log2 m) bits: exactly 64 for K = 19 (8 bytes, where round 4 wrote 12 at 5 bits per node and rounds 1-3
+// wrote 20), 32 at most up to 11 nodes, 40 bytes for K = 63 instead of 48.  The bits behind the last field are all ones,
+// rows are a whole number of dwords, at least one.  Fields have fixed positions, and the fields of positions >= |J| of any
+// order that starts with the nodes of an order ideal J depend on J and the suffix only (the nodes still free at |J| are
+// the complement of J): so a prefix with zeros behind it ORed with a suffix with zeros in front of it is the whole row,
+// which is how the block emission (ambi_enum_blocks.hpp) assembles rows.  A row decodes by itself, without the DAG:
+// row_node / row_unpack.  The table is the reference's `orders` (LGM.cpp:3380-3409) in the engine's own layout: nothing but
+// the engine's kernels and ambi_batch_unit_orders (which unpacks) ever reads it.  64..255 nodes (wide units,
+// ambi_wide.hpp): one byte per node, 128 bytes up to 127 nodes, 256 above.
 AMBI_HD bool row_packed(int K) { return K <= 63; }
-AMBI_HD int row_stride(int K) { return K <= 63 ? 4 * ((K * row_bits(K) + 31) >> 5) : (K <= 127 ? 128 : 256); }
-// dwords of the register form of a row in the general enumerate path (one byte per node there; packed when it is stored)
+AMBI_HD int ceil_log2(int m) { return m <= 1 ? 0 : 32 - __builtin_clz((uint32_t)(m - 1)); }
+AMBI_HD int lehmer_bits(int m) { const int c = ceil_log2(m); return m <= 0 ? 0 : c * m - (1 << c) + 1; }   // sum_{j=1..m} ceil(log2 j)
+AMBI_HD int row_field_bits(int K, int d) { return ceil_log2(K - d); }
+AMBI_HD int row_field_off(int K, int d) { return lehmer_bits(K) - lehmer_bits(K - d); }
+AMBI_HD int row_stride(int K) {
+    if (!row_packed(K)) return K <= 127 ? 128 : 256;
+    const int nw = (lehmer_bits(K) + 31) >> 5;
+    return 4 * (nw > 0 ? nw : 1);
+}
+// dwords of the register form of a row in the general enumerate path (one byte per node; packed when it is stored)
 AMBI_HD int row_byte_words(int K) { return K <= 32 ? ((K + 3) >> 2) : (K <= 48 ? 12 : (K <= 63 ? 16 : 32)); }
-// node d of a row (`row` = its first dword)
+// the digit of node v given the mask of the nodes still free (v among them), and the node of digit k: the k-th lowest set bit
+AMBI_HD uint32_t lehmer_digit(uint64_t free_nodes, int v) { return (uint32_t)popc64(free_nodes & ((1ull << v) - 1ull)); }
+AMBI_HD uint32_t lehmer_digit32(uint32_t free_nodes, int v) { return (uint32_t)__builtin_popcount(free_nodes & ((1u << v) - 1u)); }
+AMBI_HD int select_bit(uint64_t m, int k) {
+    int pos = 0;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint64_t lo = m & ((1ull << s) - 1ull);
+        const int c = popc64(lo);
+        if (k >= c) { k -= c; m >>= s; pos += s; } else m = lo;
+    }
+    return pos;
+}
+AMBI_HD uint64_t all_nodes(int K) { return K >= 64 ? ~0ull : ((1ull << K) - 1ull); }
+// field of `w` bits at bit `bit` of a packed row
+AMBI_HD uint32_t row_field(const uint32_t* row, int bit, int w) {
+    if (w == 0) return 0u;                     // (the last position: the bit may lie behind the row)
+    const int wi = bit >> 5, sh = bit & 31;
+    uint32_t v = row[wi] >> sh;
+    if (sh + w > 32) v |= row[wi + 1] << (32 - sh);
+    return v & ((1u << w) - 1u);
+}
+// the whole order of a row (`row` = its first dword) -> out[d * out_stride], O(K)
+AMBI_HD void row_unpack(const uint32_t* row, int K, uint8_t* out, int out_stride = 1) {
+    if (!row_packed(K)) { for (int d = 0; d < K; d++) out[d * out_stride] = reinterpret_cast<const uint8_t*>(row)[d]; return; }
+    uint64_t free_nodes = all_nodes(K);
+    int bit = 0;
+    for (int d = 0; d < K; d++) {
+        const int w = row_field_bits(K, d);
+        const int v = select_bit(free_nodes, (int)row_field(row, bit, w));
+        out[d * out_stride] = (uint8_t)v;
+        free_nodes &= ~(1ull << v);
+        bit += w;
+    }
+}
+AMBI_HD void row_unpack(const uint8_t* row, int K, uint8_t* out, int out_stride = 1) { row_unpack(reinterpret_cast<const uint32_t*>(row), K, out, out_stride); }
+// node d of a row: digits 0..d decoded in turn (a reader that wants every node unpacks the row once: row_unpack)
 AMBI_HD int row_node(const uint32_t* row, int K, int d) {
     if (!row_packed(K)) return (int)reinterpret_cast<const uint8_t*>(row)[d];
-    const int fb = row_bits(K), bit = d * fb, wi = bit >> 5, sh = bit & 31;
-    uint32_t v = row[wi] >> sh;
-    if (sh > 32 - fb) v |= row[wi + 1] << (32 - sh);
-    return (int)(v & ((1u << fb) - 1u));
+    uint64_t free_nodes = all_nodes(K);
+    int bit = 0, v = 0;
+    for (int e = 0; e <= d; e++) {
+        const int w = row_field_bits(K, e);
+        v = select_bit(free_nodes, (int)row_field(row, bit, w));
+        free_nodes &= ~(1ull << v);
+        bit += w;
+    }
+    return v;
 }
 AMBI_HD int row_node(const uint8_t* row, int K, int d) { return row_node(reinterpret_cast<const uint32_t*>(row), K, d); }
 // appends fields to a row being assembled dword by dword
@@ -64,6 +121,23 @@ struct RowBits {
         }
     }
 };
+// a byte row (K node ids) -> its packed row, row_stride(K) bytes
+AMBI_HD void row_pack(const uint8_t* nodes, int K, uint32_t* row) {
+    if (!row_packed(K)) {
+        uint8_t* b = reinterpret_cast<uint8_t*>(row);
+        for (int x = 0; x < row_stride(K); x++) b[x] = x < K ? nodes[x] : (uint8_t)0xFF;
+        return;
+    }
+    RowBits rb;
+    auto flush = [&](int wi, uint32_t w) { row[wi] = w; };
+    uint64_t free_nodes = all_nodes(K);
+    for (int d = 0; d < K; d++) {
+        const int v = nodes[d];
+        rb.put(lehmer_digit(free_nodes, v), row_field_bits(K, d), flush);
+        free_nodes &= ~(1ull << v);
+    }
+    rb.finish(row_stride(K) / 4, flush);
+}
 
 // ---- atomics usable from both builds ----
 AMBI_HD uint64_t atomic_cas_u64(uint64_t* p, uint64_t expected, uint64_t desired) {
@@ -75,9 +149,6 @@ AMBI_HD uint64_t atomic_cas_u64(uint64_t* p, uint64_t expected, uint64_t desired
     return old;
 #endif
 }
-
-AMBI_HD int ctz64(uint64_t x) { return __builtin_ctzll(x); }
-AMBI_HD int popc64(uint64_t x) { return __builtin_popcountll(x); }
 
 // nodes that may be appended to the ideal I: not in I, all predecessors in I.  `pred` must have 64 readable entries
 // (entries >= K are read and masked off).  Serial code on a lone wavefront is paid in taken branches (~25 cycles) and
@@ -463,7 +534,7 @@ template <int NW, class AUTO>
 AMBI_HD void enumerate_rows(const AUTO& au, const AutoView& cntView, int K, uint64_t first, int nrows,
                             const LaneStacks& S, uint32_t* out) {
     // (NW = dwords of the register form, one byte per node; `out` = this lane's first row in the table, whose rows are
-    // row_stride(K) bytes: the same for more than 32 nodes, 5 bits per node below -- packed when a row is stored)
+    // row_stride(K) bytes: Lehmer-coded up to 63 nodes -- encoded when a row is stored -- one byte per node above)
     PackedRow<NW> row;
     row.fill(0xFFFFFFFFu);
     int top = -1;
@@ -525,28 +596,23 @@ AMBI_HD void enumerate_rows(const AUTO& au, const AutoView& cntView, int K, uint
         top = nt;
     };
     if (row_packed(K)) {
-        // packed fields: the general path is the rare one (units whose block image does not fit group memory), so a row is
-        // simply re-packed from its byte form when it leaves, dword by dword
+        // Lehmer rows: the general path is the rare one (units whose block image does not fit group memory), so a row is
+        // simply encoded from its byte form when it leaves, dword by dword
         const int onw = row_stride(K) / 4;
-        constexpr int fb = NW <= 8 ? 5 : 6;         // (NW <= 8 <=> up to 32 nodes: row_bits(K), as a constant of the instantiation)
-        constexpr uint32_t fmask = (1u << fb) - 1u;
-        constexpr int kPW = NW <= 8 ? 6 : 13;      // packed dwords (+1 for the straddle of the last field): 5 up to 32 nodes, 12 up to 63
         for (int r0 = 0; r0 < nrows; r0++) {
-            uint32_t p[kPW];
-#pragma unroll
-            for (int i = 0; i < kPW; i++) p[i] = 0xFFFFFFFFu;
+            uint32_t* dst = out + (size_t)r0 * onw;
+            RowBits rb;
+            auto flush = [&](int wi, uint32_t w) { dst[wi] = w; };
+            uint64_t free_nodes = all_nodes(K);
 #pragma unroll
             for (int e = 0; e < NW * 4 && e < 64; e++) {
                 if (e < K) {
-                    const uint32_t v = (row.w[e >> 2] >> ((e & 3) * 8)) & fmask;
-                    const int bit = e * fb, wi = bit >> 5, sh = bit & 31;      // (constants once the loop is unrolled)
-                    p[wi] = (p[wi] & ~(fmask << sh)) | (v << sh);
-                    if (sh > 32 - fb) p[wi + 1] = (p[wi + 1] & ~(fmask >> (32 - sh))) | (v >> (32 - sh));
+                    const int v = (int)((row.w[e >> 2] >> ((e & 3) * 8)) & 63u);
+                    rb.put(lehmer_digit(free_nodes, v), row_field_bits(K, e), flush);
+                    free_nodes &= ~(1ull << v);
                 }
             }
-            uint32_t* dst = out + (size_t)r0 * onw;
-#pragma unroll
-            for (int k = 0; k < kPW - 1; k++) if (k < onw) dst[k] = p[k];
+            rb.finish(onw, flush);
             if (r0 + 1 < nrows) successor();
         }
         return;

@@ -449,28 +449,22 @@ AMBI_HD void emit_blocks_dispatch(const uint32_t* img, int nB, int K, uint32_t r
     const int nw = row_stride(K) / 4;
     uint32_t* table = reinterpret_cast<uint32_t*>(unit_rows);
 #define AMBI_EB(N) emit_blocks_wave<N>(img, nB, rlo, rhi, table, lane_lo, lane_hi, part, parts); return;
-    // (5 bits per node up to 32 nodes: class 0, K <= 20, has 1..4 dwords per row, class 1, K <= 32, has 4 or 5)
-    if (CLS < 0 || CLS == 0) { switch (nw) { case 1: AMBI_EB(1) case 2: AMBI_EB(2) case 3: AMBI_EB(3) case 4: AMBI_EB(4) default: break; } }
-    if (CLS < 0 || CLS == 1) { switch (nw) { case 4: AMBI_EB(4) case 5: AMBI_EB(5) default: break; } }
-    if (CLS < 0 || CLS == 2) { switch (nw) { case 7: AMBI_EB(7) case 8: AMBI_EB(8) case 9: AMBI_EB(9) case 10: AMBI_EB(10) case 11: AMBI_EB(11) case 12: AMBI_EB(12) default: break; } }   // (6 bits per node, 33..63 nodes)
+    // (Lehmer rows, ambi_orders.hpp: class 0, K <= 20, has 1..3 dwords per row, class 1, K <= 32, 3..5, class 2, K <= 63, 5..10)
+    if (CLS < 0 || CLS == 0) { switch (nw) { case 1: AMBI_EB(1) case 2: AMBI_EB(2) case 3: AMBI_EB(3) default: break; } }
+    if (CLS < 0 || CLS == 1) { switch (nw) { case 3: AMBI_EB(3) case 4: AMBI_EB(4) case 5: AMBI_EB(5) default: break; } }
+    if (CLS < 0 || CLS == 2) { switch (nw) { case 5: AMBI_EB(5) case 6: AMBI_EB(6) case 7: AMBI_EB(7) case 8: AMBI_EB(8) case 9: AMBI_EB(9) case 10: AMBI_EB(10) default: break; } }
 #undef AMBI_EB
 }
 
 // A unit with no more orders than the prepare stage unranked for the scan (R <= first_budget: every chain-like DAG) has
-// its whole table among those rows already: the table is a copy (node bytes, then the 0xFF padding of the row), no image.
+// its whole table among those rows already: the table is a copy (the rows encoded, ambi_orders.hpp: row_pack), no image.
 template <class G>
 AMBI_HD void copy_first_rows(const G& g, const uint8_t* first, int K, int64_t R, uint8_t* rows) {
     const int stride = row_stride(K);
-    if (row_packed(K)) {   // one thread per row (at most first_budget = 64 of them): its dwords assembled from the row's bytes
+    if (row_packed(K)) {   // one thread per row (at most first_budget = 64 of them): its Lehmer code from the row's bytes
         uint32_t* out = reinterpret_cast<uint32_t*>(rows);
         const int nw = stride / 4;
-        for (int64_t r = g.tid(); r < R; r += g.size()) {
-            uint32_t* dst = out + r * nw;
-            RowBits rb;
-            auto flush = [&](int wi, uint32_t w) { dst[wi] = w; };
-            for (int d = 0; d < K; d++) rb.put(first[r * kFirstRowStride + d], row_bits(K), flush);
-            rb.finish(nw, flush);
-        }
+        for (int64_t r = g.tid(); r < R; r += g.size()) row_pack(first + r * kFirstRowStride, K, out + r * nw);
         return;
     }
     const int64_t bytes = R * stride;
@@ -488,9 +482,9 @@ AMBI_HD void emit_blocks_dfs_dispatch(const BuildTables& B, const uint32_t* suf,
     const int nw = row_stride(K) / 4;
     uint32_t* table = reinterpret_cast<uint32_t*>(unit_rows);
 #define AMBI_ED(N) emit_blocks_dfs_wave<N>(B, suf, K, block_max, rlo, rhi, table, stack, pw, lane_lo, lane_hi); return;
-    if (CLS < 0 || CLS == 0) { switch (nw) { case 1: AMBI_ED(1) case 2: AMBI_ED(2) case 3: AMBI_ED(3) case 4: AMBI_ED(4) default: break; } }
-    if (CLS < 0 || CLS == 1) { switch (nw) { case 4: AMBI_ED(4) case 5: AMBI_ED(5) default: break; } }
-    if (CLS < 0 || CLS == 2) { switch (nw) { case 7: AMBI_ED(7) case 8: AMBI_ED(8) case 9: AMBI_ED(9) case 10: AMBI_ED(10) case 11: AMBI_ED(11) case 12: AMBI_ED(12) default: break; } }
+    if (CLS < 0 || CLS == 0) { switch (nw) { case 1: AMBI_ED(1) case 2: AMBI_ED(2) case 3: AMBI_ED(3) default: break; } }
+    if (CLS < 0 || CLS == 1) { switch (nw) { case 3: AMBI_ED(3) case 4: AMBI_ED(4) case 5: AMBI_ED(5) default: break; } }
+    if (CLS < 0 || CLS == 2) { switch (nw) { case 5: AMBI_ED(5) case 6: AMBI_ED(6) case 7: AMBI_ED(7) case 8: AMBI_ED(8) case 9: AMBI_ED(9) case 10: AMBI_ED(10) default: break; } }
 #undef AMBI_ED
 }
 // group memory of the walk per wave: the ideals of the current path + prefix words with wrap copies
@@ -620,7 +614,8 @@ AMBI_HD void stage_first(const G& g, const BatchArgs& A, int u, uint8_t* work) {
     for (int pass = 0; pass < 2 && found < 0; pass++) {
         int64_t lim = R < A.first_budget ? R : A.first_budget;
         for (int64_t nidx = 0; nidx < lim; nidx++) {
-            for (int d = g.tid(); d < K; d += g.size()) W.ord[d] = A.first_rows ? rows[nidx * rstride + d] : (uint8_t)row_node(rows + nidx * rstride, K, d);
+            if (A.first_rows) { for (int d = g.tid(); d < K; d += g.size()) W.ord[d] = rows[nidx * rstride + d]; }
+            else if (g.tid() == 0) row_unpack(rows + nidx * rstride, K, W.ord);
             g.sync();
             int Lo = 0;
             int v = eval_order(g, *W.dag, W.ord, forwardDir, inv, W.bkp, U.bkp_cap, &Lo, A.stage_clk ? A.stage_clk + (int64_t)u * kStageSlots : nullptr);
@@ -660,7 +655,7 @@ AMBI_HD int eval_indexed(const G& g, const BatchArgs& A, int u, const FirstWork&
     const UnitIn& U = A.units[u];
     const int K = out->K;
     const uint8_t* rows = A.order_arena + out->order_off;
-    for (int d = g.tid(); d < K; d += g.size()) W.ord[d] = (uint8_t)row_node(rows + nidx * row_stride(K), K, d);
+    if (g.tid() == 0) row_unpack(rows + nidx * row_stride(K), K, W.ord);   // (one pass over the row's digits)
     g.sync();
     InvMap inv{W.inv_src, W.inv_tgt};
     const int v = eval_order_w(g, W, W.ord, forwardDir, inv, W.bkp, U.bkp_cap, L);
@@ -773,7 +768,7 @@ AMBI_HD void stage_all_chunk(const G& g, const BatchArgs& A, int u, const FirstW
         const uint8_t* ord = rows + (int64_t)i * kFirstRowStride;
         if (wide) {
             const uint8_t* trow = A.order_arena + out->order_off + (first + i) * row_stride(K);
-            for (int d = g.tid(); d < K; d += g.size()) W.ord[d] = (uint8_t)row_node(trow, K, d);
+            if (g.tid() == 0) row_unpack(trow, K, W.ord);
             g.sync();
             ord = W.ord;
         }
@@ -811,7 +806,7 @@ AMBI_HD void stage_all_chunk_lanes(const G& g, const BatchArgs& A, int u, const 
         if (i < cnt) {
             if (A.all_rows_from_table && out->order_off >= 0) {   // experiment switch: the orders from the table the enumerate kernel wrote
                 const uint8_t* row = A.order_arena + out->order_off + (first + i) * row_stride(K);
-                for (int d = 0; d < K; d++) rows_t[d * 64 + i] = (uint8_t)row_node(row, K, d);
+                row_unpack(row, K, rows_t + i, 64);
             } else
                 (void)order_unrank(V, K, (uint64_t)(first + i), rows_t + i, 64);
             int L = 0;
