@@ -918,42 +918,64 @@ __global__ __launch_bounds__(256) void ambi_spin_kernel(int64_t ticks, int32_t* 
     if (sink && threadIdx.x == 0 && blockIdx.x == 0x7fffffff) *sink = 1;
 }
 __global__ void ambi_touch_kernel(int32_t* sink) { if (sink && blockIdx.x == 0x7fffffff) *sink = 1; }
-// microseconds from the start of the backlog kernel on a to the end of the tiny kernel on b (both streams idle before and after)
-static int stream_probe_us(hipStream_t a, hipStream_t b, float* us) {
-    static hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    static int64_t ticks_per_us = 0;
-    if (!e0) { HIP_CK(hipEventCreate(&e0)); HIP_CK(hipEventCreate(&e1)); HIP_CK(hipEventCreateWithFlags(&e2, hipEventDisableTiming)); }
-    if (!ticks_per_us) { int dev = 0, khz = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000; ticks_per_us = khz / 1000 > 0 ? khz / 1000 : 100; }
+// What the engine keeps per device ordinal, with PROCESS lifetime (DevicePool::context creates it on first use, on that device;
+// nothing in it is destroyed): the probe's events and the device figures it needs, the dispatch classes of the candidate side
+// streams (side_streams below) and whether the dynamic-LDS ceiling has been set.  `mu` is held by every probe and every look-up.
+struct DeviceContext {
+    std::mutex mu;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;    // the probe's events
+    int64_t ticks_per_us = 100; int ncu = 256;              // wall-clock rate, compute units
+    std::vector<hipStream_t> cand; std::vector<int> cls;    // candidate side streams in creation order, and their classes
+    std::vector<hipStream_t> rep;                           // one stream per class (class index = position)
+    std::vector<std::pair<hipStream_t, uint32_t>> callers;  // callers' streams seen so far, with the SET of classes each collides with
+    bool classed = false;                                   // cls and rep are built
+    bool lds_ceiling = false;                               // every kernel's dynamic-LDS ceiling is set (upload())
+};
+// microseconds from the start of the backlog kernel on a to the end of the tiny kernel on b (both streams of C's device and idle
+// before and after; C.mu held)
+static int stream_probe_us(DeviceContext& C, hipStream_t a, hipStream_t b, float* us) {
     HIP_CK(hipStreamSynchronize(a)); HIP_CK(hipStreamSynchronize(b));
     // 16 rounds of workgroups that hold a CU slot for ~6 us each: ~100 us of backlog
-    int ncu = 256; { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
-    HIP_CK(hipEventRecord(e0, a));
-    hipLaunchKernelGGL(ambi_spin_kernel, dim3(ncu * 8 * 16), dim3(256), 0, a, (int64_t)(6 * ticks_per_us), (int32_t*)nullptr);
-    HIP_CK(hipEventRecord(e2, a));   // (b must not start before a's kernel has been queued: it waits for nothing of a's, only the host order matters)
+    HIP_CK(hipEventRecord(C.e0, a));
+    hipLaunchKernelGGL(ambi_spin_kernel, dim3(C.ncu * 8 * 16), dim3(256), 0, a, (int64_t)(6 * C.ticks_per_us), (int32_t*)nullptr);
+    HIP_CK(hipEventRecord(C.e2, a));   // (b must not start before a's kernel has been queued: it waits for nothing of a's, only the host order matters)
     hipLaunchKernelGGL(ambi_touch_kernel, dim3(1), dim3(64), 0, b, (int32_t*)nullptr);
-    HIP_CK(hipEventRecord(e1, b));
+    HIP_CK(hipEventRecord(C.e1, b));
     HIP_CK(hipStreamSynchronize(a)); HIP_CK(hipStreamSynchronize(b));
     float ms = 0;
-    HIP_CK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_CK(hipEventElapsedTime(&ms, C.e0, C.e1));
     *us = ms * 1e3f;
     return 0;
 }
-int backend_stream_probe(void* a, void* b, float* us) { return stream_probe_us((hipStream_t)a, (hipStream_t)b, us); }
 
 // The dynamic-LDS ceiling of a kernel is a per-function, process-wide attribute: every batch asks for the device limit,
 // so that a second batch with smaller units cannot lower it under a first batch that is still launching (the launches
 // themselves request only what their units need).
 constexpr int kLdsMaxDynamic = 160 * 1024 - 1024;
 
+// Every backend entry that touches the GPU runs on the device of the batch's lease, whatever device the calling thread has
+// current (a batch dealt over several devices answers its per-unit getters from the device that holds the unit; a host
+// program working on another device finds its current device unchanged afterwards).  dev < 0: nothing to select.
+struct DeviceGuard {
+    int prev = -1; bool switched = false;
+    explicit DeviceGuard(int dev) {
+        if (dev < 0 || hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); return; }
+        if (prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard&) = delete; DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
 // ------------------------------------------------------------------------------------------------
 // Per-device resources with PROCESS lifetime.
 //
 // Round 2 created and destroyed 3-4 streams (one of them with a dispatch priority), 6+ events and three pinned allocations
 // with every batch, and a long create / run / destroy loop showed rare stray writes into host memory of the process
-// (DESIGN.md 8b).  Nothing the HIP runtime hands out is destroyed per batch any more: a batch LEASES a context -- side
-// streams, events, the pinned words the kernels report through, a pinned staging block, a pinned result mailbox and
-// grow-only device blocks -- from a per-device free list and gives it back when it is destroyed (after synchronising every
-// stream it used).  Leases are never destroyed; at process exit they are left to the runtime.
+// (DESIGN.md 8b).  Nothing the HIP runtime hands out is destroyed per batch any more: a batch LEASES a context -- events,
+// the pinned words the kernels report through, a pinned staging block, a pinned result mailbox, grow-only device blocks, a
+// copy stream -- from a per-device free list and gives it back when it is destroyed (after synchronising every stream it
+// used).  Its side streams come from the device's context (side_streams).  Leases and contexts are never destroyed; at
+// process exit they are left to the runtime.
 // ------------------------------------------------------------------------------------------------
 struct PinnedWords {                    // what kernels write into host memory (BatchArgs::host_pending, host_needed, express_*, plan_seq, late_flag)
     uint32_t guard_lo[16];
@@ -964,9 +986,7 @@ struct PinnedWords {                    // what kernels write into host memory (
 struct TimingEvents { const char* name; hipEvent_t a, b; };
 struct Lease {
     int device = 0;
-    // side streams, created on first use: lean finish, direct full finish, scan for the first valid order (highest dispatch
-    // priority), lattice kernel of a small batch
-    hipStream_t back_stream = nullptr, full_stream = nullptr, first_stream = nullptr, lattice_stream = nullptr;
+    DeviceContext* ctx = nullptr;   // the device's
     hipEvent_t ev_fork = nullptr, ev_prep = nullptr, ev_back = nullptr, ev_first = nullptr, ev_full = nullptr, ev_plan = nullptr, ev_express = nullptr, ev_lat = nullptr, ev_tail = nullptr;
     PinnedWords* h_words = nullptr; PinnedWords* dh_words = nullptr;
     uint8_t* d_block = nullptr; int64_t d_block_bytes = 0;      // inputs + working set + result blob of the batch
@@ -988,10 +1008,27 @@ struct Lease {
 constexpr int64_t kKeepBlock = 64ll << 20, kKeepArena = 256ll << 20, kKeepCells = 64ll << 20, kKeepStage = 16ll << 20, kKeepMail = 8ll << 20, kKeepRuns = 16ll << 20;
 
 class DevicePool {
-    std::mutex mu_;
+    std::mutex mu_;                       // the free list and the contexts' table: never held during a probe
     std::vector<Lease*> free_;
+    std::vector<DeviceContext*> ctx_;     // one per device ordinal
+    DevicePool() { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n < 0) n = 0; ctx_.assign((size_t)n, nullptr); }
   public:
     static DevicePool& get() { static DevicePool* p = new DevicePool(); return *p; }   // (never destroyed: no HIP call from a static destructor)
+    int context(int dev, DeviceContext** out) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (dev < 0 || dev >= (int)ctx_.size()) return -31;
+        if (!ctx_[dev]) {
+            DeviceGuard dg(dev);
+            DeviceContext* C = new DeviceContext();
+            HIP_CK(hipEventCreate(&C->e0)); HIP_CK(hipEventCreate(&C->e1)); HIP_CK(hipEventCreateWithFlags(&C->e2, hipEventDisableTiming));
+            int khz = 0, ncu = 0;
+            if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz / 1000 > 0) C->ticks_per_us = khz / 1000;
+            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) C->ncu = ncu;
+            ctx_[dev] = C;
+        }
+        *out = ctx_[dev];
+        return 0;
+    }
     int acquire(Lease** out) {
         int dev = 0;
         HIP_CK(hipGetDevice(&dev));
@@ -1010,8 +1047,10 @@ class DevicePool {
                                     "instead of 1.10 ms per 4096-sample step).  Set GPU_MAX_HW_QUEUES=8 in the environment before the HIP runtime starts.\n", q ? q : "unset");
             });
         }
+        DeviceContext* C = nullptr;
+        if (int rc = context(dev, &C)) return rc;
         Lease* L = new Lease();
-        L->device = dev;
+        L->device = dev; L->ctx = C;
         hipEvent_t* evs[] = {&L->ev_fork, &L->ev_prep, &L->ev_back, &L->ev_first, &L->ev_full, &L->ev_plan, &L->ev_express, &L->ev_lat, &L->ev_tail};
         for (hipEvent_t* e : evs) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CK(hipHostMalloc((void**)&L->h_words, sizeof(PinnedWords)));
@@ -1028,86 +1067,66 @@ class DevicePool {
         free_.push_back(L);
     }
 };
-// a side stream of the lease (one of its members): created on first use, with the device's highest dispatch priority if `highest`
-// and the device has priorities
-static int lease_stream(hipStream_t* side, bool highest, hipStream_t* out) {
-    if (!*side) {
-        int least = 0, greatest = 0;
-        if (highest && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-            HIP_CK(hipStreamCreateWithPriority(side, hipStreamNonBlocking, greatest));
-        } else {
-            if (highest) (void)hipGetLastError();   // no priorities on this device
-            HIP_CK(hipStreamCreateWithFlags(side, hipStreamNonBlocking));
-        }
-    }
-    *out = *side;
-    return 0;
-}
 // ---- side streams that really run beside the caller's stream ----
 // The command processor hands out workgroups through four dispatch pipes; the streams of a process are spread over them in
 // creation order, and two streams on one pipe hand out their kernels' workgroups one kernel after the other.  Which pipe a stream
-// got cannot be asked, only observed (stream_probe_us), so the pool keeps eight candidate streams per device, sorted into
+// got cannot be asked, only observed (stream_probe_us), so the device's context keeps eight candidate streams, sorted into
 // classes of streams that do NOT run side by side, learns the class of every caller's stream when it first sees it, and gives a
 // batch side streams from the other classes.  (Round 3 relied on the creation order: correct for the legacy default stream in a
 // process that creates no other streams first, 1.28 instead of 0.86 ms per step on a stream of torch's pool.)
-struct StreamClasses {
-    std::vector<hipStream_t> cand; std::vector<int> cls;    // candidates and their classes
-    std::vector<hipStream_t> rep;                            // one stream per class (class index = position)
-    std::vector<std::pair<hipStream_t, uint32_t>> callers;   // callers' streams seen so far, with the SET of classes each collides with
-    bool built = false;
-};
 constexpr float kProbeSharedUs = 55.f;   // measured: 10-17 us side by side, 105-125 us behind the backlog
-static std::mutex g_classes_mu;
-static StreamClasses g_classes[16];
-static int stream_class_of(StreamClasses& C, hipStream_t s, int* out) {   // -1: runs beside every known class
+struct SideStreams { hipStream_t lean = nullptr, full = nullptr, scan = nullptr; };   // lean finish, direct full finish, scan for the first valid order + lattice kernel
+static int add_candidates(DeviceContext& C, size_t n) {   // the first n candidates exist
+    while (C.cand.size() < n) { hipStream_t t; HIP_CK(hipStreamCreateWithFlags(&t, hipStreamNonBlocking)); C.cand.push_back(t); }
+    return 0;
+}
+static int stream_class_of(DeviceContext& C, hipStream_t s, int* out) {   // -1: runs beside every known class
     for (size_t c = 0; c < C.rep.size(); c++) {
         float us = 0;
-        if (int rc = stream_probe_us(C.rep[c], s, &us)) return rc;
+        if (int rc = stream_probe_us(C, C.rep[c], s, &us)) return rc;
         if (us > kProbeSharedUs) { *out = (int)c; return 0; }
     }
     *out = -1;
     return 0;
 }
-static int build_stream_classes(StreamClasses& C) {
-    if (C.built) return 0;
-    { float us; hipStream_t t0, t1;   // first use of the probe kernels (code loading) outside the measurements
-      HIP_CK(hipStreamCreateWithFlags(&t0, hipStreamNonBlocking)); HIP_CK(hipStreamCreateWithFlags(&t1, hipStreamNonBlocking));
-      C.cand.push_back(t0); C.cand.push_back(t1);
-      if (int rc = stream_probe_us(t0, t1, &us)) return rc; }
+static int build_stream_classes(DeviceContext& C) {
+    if (C.classed) return 0;
+    C.cls.clear(); C.rep.clear();
+    { float us;   // first use of the probe kernels (code loading) outside the measurements
+      if (int rc = add_candidates(C, 2)) return rc;
+      if (int rc = stream_probe_us(C, C.cand[0], C.cand[1], &us)) return rc; }
     // eight candidates; up to sixteen while fewer than four classes have shown up (other libraries' streams -- RCCL's -- sit between
     // the engine's in creation order)
     for (size_t i = 0; i < 16; i++) {
         if (i >= 8 && C.rep.size() >= 4) break;
-        if (i >= C.cand.size()) { hipStream_t t; HIP_CK(hipStreamCreateWithFlags(&t, hipStreamNonBlocking)); C.cand.push_back(t); }
+        if (int rc = add_candidates(C, i + 1)) return rc;
         int c = -1;
         if (int rc = stream_class_of(C, C.cand[i], &c)) return rc;
         if (c < 0) { c = (int)C.rep.size(); C.rep.push_back(C.cand[i]); }
         C.cls.push_back(c);
     }
-    C.built = true;
+    C.classed = true;
     if (ambi_env("AMBI_DEBUG")) { fprintf(stderr, "ambigram_hip: %zu dispatch classes among %zu candidate streams:", C.rep.size(), C.cand.size()); for (int c : C.cls) fprintf(stderr, " %d", c); fprintf(stderr, "\n"); }
     return 0;
 }
-// side streams for a batch whose kernels start on `caller`: out[k], k = 0 lean finish, 1 direct full finish, 2 scan / lattice -- from
-// classes other than the caller's and, while there are enough classes, from different ones; `set`: which of the candidates of a class
-static int classified_side_streams(int device, hipStream_t caller, int set, hipStream_t out[3]) {
-    if (device < 0 || device >= 16) return -31;
-    std::lock_guard<std::mutex> lk(g_classes_mu);
-    StreamClasses& C = g_classes[device];
-    if (int rc = build_stream_classes(C)) return rc;
+// The side streams of a batch whose kernels start on `caller`: from classes other than the caller's and, while there are enough
+// classes, from different ones; `set`: which of the candidates of a class.  Never a null stream on success.
+static int side_streams(DeviceContext& C, hipStream_t caller, int set, bool classes_on, SideStreams* out) {
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (classes_on) { if (int rc = build_stream_classes(C)) return rc; }
     // Every class the caller's stream collides with, in either direction: a stream can sit on the dispatch pipe of one class AND share a
     // hardware queue with a candidate of another (the legacy default stream of a process that creates it after the candidates: the lattice
     // kernel of a single sample then ran BEHIND the express kernel on one queue, 142 instead of 89 us end to end from a C caller).
-    const int nc = (int)C.rep.size();
-    uint32_t mask = 0; bool known = false;
+    const int nc = classes_on ? (int)C.rep.size() : 0;   // (classes off: none, and no probe)
+    uint32_t mask = 0; bool known = nc == 0;
     for (auto& pr : C.callers) if (pr.first == caller) { mask = pr.second; known = true; }
     if (!known) {
-        for (size_t i = 0; i < C.cand.size(); i++) if (C.cand[i] == caller) { mask = 1u << C.cls[i]; known = true; }
+        for (size_t i = 0; i < C.cls.size(); i++) if (C.cand[i] == caller) { mask = 1u << C.cls[i]; known = true; }
         if (!known) {
             for (int c = 0; c < nc; c++) {
                 float ab = 0, ba = 0;
-                if (int rc = stream_probe_us(C.rep[c], caller, &ab)) return rc;
-                if (ab <= kProbeSharedUs) { if (int rc = stream_probe_us(caller, C.rep[c], &ba)) return rc; }
+                if (int rc = stream_probe_us(C, C.rep[c], caller, &ab)) return rc;
+                if (ab <= kProbeSharedUs) { if (int rc = stream_probe_us(C, caller, C.rep[c], &ba)) return rc; }
                 if (ab > kProbeSharedUs || ba > kProbeSharedUs) mask |= 1u << c;
             }
         }
@@ -1116,18 +1135,33 @@ static int classified_side_streams(int device, hipStream_t caller, int set, hipS
     }
     int cc = -1;
     for (int c = 0; c < nc; c++) if ((mask >> c) & 1u) { cc = c; break; }
+    hipStream_t s[3];
     int k = 0;
     for (int step = 1; step <= nc && k < 3; step++) {
         const int c = ((cc < 0 ? 0 : cc) + step) % nc;
         if ((mask >> c) & 1u) continue;
         // the set-th candidate of class c (wrapping)
         std::vector<hipStream_t> of;
-        for (size_t i = 0; i < C.cand.size(); i++) if (C.cls[i] == c) of.push_back(C.cand[i]);
+        for (size_t i = 0; i < C.cls.size(); i++) if (C.cls[i] == c) of.push_back(C.cand[i]);
         if (of.empty()) continue;
-        out[k++] = of[(size_t)set % of.size()];
+        s[k++] = of[(size_t)set % of.size()];
     }
-    for (int j = k; j < 3; j++) out[j] = k > 0 ? out[j % k] : nullptr;   // fewer classes than streams: some share
-    return k > 0 ? 0 : 1;   // 1: every stream behaves like the caller's (a profiler that serialises the kernels): nothing to choose
+    if (k == 0) {   // every class behaves like the caller's stream (a profiler that serialises the kernels), or classes off: creation order
+        if (int rc = add_candidates(C, 3)) return rc;
+        for (; k < 3; k++) s[k] = C.cand[k];
+    }
+    for (int j = k; j < 3; j++) s[j] = s[j % k];   // fewer classes than streams: some share
+    *out = SideStreams{s[0], s[1], s[2]};
+    return 0;
+}
+// ambi_debug_stream_probe: on the current device, serialised with the engine's own probes there
+int backend_stream_probe(void* a, void* b, float* us) {
+    int dev = 0;
+    HIP_CK(hipGetDevice(&dev));
+    DeviceContext* C = nullptr;
+    if (int rc = DevicePool::get().context(dev, &C)) return rc;
+    std::lock_guard<std::mutex> lk(C->mu);
+    return stream_probe_us(*C, (hipStream_t)a, (hipStream_t)b, us);
 }
 
 // grow-only block of the lease (device memory, or pinned host memory with its device address)
@@ -1159,18 +1193,6 @@ struct DevBuf {
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-// Every backend entry that touches the GPU runs on the device of the batch's lease, whatever device the calling thread has
-// current (a batch dealt over several devices answers its per-unit getters from the device that holds the unit; a host
-// program working on another device finds its current device unchanged afterwards).  dev < 0: nothing to select.
-struct DeviceGuard {
-    int prev = -1; bool switched = false;
-    explicit DeviceGuard(int dev) {
-        if (dev < 0 || hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete; DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1223,18 +1245,14 @@ class HipBackend : public Backend {
     int shared_units_ = -1;   // units whose table is written by several workgroups: -1 unknown, else the count
     long timed_runs_ = 0;
     hipEvent_t ev_fork_ = nullptr;
-    // overlap of [first valid order, finish] with the enumerate kernel: own stream + two events (the lease's)
+    // overlap of [first valid order, finish] with the enumerate kernel: side streams + events (the lease's)
     bool overlap_back_ = false, want_overlap_ = true;
-    hipStream_t back_stream_ = nullptr;
+    SideStreams side_; hipStream_t side_for_ = (hipStream_t)-1;   // side streams of the step (side_streams) and the caller's stream they were chosen for
     hipEvent_t ev_prep_ = nullptr, ev_back_ = nullptr, ev_first_ = nullptr, ev_full_ = nullptr;
-    hipStream_t full_stream_ = nullptr;
     bool first_launched_ = false; hipEvent_t ev_plan_ = nullptr;
     uint8_t* d_direct_cells_ = nullptr; int64_t direct_stride_ = 0; int direct_slots_ = 0; int lds_finish_ext_ = 0; bool direct_ext_ = true;   // env AMBI_DIRECT_EXT: the direct launch keeps its path cells in device memory
     int direct_cells_ = 0; bool direct_retry_ = false;   // path area of the direct full-finish launch (0: the batch's capacity bound); env AMBI_DIRECT_CELLS
     int full_threads_ = 1024;  // env AMBI_FULL_THREADS: threads per workgroup of the direct full-finish launch (256 / 512 / 1024)
-    bool classed_ = true;              // env AMBI_STREAM_CLASSES=0: side streams by creation order (rounds 1-3) instead of by observed dispatch class
-    hipStream_t classed_for_ = (hipStream_t)-1; hipStream_t classed_streams_[3] = {nullptr, nullptr, nullptr};
-    hipStream_t first_stream_ = nullptr;   // the scan for the first valid order, started beside the plan kernel (launch_front)
     int32_t* d_direct_list_ = nullptr; int direct_n_ = 0, direct_grid_ = 1024;
     int32_t* d_edit_list_ = nullptr; bool direct_edit_ = true; int lds_finish_edit_ = 0, edit_grid_ = 1024;   // env AMBI_DIRECT_EDIT: these units through stage_finish_edit first (ambi_finish_edit_kernel), the ext launch behind it for what that hands on
     // express path (small batches): one kernel reconstructs every unit whose first order assembles; results are complete at ev_express_
@@ -1242,7 +1260,7 @@ class HipBackend : public Backend {
     static constexpr int kExpressThreads = 512;   // the serial stages use three wavefronts, the finish stage and the mailbox copy all of them
     int express_units_ = 32, lds_express_ = 0, lds_lattice_ = 0, lds_lattice_own_ = 0;
     bool lazy_ = false, tables_written_ = false;   // FLAG_LAZY_ORDERS: the run leaves the order tables out; they are written on demand
-    bool side_lattice_ = false, flushed_ = false; hipStream_t lattice_stream_ = nullptr;   // small batches: the lattice kernel beside the express kernel
+    bool side_lattice_ = false, flushed_ = false;   // small batches: the lattice kernel beside the express kernel
     uint64_t* d_lat_R_ = nullptr; int32_t* d_lat_status_ = nullptr; int64_t* d_lat_sum_ = nullptr;
     bool express_ = false;
     hipEvent_t ev_express_ = nullptr;
@@ -1273,15 +1291,12 @@ class HipBackend : public Backend {
     bool debug_ = false;      // env AMBI_DEBUG: budgets and grids chosen; guard words of the direct path areas checked at wait()
 
     // Everything this batch queued is complete when this returns: the caller's stream (only if a run is still in flight -- the
-    // stream must outlive its work) and every side stream of the lease, each synchronised EXPLICITLY (round 2 relied on
-    // hipFree's implicit device synchronisation and destroyed streams it had never synchronised).
+    // stream must outlive its work), the side streams this batch used and the lease's copy and run streams, each synchronised
+    // EXPLICITLY (round 2 relied on hipFree's implicit device synchronisation and destroyed streams it had never synchronised).
     void sync_all() {
         if (!lease_) return;
         if (inflight_) { (void)hipStreamSynchronize(stream_); inflight_ = false; }
-        for (hipStream_t s : {lease_->back_stream, lease_->full_stream, lease_->first_stream, lease_->lattice_stream}) if (s) (void)hipStreamSynchronize(s);
-        if (lease_->copy_stream) (void)hipStreamSynchronize(lease_->copy_stream);
-        if (lease_->run_stream) (void)hipStreamSynchronize(lease_->run_stream);
-        for (hipStream_t s : classed_streams_) if (s) (void)hipStreamSynchronize(s);
+        for (hipStream_t s : {side_.lean, side_.full, side_.scan, lease_->copy_stream, lease_->run_stream}) if (s) (void)hipStreamSynchronize(s);
         (void)hipGetLastError();
     }
     // guard words around the pinned words the kernels write through (always) and around the path areas of the direct
@@ -1401,8 +1416,8 @@ class HipBackend : public Backend {
         debug_ = ambi_env("AMBI_DEBUG") != nullptr;
         if ((rc = DevicePool::get().acquire(&lease_))) return rc;
         Lease* L = lease_;
-        if (device_ != L->device) classed_for_ = (hipStream_t)-1;   // (another device: its own stream classes)
         device_ = L->device;
+        side_ = SideStreams{}; side_for_ = (hipStream_t)-1;   // (chosen by the first run)
         h_npending_ = &L->h_words->npending; h_needed_ = L->h_words->needed;
         dh_npending_ = &L->dh_words->npending; dh_needed_ = L->dh_words->needed;
         h_express_left_ = &L->h_words->express_left; dh_express_left_ = &L->dh_words->express_left;
@@ -1444,10 +1459,10 @@ class HipBackend : public Backend {
                     lds_prepare_, lds_first_, lds_finish_, lds_enum_, lds_blocks_);
             return ST_ERR_BAD_INPUT;
         }
-        {   // the dynamic-LDS ceiling of every kernel: a per-function, process-wide attribute, set once
-            static std::mutex mu; static uint64_t done = 0; hipError_t err = hipSuccess;   // (per device: one bit each)
-            std::lock_guard<std::mutex> lk(mu);
-            if (!((done >> (L->device & 63)) & 1ull)) {
+        {   // the dynamic-LDS ceiling of every kernel: a per-function, process-wide attribute, set once per device
+            hipError_t err = hipSuccess;
+            std::lock_guard<std::mutex> lk(L->ctx->mu);
+            if (!L->ctx->lds_ceiling) {
                 const void* fns[] = {(const void*)ambi_blocks_build_kernel, (const void*)ambi_prepare_kernel, (const void*)ambi_first_kernel, (const void*)ambi_resolve_kernel,
                                      (const void*)ambi_finish_kernel, (const void*)ambi_finish_ext_kernel, (const void*)ambi_finish_edit_kernel, (const void*)ambi_finish_lean_kernel,
                                      (const void*)ambi_enumerate_kernel<0>, (const void*)ambi_enumerate_kernel<1>, (const void*)ambi_enumerate_kernel<2>,
@@ -1455,7 +1470,7 @@ class HipBackend : public Backend {
                                      (const void*)ambi_express_kernel, (const void*)ambi_lattice_kernel, (const void*)ambi_lattice_own_kernel, (const void*)ambi_search_kernel, (const void*)ambi_all_kernel,
                                      (const void*)ambi_all_lanes_kernel, (const void*)ambi_order_paths_kernel};
                 for (const void* f : fns) { hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMaxDynamic); if (e != hipSuccess) err = e; }
-                if (err == hipSuccess) done |= 1ull << (L->device & 63);   // (a failed attempt is tried again by the next upload)
+                L->ctx->lds_ceiling = err == hipSuccess;   // (a failed attempt is tried again by the next upload)
             }
             HIP_CK(err);
         }
@@ -1469,30 +1484,20 @@ class HipBackend : public Backend {
         { const char* e9 = ambi_env("AMBI_BLOCK_DFS"); block_dfs_ = e9 ? (atoi(e9) != 0) : 1; }
         { const char* e9 = ambi_env("AMBI_EMIT_INTERLEAVE"); emit_interleave_ = e9 ? (atoi(e9) != 0) : 1; }
         { const char* e5 = ambi_env("AMBI_OVERLAP_BACK"); want_overlap_ = e5 ? atoi(e5) != 0 : true; }
-        back_stream_ = nullptr; full_stream_ = nullptr; first_stream_ = nullptr; direct_n_ = 0; d_direct_cells_ = nullptr; direct_slots_ = 0;
-        { const char* e = ambi_env("AMBI_STREAM_CLASSES"); classed_ = e ? atoi(e) != 0 : true; }
+        direct_n_ = 0; d_direct_cells_ = nullptr; direct_slots_ = 0;
         std::vector<int32_t> dl;
         if (want_overlap_) {
-            // the stream of the lean finish kernel: default dispatch priority (the lowest, round 1's setting, measured slower: with
-            // the scan out of the way early the finish kernels have the whole enumerate kernel to hide behind, and holding them
-            // back only lengthens the tail after it: 1.185 -> 1.168 ms per step, four interleaved runs)
-            if ((rc = lease_stream(&L->back_stream, false, &back_stream_))) return rc;
             // (direct full-stage launch: 512 threads with the path cells in device memory, 1024 with the cells in group memory --
             // measured, four interleaved runs: cells in group memory 1.151 ms per step; in device memory 256 / 512 / 1024
             // threads = 1.133 / 1.110 / 1.200)
             { const char* ee = ambi_env("AMBI_DIRECT_EXT"); direct_ext_ = ee ? atoi(ee) != 0 : true; }
             { const char* e = ambi_env("AMBI_FULL_THREADS"); full_threads_ = e ? atoi(e) : (direct_ext_ ? 512 : 1024); if (full_threads_ != 256 && full_threads_ != 512 && full_threads_ != 1024) full_threads_ = direct_ext_ ? 512 : 1024; }
-            if ((rc = lease_stream(&L->first_stream, true, &first_stream_))) return rc;
             {   // units that go straight to the full finish stage (env AMBI_DIRECT_FULL=0: none, they pass through the lean stage first)
                 const char* e7 = ambi_env("AMBI_DIRECT_FULL"); const bool on = e7 ? atoi(e7) != 0 : true;
                 const char* e8 = ambi_env("AMBI_DIRECT_GRID"); direct_grid_ = e8 ? atoi(e8) : 1024; if (direct_grid_ < 1) direct_grid_ = 1;   // one workgroup per unit up to 1024 (measured: 64 / 128 / 256 / 512 workgroups for 512 units = 1.63 / 1.37 / 1.25 / 1.23 ms per step; without this launch 1.30)
                 if (on && lean_finish_) for (size_t u2 = 0; u2 < U; u2++) if (H.units[u2].direct_full) dl.push_back((int32_t)u2);
                 direct_n_ = (int)dl.size();
                 if (direct_n_ > 0) {
-                    // the direct full-finish stream: default priority.  The stream belongs to the lease and is never destroyed -- with
-                    // round 2's per-batch create / destroy of a priority stream here a long soak showed stray writes into host memory
-                    // (DESIGN.md 8b).
-                    if ((rc = lease_stream(&L->full_stream, false, &full_stream_))) return rc;
                     if (direct_ext_) lds_finish_ext_ = (int)finish_work_bytes(H.max_n, H.max_m, H.max_bkp, 0, H.max_out);
                     { const char* ed = ambi_env("AMBI_DIRECT_EDIT"); direct_edit_ = (ed ? atoi(ed) != 0 : true) && direct_ext_; }
                     { const char* eg = ambi_env("AMBI_EDIT_GRID"); edit_grid_ = eg ? atoi(eg) : 1024; if (edit_grid_ < 1) edit_grid_ = 1; }
@@ -1507,7 +1512,6 @@ class HipBackend : public Backend {
             lds_lattice_ = (int)(64 * 8 + kPrepLatticeBytes + 64);
             lds_lattice_own_ = (int)lattice_own_bytes(H.max_k) + 64;
             side_lattice_ = (int)U <= express_units_;
-            if (side_lattice_ && (rc = lease_stream(&L->lattice_stream, false, &lattice_stream_))) return rc;
         }
         // result mailbox in pinned host memory: batches that can take the express path, while the slots stay small
         mail_off_.assign(U, 0); mail_bytes_ = 0; mail_on_ = false; mail_valid_ = false;
@@ -1659,7 +1663,7 @@ class HipBackend : public Backend {
             if (side) {
                 lease_->h_words->lat_unsure = 0;
                 if (flushed_) (void)hipEventRecord(ev_fork_, st);
-                (void)hipStreamWaitEvent(lattice_stream_, flushed_ ? ev_fork_ : lease_->ev_tail, 0);
+                (void)hipStreamWaitEvent(side_.scan, flushed_ ? ev_fork_ : lease_->ev_tail, 0);
             }
             tick("ambi_express_kernel", 0, true);
             hipLaunchKernelGGL(ambi_express_kernel, dim3(A.n_units), dim3(kExpressThreads), lds_express_, st, Ax);
@@ -1667,8 +1671,8 @@ class HipBackend : public Backend {
             (void)hipEventRecord(ev_express_, st);
             tick("ambi_plan_kernel", 1, true);
             if (side) {   // the lattice beside the express kernel, on a stream of its own; the plan kernel behind both
-                hipLaunchKernelGGL(ambi_lattice_own_kernel, dim3(A.n_units), dim3(64), lds_lattice_own_, lattice_stream_, A);
-                (void)hipEventRecord(lease_->ev_lat, lattice_stream_);
+                hipLaunchKernelGGL(ambi_lattice_own_kernel, dim3(A.n_units), dim3(64), lds_lattice_own_, side_.scan, A);
+                (void)hipEventRecord(lease_->ev_lat, side_.scan);
                 (void)hipStreamWaitEvent(st, lease_->ev_lat, 0);
             } else
             hipLaunchKernelGGL(ambi_lattice_kernel, dim3(A.n_units), dim3(64), lds_lattice_, st, A);
@@ -1682,11 +1686,11 @@ class HipBackend : public Backend {
             // instead of queueing behind 4096 enumerate workgroups for group memory.
             if (overlap_back_) {
                 (void)hipEventRecord(ev_prep_, st);
-                (void)hipStreamWaitEvent(first_stream_, ev_prep_, 0);
-                tick("ambi_first_kernel", 4, true, first_stream_);
-                hipLaunchKernelGGL(ambi_first_kernel, dim3(A.n_units), dim3(64), lds_first_, first_stream_, A);
-                tick("ambi_first_kernel", 4, false, first_stream_);
-                (void)hipEventRecord(ev_first_, first_stream_);
+                (void)hipStreamWaitEvent(side_.scan, ev_prep_, 0);
+                tick("ambi_first_kernel", 4, true, side_.scan);
+                hipLaunchKernelGGL(ambi_first_kernel, dim3(A.n_units), dim3(64), lds_first_, side_.scan, A);
+                tick("ambi_first_kernel", 4, false, side_.scan);
+                (void)hipEventRecord(ev_first_, side_.scan);
                 first_launched_ = true;
             }
             tick("ambi_plan_kernel", 1, true);
@@ -1750,7 +1754,7 @@ class HipBackend : public Backend {
         // enumerate kernel it is launched AHEAD of it: behind the enumerate kernel in launch order its 4096 one-wave
         // workgroups only get group memory as enumerate workgroups retire (0.06 ms alone, 0.5-0.6 ms beside), and the
         // finish kernels behind it then start half-way through the table and end after it.
-        hipStream_t sb = overlap_back_ ? back_stream_ : st;
+        hipStream_t sb = overlap_back_ ? side_.lean : st;
         auto launch_first = [&]() {
             tick("ambi_first_kernel", 4, true, sb);
             hipLaunchKernelGGL(ambi_first_kernel, dim3(U), dim3(64), lds_first_, sb, A);
@@ -1758,7 +1762,7 @@ class HipBackend : public Backend {
         };
         if (first_launched_) {   // started beside the plan kernel (launch_front): the finish kernels wait for both
             (void)hipStreamWaitEvent(sb, ev_first_, 0); (void)hipStreamWaitEvent(sb, ev_plan_, 0);
-            if (full_stream_) (void)hipStreamWaitEvent(full_stream_, ev_plan_, 0);
+            if (direct_n_ > 0) (void)hipStreamWaitEvent(side_.full, ev_plan_, 0);
         } else if (overlap_back_) {   // (express chain) on the back stream behind the plan kernel, ahead of the enumerate launch
             (void)hipStreamWaitEvent(sb, ev_prep_, 0);
             launch_first();
@@ -1780,8 +1784,8 @@ class HipBackend : public Backend {
         if (!overlap_back_) launch_first();   // behind the enumerate kernel on the caller's stream
         // units with deletion / duplication candidates go straight to the full finish stage, on a stream of their own beside
         // the lean kernel (both behind the scan, both beside the enumerate kernel); few workgroups, each taking units in turn
-        if (direct_n_ > 0 && overlap_back_ && full_stream_) {
-            (void)hipStreamWaitEvent(full_stream_, ev_first_, 0);
+        if (direct_n_ > 0 && overlap_back_) {
+            (void)hipStreamWaitEvent(side_.full, ev_first_, 0);
             const int dgrid = direct_n_ < direct_grid_ ? direct_n_ : direct_grid_;
             // path area of this launch: the capacity bound of the batch, or (experiment switch AMBI_DIRECT_CELLS, see wait())
             // fewer cells -- a path that does not fit then goes through the list kernel behind, which has the full area
@@ -1792,23 +1796,23 @@ class HipBackend : public Backend {
                 lds_direct = (int)finish_work_bytes(hb().max_n, hb().max_m, hb().max_bkp, direct_cells_, hb().max_out);
             }
             direct_retry_ = Ad.finish_retry != 0;
-            tick("ambi_finish_ext_kernel", 6, true, full_stream_);
+            tick("ambi_finish_ext_kernel", 6, true, side_.full);
             if (direct_ext_ && d_direct_cells_ && direct_edit_) {
                 // the edits of lone SVs on the runs of the path; what that stage hands on (chaining SVs, lists that outgrow their room)
                 // to the launch with the path cells in device memory, over the list the first one leaves on the device
                 direct_retry_ = false;
                 const int egrid = direct_n_ < edit_grid_ ? direct_n_ : edit_grid_;
-                hipLaunchKernelGGL(ambi_finish_edit_kernel, dim3(egrid), dim3(256), lds_finish_edit_, full_stream_, A, (const int32_t*)d_direct_list_, direct_n_, d_edit_list_, d_refin_count_ + 1);
-                hipLaunchKernelGGL(ambi_finish_ext_kernel, dim3(dgrid < 64 ? dgrid : 64), dim3(full_threads_), lds_finish_ext_, full_stream_, A, (const int32_t*)d_edit_list_, 0, d_direct_cells_, direct_stride_,
+                hipLaunchKernelGGL(ambi_finish_edit_kernel, dim3(egrid), dim3(256), lds_finish_edit_, side_.full, A, (const int32_t*)d_direct_list_, direct_n_, d_edit_list_, d_refin_count_ + 1);
+                hipLaunchKernelGGL(ambi_finish_ext_kernel, dim3(dgrid < 64 ? dgrid : 64), dim3(full_threads_), lds_finish_ext_, side_.full, A, (const int32_t*)d_edit_list_, 0, d_direct_cells_, direct_stride_,
                                    (const int32_t*)(d_refin_count_ + 1));
             } else
             if (direct_ext_ && d_direct_cells_) {   // path cells in device memory: a 13 KB workgroup that fits where a lean one fits
                 direct_retry_ = false;
-                hipLaunchKernelGGL(ambi_finish_ext_kernel, dim3(dgrid), dim3(full_threads_), lds_finish_ext_, full_stream_, A, (const int32_t*)d_direct_list_, direct_n_, d_direct_cells_, direct_stride_);
+                hipLaunchKernelGGL(ambi_finish_ext_kernel, dim3(dgrid), dim3(full_threads_), lds_finish_ext_, side_.full, A, (const int32_t*)d_direct_list_, direct_n_, d_direct_cells_, direct_stride_);
             } else
-            hipLaunchKernelGGL(ambi_finish_kernel, dim3(dgrid), dim3(full_threads_), lds_direct, full_stream_, Ad, (const int32_t*)d_direct_list_, (const int32_t*)nullptr, direct_n_);
-            tick("ambi_finish_ext_kernel", 6, false, full_stream_);
-            (void)hipEventRecord(ev_full_, full_stream_);
+            hipLaunchKernelGGL(ambi_finish_kernel, dim3(dgrid), dim3(full_threads_), lds_direct, side_.full, Ad, (const int32_t*)d_direct_list_, (const int32_t*)nullptr, direct_n_);
+            tick("ambi_finish_ext_kernel", 6, false, side_.full);
+            (void)hipEventRecord(ev_full_, side_.full);
         }
         tick("ambi_finish_kernel", 5, true, sb);
         const int fgrid = finish_grid_for(U);
@@ -1818,14 +1822,14 @@ class HipBackend : public Backend {
             // units whose SVs chain or edit the path: the full stage right behind, over the list the lean kernel left on the
             // device (an empty list costs one launch of workgroups that exit at once)
             if (hb().any_sv) {
-                if (direct_retry_ && direct_n_ > 0 && overlap_back_ && full_stream_) (void)hipStreamWaitEvent(sb, ev_full_, 0);   // the direct launch may add to the list
+                if (direct_retry_ && direct_n_ > 0 && overlap_back_) (void)hipStreamWaitEvent(sb, ev_full_, 0);   // the direct launch may add to the list
                 hipLaunchKernelGGL(ambi_finish_kernel, dim3(U < 256 ? U : 256), dim3(256), lds_finish_, sb, A, (const int32_t*)d_refin_list_, (const int32_t*)d_refin_count_, -1);   // (at most one such workgroup fits a CU: more than 256 gain nothing)
             }
         } else hipLaunchKernelGGL(ambi_finish_kernel, dim3(U), dim3(256), lds_finish_, sb, A, (const int32_t*)nullptr, (const int32_t*)nullptr, -1);
         tick("ambi_finish_kernel", 5, false, sb);
         if (overlap_back_) {
             (void)hipEventRecord(ev_back_, sb); (void)hipStreamWaitEvent(st, ev_back_, 0);
-            if (direct_n_ > 0 && full_stream_) (void)hipStreamWaitEvent(st, ev_full_, 0);
+            if (direct_n_ > 0) (void)hipStreamWaitEvent(st, ev_full_, 0);
         }
     }
 
@@ -1847,21 +1851,12 @@ class HipBackend : public Backend {
         if (!uploaded_) return -32;
         if (ran_ && !tuned_ && tables_written_) { if (int rc = tune_after_first_run()) return rc; }
         stream_ = (hipStream_t)stream;
-        if (classed_ && (back_stream_ || side_lattice_)) {
+        if ((want_overlap_ || side_lattice_) && stream_ != side_for_) {
             // side streams that dispatch beside THIS caller's stream (learnt once per stream and device: a few probe launches; a
-            // stream seen before costs a look-up)
-            if (stream_ != classed_for_) {
-                hipStream_t sd[3] = {nullptr, nullptr, nullptr};
-                const int rc = classified_side_streams(device_, stream_, (int)(lease_->uses & 1), sd);
-                if (rc < 0) return rc;
-                for (int k = 0; k < 3; k++) classed_streams_[k] = rc == 0 ? sd[k] : nullptr;   // (rc 1: keep the lease's streams, rounds 1-3's choice)
-                classed_for_ = stream_;
-            }
-            // (each replaces a stream of the lease that this batch uses)
-            if (back_stream_ && classed_streams_[0]) back_stream_ = classed_streams_[0];
-            if (full_stream_ && classed_streams_[1]) full_stream_ = classed_streams_[1];
-            if (first_stream_ && classed_streams_[2]) first_stream_ = classed_streams_[2];
-            if (side_lattice_ && classed_streams_[2]) lattice_stream_ = classed_streams_[2];
+            // stream seen before costs a look-up).  env AMBI_STREAM_CLASSES=0: by creation order, without probes
+            const char* e = ambi_env("AMBI_STREAM_CLASSES");
+            if (int rc = side_streams(*lease_->ctx, stream_, (int)(lease_->uses & 1), e ? atoi(e) != 0 : true, &side_)) return rc;
+            side_for_ = stream_;
         }
         t_run_ = std::chrono::steady_clock::now();
         flushed_ = upload_pending_;
@@ -1873,8 +1868,8 @@ class HipBackend : public Backend {
         all_done_ = false;
         const int U = A_.n_units;
         lazy_ = (flags & FLAG_LAZY_ORDERS) != 0;
-        overlap_back_ = want_overlap_ && back_stream_ != nullptr;
-        A_.direct_full_on = (overlap_back_ && direct_n_ > 0 && full_stream_ != nullptr) ? 1 : 0;
+        overlap_back_ = want_overlap_;
+        A_.direct_full_on = (overlap_back_ && direct_n_ > 0) ? 1 : 0;
         express_ = U <= express_units_ && lds_express_ <= kLdsMaxDynamic && dh_express_left_ != nullptr && n_wide_ == 0;
         // no copy commands around the kernels: they zero their counters and store the two words the host reads into pinned
         // memory themselves (see BatchArgs::zero_pending)

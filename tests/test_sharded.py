@@ -1,6 +1,8 @@
 """ambi_batch_run_sharded: the C-level multi-device driver (one host thread per device, units dealt round-robin, results merged
 on the host).  N shares on ONE device (the way to exercise the N > 1 path on a one-GPU box) and on the host
 simulation; the merged results must equal a single-device run and the oracle, for every getter."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -83,3 +85,28 @@ def test_sharded_n_shares_on_one_gpu(hip_lib, oracle, workdir, shares):
 def test_sharded_all_visible_devices_and_all_mode(hip_lib, oracle, workdir):
     _check(hip_lib, oracle, workdir, "shgv", None, count=9)
     _check(hip_lib, oracle, workdir, "shga", [0, 0, 0], count=7, flags=api.FLAG_ALL)
+
+
+@pytest.mark.gpu
+def test_two_devices_in_one_process(hip_lib, oracle, workdir):
+    """Every device probes its streams with its own events: shares over devices [0, 1] and [1, 0], a batch on device 1 after one on
+    device 0 (ambi_set_device), and the stream probe on device 1."""
+    n = ctypes.c_int(0)
+    hip_lib.ambi_device_count(ctypes.byref(n))
+    if n.value < 2:
+        pytest.skip("needs two visible devices")
+    _check(hip_lib, oracle, workdir, "sh01_", [0, 1])
+    _check(hip_lib, oracle, workdir, "sh10_", [1, 0])
+    gs, samples, b0, b1 = _batch(hip_lib, workdir, "shd_", 5)
+    try:
+        for dev, b in ((0, b0), (1, b1)):
+            assert hip_lib.ambi_set_device(dev) == 0
+            b.upload(); b.run(0); b.download()
+        for u in range(len(gs)):
+            assert b0.unit_result(u) == b1.unit_result(u), u
+            assert b1.unit_path(u, 1).tolist() == b0.unit_path(u, 1).tolist() == oracle.run_bfb(*samples[u])["chr"][0]["path_indel"], u
+        us = ctypes.c_float(0)
+        assert hip_lib.ambi_debug_stream_probe(None, None, ctypes.byref(us)) == 0 and us.value > 0
+    finally:
+        hip_lib.ambi_set_device(0)
+        b0.close(); b1.close()
