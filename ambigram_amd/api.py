@@ -80,6 +80,7 @@ def _declare(L):
         "ambi_batch_size": (C.c_int, [vp, pi32]),
         "ambi_batch_configure": (C.c_int, [vp, i64, i32, i32, i32]),
         "ambi_batch_debug_inject_validity": (C.c_int, [vp, i32, pi8, i64]),
+        "ambi_batch_debug_unit_order": (C.c_int, [vp, i32, pu8, i32]),
         "ambi_batch_upload": (C.c_int, [vp]),
         "ambi_batch_run": (C.c_int, [vp, u32, vp]),
         "ambi_batch_wait": (C.c_int, [vp]),
@@ -396,6 +397,14 @@ class Batch:
         (forward-seed orientation first); 1 valid, 0 invalid, negative status, 127 = evaluate as usual."""
         v, vp = _arr(verdicts, np.int8)
         self._ck(self.lib.ambi_batch_debug_inject_validity(self.h, unit, vp, len(v)), "debug_inject_validity")
+
+    def debug_unit_order(self, unit):
+        """Diagnostics (include/ambigram_hip.h): the order a unit with injected verdicts was resolved with, as the engine
+        decoded it (uint8 node numbers; empty when no stage stored a row in the last run)."""
+        out = np.zeros(256, np.uint8)
+        n = self.lib.ambi_batch_debug_unit_order(self.h, unit, out.ctypes.data_as(_P(C.c_uint8)), len(out))
+        self._ck(min(n, 0), "debug_unit_order")
+        return out[:n]
 
     def upload(self):
         self._ck(self.lib.ambi_batch_upload(self.h), "upload")

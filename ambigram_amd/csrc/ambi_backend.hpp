@@ -59,6 +59,8 @@ class Backend {
     virtual int runs_to_host(int which, int slot, int with_headers, void* stream) { (void)which; (void)slot; (void)with_headers; (void)stream; return ST_ERR_BAD_INPUT; }
     virtual int runs_wait(int slot, RunsView* out) { (void)slot; (void)out; return ST_ERR_BAD_INPUT; }
     virtual int copy_orders(int unit, int64_t first, int64_t count, uint8_t* out) = 0;
+    // diagnostics: the kDebugOrderBytes of BatchArgs::debug_order of a unit with injected verdicts (all zero: no stage stored a row)
+    virtual int copy_debug_order(int unit, uint8_t* out) { (void)unit; (void)out; return ST_ERR_BAD_INPUT; }
     virtual int copy_dag(int unit, Dag* out) = 0;
     // the same for a wide unit (64..127 nodes): node records [K][3] each, successor sets as [K][2] 64-bit words
     virtual int copy_dag_wide(int unit, int32_t* pat, int32_t* loop, uint64_t* succ2) { (void)unit; (void)pat; (void)loop; (void)succ2; return ST_ERR_BAD_INPUT; }

@@ -167,8 +167,12 @@ struct BatchArgs {
     // diagnostics hook (ambi_batch_debug_inject_validity): verdicts that REPLACE the outcome of evaluating an order, so that
     // the control flow around the evaluation (scan budget, parallel search, minimum index, orientation flip, --all) can be
     // driven to places no known input reaches.  nullptr in every ordinary run.
-    const int8_t* inject_valid;  // pool: per unit 2*R verdicts, first orientation "forward seed" then "reversed seed"; 127 = evaluate
-    const int64_t* inject_off;   // [U][2] {offset into the pool or -1, number of verdicts}
+    int8_t* inject_valid;        // pool: per unit 2*R verdicts, first orientation "forward seed" then "reversed seed"; 127 = evaluate;
+                                 // kInjectRecord + {0, 1}: that verdict, and --all leaves the decoded row of this order of a wide unit in the unit's slot.
+                                 // In FRONT of the verdicts, one slot of kDebugOrderBytes per unit with verdicts: the order the unit was resolved with,
+                                 // as the stage that published it decoded it (K node numbers, 0xFF behind them; zeroed by every run) -- the only
+                                 // bytes of the pool a kernel writes
+    const int64_t* inject_off;   // [U][kInjectStride] {offset of the verdicts in the pool or -1, number of verdicts, index of the slot or -1}
     // --all (ambi_all_kernel): validity bitmaps of both passes, one bit per order
     uint64_t* all_bits;          // pool of 64-order words
     const int64_t* all_off;      // [U+1] first word of every unit's pass-0 map; its pass-1 map follows (ceil(R/64) words each)
@@ -207,6 +211,7 @@ struct BatchArgs {
     int32_t* run_len;
     const int64_t* run_slot;
 };
+constexpr int kInjectStride = 3, kInjectRecord = 64, kDebugOrderBytes = 256;
 
 // Mailbox slot of one unit: [UnitOut, 128 bytes] [path: path_cap cells] [path after indelBFB: path_cap cells] [output junctions:
 // out_cap records], each part on a 16-byte boundary; only the used prefix of every part is written.

@@ -388,6 +388,18 @@ int ambi_batch_debug_inject_validity(ambi_batch_t* b, int32_t unit, const int8_t
     b->hb.inject_unit[unit].assign(verdicts, verdicts + count);
     return 0;
 }
+int ambi_batch_debug_unit_order(ambi_batch_t* b, int32_t unit, uint8_t* out, int32_t cap) {
+    if (!b || !(b->uploaded || !b->shards.empty()) || !out || cap < 0 || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    int local = unit;
+    Backend* be = b->owner(unit, &local);
+    uint8_t slot[kDebugOrderBytes];
+    if (int rc = be->copy_debug_order(local, slot)) return rc;
+    if (slot[kDebugOrderBytes - 1] != 0xFF) return 0;   // (a stored row has at most 255 nodes and 0xFF behind them; the slot is zeroed by every run)
+    int K = 0;
+    while (slot[K] != 0xFF) K++;
+    for (int d = 0; d < K && d < cap; d++) out[d] = slot[d];
+    return K;
+}
 int ambi_batch_upload(ambi_batch_t* b) {
     if (!b) return AMBI_ERR_ARG;
     if (b->hb.units.empty() || !b->shards.empty()) return AMBI_ERR_STATE;

@@ -718,6 +718,7 @@ __global__ __launch_bounds__(64) void ambi_order_paths_kernel(BatchArgs A, int u
     load_first_work(g, A, u, W);
     int L = 0;
     const int v = eval_indexed(g, A, u, W, order_idx[j], forward != 0, &L);
+    if (gridDim.x == 1) debug_store_order(g, A, u, W.ord, unit_out(A.results, u)->K);   // (diagnostics: a request for ONE path also tells which row it was made from)
     int P = -1;
     if (v == 1) P = expand_bkp(g, W.bkp, L, (cell_t*)nullptr, (int)(stride < U.path_cap ? stride : U.path_cap), offs, cells + (int64_t)j * stride, U.seg_base);
     if (g.tid() == 0) lengths[j] = P;
@@ -1362,7 +1363,7 @@ class HipBackend : public Backend {
         c.take(&d_units_, U); c.take(&d_seg_cn_, H.seg_cn.size()); c.take(&d_junc_cn_, H.junc_cn.size()); c.take(&d_junc_ends_, H.junc_ends.size());
         c.take(&d_elems_, H.elems.size()); c.take(&d_scratch_off_, U); c.take(&d_direct_list_, direct_list.size()); c.take(&d_mail_off_, U);
         c.take(&d_wide_index_, U); c.take(&d_wide_units_, (size_t)H.n_wide);
-        c.take(&d_inject_, H.inject.size()); c.take(&d_inject_off_, H.inject.empty() ? 0 : 2 * U);
+        c.take(&d_inject_, H.inject.size()); c.take(&d_inject_off_, H.inject.empty() ? 0 : kInjectStride * U);
         c.take(&d_run_slot_, U + 1);
         in_bytes_ = c.off;
         zero_off_ = c.off;
@@ -1561,7 +1562,7 @@ class HipBackend : public Backend {
             for (size_t u2 = 0; u2 < U; u2++) if (H.wide_index[u2] >= 0) wu.push_back((int32_t)u2);
             if (!wu.empty()) put(d_wide_units_, wu.data(), wu.size() * sizeof(int32_t));
         }
-        if (!H.inject.empty()) { put(d_inject_, H.inject.data(), H.inject.size()); put(d_inject_off_, H.inject_off.data(), 2 * U * sizeof(int64_t)); }
+        if (!H.inject.empty()) { put(d_inject_, H.inject.data(), H.inject.size()); put(d_inject_off_, H.inject_off.data(), kInjectStride * U * sizeof(int64_t)); }
         if (pinned) upload_pending_ = true;
         else {
             HIP_CK(hipMemcpy(L->d_block, img, (size_t)in_bytes_, hipMemcpyHostToDevice));
@@ -1865,6 +1866,7 @@ class HipBackend : public Backend {
         runs_parity_ = run_seq_ & 1;
         mail_valid_ = false;
         bind(flags);
+        if (d_inject_) HIP_CK(hipMemsetAsync(d_inject_, 0, (size_t)hb().n_armed * kDebugOrderBytes, stream_));   // (diagnostics: the slots in front of the verdicts hold a row stored by THIS run)
         all_done_ = false;
         const int U = A_.n_units;
         lazy_ = (flags & FLAG_LAZY_ORDERS) != 0;
@@ -2379,6 +2381,15 @@ class HipBackend : public Backend {
         HIP_CK(hipMemcpy(tmp.data(), d_arena_ + h.order_off + first * stride, tmp.size(), hipMemcpyDeviceToHost));
         // (Lehmer codes up to 63 nodes, a byte per node above: row_unpack decodes either)
         for (int64_t r = 0; r < count; r++) row_unpack(tmp.data() + r * stride, h.K, out + r * h.K);
+        return 0;
+    }
+    int copy_debug_order(int unit, uint8_t* out) override {
+        DeviceGuard dg_(device_);
+        if (int rc = wait()) return rc;
+        const HostBatch& H = hb();
+        const int64_t slot = (H.inject.empty() || !d_inject_) ? -1 : H.inject_off[kInjectStride * (size_t)unit + 2];
+        if (slot < 0) return ST_ERR_BAD_INPUT;
+        HIP_CK(hipMemcpy(out, d_inject_ + slot * kDebugOrderBytes, kDebugOrderBytes, hipMemcpyDeviceToHost));
         return 0;
     }
     int copy_dag(int unit, Dag* out) override {

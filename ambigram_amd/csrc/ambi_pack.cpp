@@ -177,16 +177,20 @@ void HostBatch::finalize() {
     for (size_t u = 0; u < units.size(); u++) if (units[u].n_elem > kMaxNodes) wide_index[u] = n_wide++;
     ideal_slots = islots;
     scratch_ints = sints;
-    inject.clear(); inject_off.clear();
+    inject.clear(); inject_off.clear(); n_armed = 0;
     bool any = false;
     for (auto& v : inject_unit) any = any || !v.empty();
     if (any) {
-        inject_off.assign(2 * units.size(), -1);
+        for (auto& v : inject_unit) n_armed += !v.empty();
+        inject.assign((size_t)n_armed * kDebugOrderBytes, 0);
+        int slot = 0;
+        inject_off.assign(kInjectStride * units.size(), -1);
         for (size_t u = 0; u < units.size(); u++) {
-            inject_off[2 * u + 1] = 0;
+            inject_off[kInjectStride * u + 1] = 0;
             if (u < inject_unit.size() && !inject_unit[u].empty()) {
-                inject_off[2 * u] = (int64_t)inject.size();
-                inject_off[2 * u + 1] = (int64_t)inject_unit[u].size();
+                inject_off[kInjectStride * u] = (int64_t)inject.size();
+                inject_off[kInjectStride * u + 1] = (int64_t)inject_unit[u].size();
+                inject_off[kInjectStride * u + 2] = slot++;
                 inject.insert(inject.end(), inject_unit[u].begin(), inject_unit[u].end());
             }
         }

@@ -30,8 +30,9 @@ struct HostBatch {
     std::vector<int32_t> wide_index;        // [U] index among the wide units or -1; filled by finalize()
     bool any_sv = false;                    // some unit has a junction indelBFB would look at (neither adjacency nor fold-back): the full finish stage may be needed
     // diagnostics hook (ambi_batch_debug_inject_validity): verdict overrides per unit, see BatchArgs::inject_valid
-    std::vector<int8_t> inject;
-    std::vector<int64_t> inject_off;        // [U][2] {offset or -1, count}; filled by finalize()
+    std::vector<int8_t> inject;             // [n_armed][kDebugOrderBytes] slots (zero), then the verdicts
+    std::vector<int64_t> inject_off;        // [U][kInjectStride] {offset of the verdicts in `inject` or -1, count, slot or -1}; filled by finalize()
+    int n_armed = 0;                        // units with injected verdicts (= slots at the front of `inject`)
     std::vector<std::vector<int8_t>> inject_unit;
 
     // Raw unit: local ids 1..n_seg, junctions already restricted to the unit.  Returns unit index or negative Status.

@@ -575,11 +575,29 @@ AMBI_HD void load_first_work(const G& g, const BatchArgs& A, int u, const FirstW
 // diagnostics hook (BatchArgs::inject_valid): the verdict of order nidx in the given orientation, or `v` itself
 AMBI_HD int injected_verdict(const BatchArgs& A, int u, int64_t R, int64_t nidx, bool forwardDir, int v) {
     if (!A.inject_valid) return v;
-    const int64_t off = A.inject_off[2 * (int64_t)u], len = A.inject_off[2 * (int64_t)u + 1];
+    const int64_t off = A.inject_off[kInjectStride * (int64_t)u], len = A.inject_off[kInjectStride * (int64_t)u + 1];
     const int64_t at = (forwardDir ? 0 : R) + nidx;
     if (off < 0 || at >= len) return v;
     const int x = A.inject_valid[off + at];
-    return x == 127 ? v : x;
+    return x == 127 ? v : (x >= kInjectRecord ? x - kInjectRecord : x);
+}
+// ... and whether that verdict asks --all for the decoded row of its order (kInjectRecord)
+AMBI_HD bool inject_records(const BatchArgs& A, int u, int64_t R, int64_t nidx, bool forwardDir) {
+    if (!A.inject_valid) return false;
+    const int64_t off = A.inject_off[kInjectStride * (int64_t)u], len = A.inject_off[kInjectStride * (int64_t)u + 1];
+    const int64_t at = (forwardDir ? 0 : R) + nidx;
+    if (off < 0 || at >= len) return false;
+    const int x = A.inject_valid[off + at];
+    return x != 127 && x >= kInjectRecord;
+}
+// diagnostics (the slots in front of BatchArgs::inject_valid): the order a stage has just evaluated for a unit with verdicts, as it decoded it
+template <class G>
+AMBI_HD void debug_store_order(const G& g, const BatchArgs& A, int u, const uint8_t* ord, int K) {
+    if (!A.inject_valid) return;
+    const int64_t slot = A.inject_off[kInjectStride * (int64_t)u + 2];
+    if (slot < 0) return;
+    uint8_t* dst = reinterpret_cast<uint8_t*>(A.inject_valid) + slot * kDebugOrderBytes;
+    for (int d = g.tid(); d < kDebugOrderBytes; d += g.size()) dst[d] = d < K ? ord[d] : (uint8_t)0xFF;
 }
 
 template <class G>
@@ -634,6 +652,7 @@ AMBI_HD void stage_first(const G& g, const BatchArgs& A, int u, uint8_t* work) {
     if (status == ST_OK) {
         cell_t* dst = reinterpret_cast<cell_t*>(res + Lay.bkp);
         for (int i = g.tid(); i < L; i += g.size()) dst[i] = W.bkp[i];
+        debug_store_order(g, A, u, W.ord, K);   // (W.ord: the order of the hit)
     }
     if (g.tid() == 0) {
         out->status = status;
@@ -723,6 +742,7 @@ AMBI_HD void stage_resolve(const G& g, const BatchArgs& A, int u, uint8_t* work,
     load_first_work(g, A, u, W);
     int L = 0;
     const int v = eval_indexed(g, A, u, W, f, forward, &L);   // materialise the winner's breakpoints
+    debug_store_order(g, A, u, W.ord, out->K);
     const UnitLayout Lay = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
     cell_t* dst = reinterpret_cast<cell_t*>(A.results + U.res_off + Lay.bkp);
     for (int i = g.tid(); i < L; i += g.size()) dst[i] = W.bkp[i];
@@ -771,6 +791,7 @@ AMBI_HD void stage_all_chunk(const G& g, const BatchArgs& A, int u, const FirstW
             if (g.tid() == 0) row_unpack(trow, K, W.ord);
             g.sync();
             ord = W.ord;
+            if (inject_records(A, u, R, first + i, forward)) debug_store_order(g, A, u, W.ord, K);
         }
         int v = eval_order_w(g, W, ord, forward, inv, W.bkp, U.bkp_cap, &L);
         v = injected_verdict(A, u, R, first + i, forward, v);
@@ -1447,7 +1468,7 @@ AMBI_HD bool stage_express(const GW& gw, const GB& gb, int role, const BatchArgs
     AMBI_MARK(A, gb, u, 3);
     if (role == 1 || role < 0) {
         int v = placed < 0 ? placed : eval_finish(gw, placed, K, W.F.bkp, L, InvMap{W.F.inv_src, W.F.inv_tgt}, true);
-        if (A.inject_valid && A.inject_off[2 * (int64_t)u] >= 0) v = 0;   // injected verdicts (diagnostics) are indexed with R: the scan kernel applies them
+        if (A.inject_valid && A.inject_off[kInjectStride * (int64_t)u] >= 0) v = 0;   // injected verdicts (diagnostics) are indexed with R: the scan kernel applies them
         if (gw.tid() == 0) fl[5] = v;
     }
     gb.sync();

@@ -169,6 +169,15 @@ int ambi_batch_configure(ambi_batch_t* b, int64_t order_arena_bytes, int32_t ide
  * usual.  Call after the unit was added and before ambi_batch_upload; the breakpoints of a "valid" order are those the
  * real assembly leaves. */
 int ambi_batch_debug_inject_validity(ambi_batch_t* b, int32_t unit, const int8_t* verdicts, int64_t count);
+/* The other half of that hook: which ORDER the engine made the result of such a unit from.  After a run (waited for), the
+ * node numbers of the order whose evaluation the unit's header reports (first_valid / first_forward), exactly as the stage that
+ * published it decoded them from its source -- the first rows in group memory (scan inside the budget) or the unit's row of
+ * the order table in device memory (parallel search) -- so that a test can tell row f from any other valid row.  A verdict
+ * of 64 + {0, 1} means that verdict and, under AMBI_FLAG_ALL on a unit with more than 63 nodes (the only --all form that
+ * reads the table), "leave the decoded row of THIS order here" (mark one order per run); ambi_batch_all_paths with count == 1
+ * leaves the row it made that path from.  Returns the number of nodes
+ * written to out[0..cap) (0: no stage stored a row in the last run), AMBI_ERR_ARG for a unit without injected verdicts. */
+int ambi_batch_debug_unit_order(ambi_batch_t* b, int32_t unit, uint8_t* out, int32_t cap);
 
 /* Packs the units and hands the inputs to the current device (they stay resident in HBM across runs).  Streams, events,
  * pinned words and device blocks come from a per-device pool with process lifetime (created on first use, reused by every

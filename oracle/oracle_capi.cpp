@@ -3,6 +3,7 @@
 // Results are returned as one JSON document so the Python side needs no struct mirroring.
 #include <chrono>
 #include <cstring>
+#include <map>
 #include <sstream>
 #include <string>
 
@@ -53,7 +54,7 @@ void oracle_free(char* p) { free(p); }
 
 // Runs the whole `--op bfb` flow (localhap.cpp:49-388) with the cbc step replaced by the given .sol files
 // (comma separated, one per chromosome that reaches the ILP).  flags: bit0 reversed, bit1 all, bit2 junc_info,
-// bit3 keep orders in the dump.  Returns a malloc'ed JSON string (free with oracle_free).
+// bit3 keep orders in the dump, bit4 --all paths as distinct paths + an index per valid order.  Returns a malloc'ed JSON string (free with oracle_free).
 char* oracle_run_bfb(const char* lh, const char* juncs, const char* sols, int flags, long long maxOrders, double* seconds) {
     RunOptions opt;
     opt.lh = lh; opt.juncs = juncs ? juncs : "";
@@ -100,7 +101,21 @@ char* oracle_run_bfb(const char* lh, const char* juncs, const char* sols, int fl
           << ",\"ub_valid\":" << (s.bfb.undefinedOnValid ? "true" : "false");
         o << ",\"bkp\":"; jarr(o, s.bfb.bkpFirst);
         o << ",\"path\":"; jarr(o, s.bfb.path);
+        if (flags & 16) {   // every distinct path once + one index per valid order: the same information in a dump that stays small when thousands of orders give one path
+            std::map<std::vector<int>, int> seen;
+            std::vector<const std::vector<int>*> uniq;
+            std::vector<int> ref;
+            for (const auto& p : s.bfb.allPaths) {
+                auto it = seen.find(p);
+                if (it == seen.end()) { it = seen.emplace(p, (int)uniq.size()).first; uniq.push_back(&it->first); }
+                ref.push_back(it->second);
+            }
+            o << ",\"all_paths\":[],\"all_paths_unique\":[";
+            for (size_t i = 0; i < uniq.size(); i++) { if (i) o << ','; jarr(o, *uniq[i]); }
+            o << "],\"all_paths_ref\":"; jarr(o, ref);
+        } else {
         o << ",\"all_paths\":"; jarr2(o, s.bfb.allPaths);
+        }
         o << ",\"all_eval_idx\":"; jarr(o, s.bfb.allEvalIdx);
         o << ",\"indel_printed\":" << (s.indelPrinted ? "true" : "false");
         o << ",\"path_indel\":"; jarr(o, s.pathAfterIndel);

@@ -15,6 +15,7 @@ FLAG_REVERSED = 1
 FLAG_ALL = 2
 FLAG_JUNC_INFO = 4
 FLAG_KEEP_ORDERS = 8
+FLAG_ALL_DEDUP = 16
 
 
 def build(ref=True):
@@ -65,15 +66,20 @@ def lib_O0():
     return _LIB_O0
 
 
-def run_bfb(lh, sols, juncs="", reversed_=False, all_=False, junc_info=False, keep_orders=False, max_orders=0, O0=False):
-    """Whole `--op bfb` flow on the CPU oracle. `sols`: list of .sol paths, one per chromosome reaching the ILP."""
+def run_bfb(lh, sols, juncs="", reversed_=False, all_=False, junc_info=False, keep_orders=False, max_orders=0, O0=False, dedup_all=False):
+    """Whole `--op bfb` flow on the CPU oracle. `sols`: list of .sol paths, one per chromosome reaching the ILP.
+    `dedup_all`: the --all paths cross the binding as distinct paths + one index per valid order (units with tens of thousands of
+    orders that all give the same path); `all_paths` is the same list of lists either way (equal entries share one list)."""
     flags = (FLAG_REVERSED if reversed_ else 0) | (FLAG_ALL if all_ else 0) | \
-            (FLAG_JUNC_INFO if junc_info else 0) | (FLAG_KEEP_ORDERS if keep_orders else 0)
+            (FLAG_JUNC_INFO if junc_info else 0) | (FLAG_KEEP_ORDERS if keep_orders else 0) | (FLAG_ALL_DEDUP if dedup_all else 0)
     sec = ctypes.c_double(0)
     p = (lib_O0() if O0 else lib()).oracle_run_bfb(lh.encode(), juncs.encode(), ",".join(sols).encode(), flags, max_orders,
                                                      ctypes.byref(sec))
     out = _take(p)
     out["seconds"] = sec.value
+    if dedup_all:
+        for c in out["chr"]:
+            c["all_paths"] = [c["all_paths_unique"][i] for i in c["all_paths_ref"]]
     return out
 
 

@@ -210,6 +210,7 @@ class HostSimBackend : public Backend {
         HostGroup g;
         bind(flags);
         n_pending_ = 0;
+        std::fill(hb_.inject.begin(), hb_.inject.begin() + (size_t)hb_.n_armed * kDebugOrderBytes, 0);   // the slots of the decoded orders: this run's only
         const int Un = (int)units_.size();
         // small batches: the express stage (whole reconstruction of units whose first order assembles) in front, the lattice
         // stage behind it, as the HIP backend launches them (env AMBI_EXPRESS_UNITS, default 32; 0 = never)
@@ -380,6 +381,7 @@ class HostSimBackend : public Backend {
         for (int64_t j = 0; j < count; j++) {
             int L = 0;
             const int ok = eval_indexed(g, A_, unit, W, v[first + j], fwd, &L);
+            if (count == 1) debug_store_order(g, A_, unit, W.ord, unit_out(A_.results, unit)->K);   // as ambi_order_paths_kernel
             lengths[j] = ok == 1 ? expand_bkp(g, W.bkp, L, (cell_t*)nullptr, (int)(stride < U.path_cap ? stride : U.path_cap), offs.data(),
                                               cells + j * stride, U.seg_base)
                                  : -1;
@@ -435,6 +437,12 @@ class HostSimBackend : public Backend {
         const int stride = row_stride(h->K);
         for (int64_t r = 0; r < count; r++)
             for (int d = 0; d < h->K; d++) out[r * h->K + d] = (uint8_t)row_node(arena_.data() + h->order_off + (first + r) * stride, h->K, d);
+        return 0;
+    }
+    int copy_debug_order(int unit, uint8_t* out) override {
+        const int64_t slot = hb_.inject.empty() ? -1 : hb_.inject_off[kInjectStride * (size_t)unit + 2];
+        if (slot < 0) return ST_ERR_BAD_INPUT;
+        memcpy(out, hb_.inject.data() + slot * kDebugOrderBytes, kDebugOrderBytes);
         return 0;
     }
     int copy_dag(int unit, Dag* out) override { *out = dags_[unit]; return 0; }

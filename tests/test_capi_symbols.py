@@ -25,6 +25,7 @@ def test_library_exports_declared_symbols(built):
     lib = ctypes.CDLL(built)
     names = _declared()
     assert len(names) >= 35
+    assert "ambi_batch_debug_inject_validity" in names and "ambi_batch_debug_unit_order" in names     # the diagnostics hook and its read-back
     for n in names:
         assert hasattr(lib, n), "missing export " + n
 
