@@ -14,6 +14,8 @@
 //   ambi_search/resolve_kernel    1 wave  / chunk of orders (only for units whose scan budget ran out)
 //   ambi_finish_kernel            1 block / unit   bkp -> path (LDS int16), indelBFB, output junctions
 //   ambi_pack_*                   optional end-of-batch packing of the paths for an RCCL gather
+// Every kernel is a wrapper around the stage functions of ambi_stages.hpp, the four table kernels (blocks_build,
+// enumerate_blocks, enumerate, enumerate_wide) included: their logic is under that file's stage_enumerate banner.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -332,75 +334,28 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
     }
 }
 
-// One wavefront per work block of 64*T consecutive ranks of one unit.  Lane l unranks rank base + l*T from the
-// automaton and walks T lexicographic successors; rows leave the registers as 16-byte stores (4 rows per group), so
-// every byte of the table is written exactly once and nothing is staged through an LDS tile.
-// LDS per wave: [enum_stack_lds] per-lane DFS stacks (depth-major) | [enum_auto_lds] compact copy of the unit's
-// automaton (avail masks, child bases, child links) when it fits, else the automaton is read through L2.
+// The four table kernels: group set-up, the grid-stride loop over the work blocks and the filters in front; what a workgroup or
+// wave does with a work block is in ambi_stages.hpp (stage_enumerate), which the host simulation runs as well.
+// General path (enumerate_general_block): one wavefront per 64*T consecutive ranks of one unit, rows leave the registers as 16-byte stores.
+// LDS per wave: [enum_stack_lds] per-lane DFS stacks | [enum_auto_lds] compact copy of the unit's automaton when it fits.
 template <int CLS>
 __global__ __launch_bounds__(256) void ambi_enumerate_kernel(BatchArgs A) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    const int wave_bytes = A.enum_stack_lds + A.enum_auto_lds;
-    uint8_t* stacks = ambi_lds + (size_t)wave * wave_bytes;
-    uint8_t* amem = stacks + A.enum_stack_lds;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint8_t* stacks = ambi_lds + (size_t)wave * (A.enum_stack_lds + A.enum_auto_lds);
     WaveGroup g;
     const int64_t total = A.blk_off[A.n_units];
-    int staged_unit = -1;
-    bool in_lds = false;
-    (void)wpb;
-    // general path: only units whose block tables did not fit (flagged by ambi_enumerate_blocks_kernel)
+    StagedAuto S;
+    // only units whose block tables did not fit (flagged by ambi_blocks_build_kernel / ambi_enumerate_blocks_kernel)
     for (int64_t b = (int64_t)blockIdx.x; b < total; b += (int64_t)gridDim.x) {
-        int lo = 0, hi = A.n_units;
-        if (b < A.n_units && A.blk_off[b] == b && A.blk_off[b + 1] == b + 1) lo = (int)b;   // one work block per unit so far: two independent reads
-        else while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (A.blk_off[mid] <= b) lo = mid; else hi = mid; }
-        const int u = A.unit_base + lo;
-        const UnitOut* out = unit_out(A.results, u);
-        const int K = out->K, T = A.rows_per_lane[u];
-        if (enum_class_of(K) != CLS) continue;   // rows of this width belong to another instantiation
+        const int lo = unit_of_work_block(A, b), u = A.unit_base + lo;
+        if (enum_class_of(unit_out(A.results, u)->K) != CLS) continue;   // rows of this width belong to another instantiation
         if (!A.unit_fallback[u]) continue;
-        const int64_t R = out->num_orders;
-        const int64_t base_rank = (b - A.blk_off[lo]) * 256ll * T + (int64_t)wave * 64 * T;
-        const IdealTable tbl = unit_ideal_table(A, u);
-        const AutoView V = auto_view(tbl);
-        const int nI = V.nI, nC = tbl.counter[1];
-        const bool wide = K > 32;
-        const int msz = wide ? 8 : 4;
-        uint8_t* av_l = amem;
-        uint32_t* rec_l = reinterpret_cast<uint32_t*>(amem + (size_t)nI * msz);
-        uint16_t* cb_l = reinterpret_cast<uint16_t*>(rec_l + nI);
-        uint16_t* ch_l = cb_l + nI;
-        if (u != staged_unit) {
-            g.sync();
-            const int64_t need = (int64_t)nI * (msz + 6) + 2ll * nC + 16;
-            in_lds = need <= A.enum_auto_lds && nC < 65536;
-            if (in_lds) {
-                for (int i = lane; i < nI; i += 64) {
-                    const uint64_t av = V.avail[i];
-                    if (wide) reinterpret_cast<uint64_t*>(av_l)[i] = av;
-                    else reinterpret_cast<uint32_t*>(av_l)[i] = (uint32_t)av;
-                    cb_l[i] = (uint16_t)V.cbase[i];
-                    rec_l[i] = av ? make_rec(av, V.child[V.cbase[i]]) : 0u;
-                }
-                for (int i = lane; i < nC; i += 64) ch_l[i] = V.child[i];
-            }
-            staged_unit = u;
-            g.sync();
-        }
-        uint8_t* rows = A.order_arena + out->order_off;   // 16-byte aligned; lane ranges start at multiples of 4 rows
-        const int64_t first = base_rank + (int64_t)lane * T;
-        if (in_lds) {
-            LdsAuto<uint32_t> a32{reinterpret_cast<const uint32_t*>(av_l), rec_l, cb_l, ch_l};
-            LdsAuto<uint64_t> a64{reinterpret_cast<const uint64_t*>(av_l), rec_l, cb_l, ch_l};
-            enumerate_lane_dispatch<CLS>(a32, a64, V, K, R, first, T, stacks, lane, 64, rows);
-        } else {
-            GlobalAuto ga{V};
-            enumerate_lane_dispatch<CLS>(ga, ga, V, K, R, first, T, stacks, lane, 64, rows);
-        }
+        enumerate_general_block<CLS>(g, A, u, b - A.blk_off[lo], S, stacks, stacks + A.enum_stack_lds, wave, lane);
     }
 }
 
-// Builds the block-emission image of every unit whose table is written by MORE THAN ONE workgroup and parks it in HBM
-// (a unit with a single work block gets its image built in LDS by the enumerate workgroup itself, below).
+// Builds the block-emission image (build_unit_image) of every unit whose table is written by MORE THAN ONE workgroup and parks
+// it in HBM (a unit with a single work block gets its image built in LDS by the enumerate workgroup itself, stage_unit_image).
 __global__ __launch_bounds__(256) void ambi_blocks_build_kernel(BatchArgs A) {
     __shared__ int scratch[40];
     BlockGroup g(scratch);
@@ -414,66 +369,44 @@ __global__ __launch_bounds__(256) void ambi_blocks_build_kernel(BatchArgs A) {
         return;
     }
     const IdealTable tbl = unit_ideal_table(A, u);
-    const int K = out->K;
     BlockImageHeader H;
-    // the automaton copy sits in LDS, the image is assembled word by word straight in its HBM slot
+    // the build tables sit in LDS, the image is assembled word by word straight in its HBM slot; a directory-free image leaves
+    // room in front for the tables, which the walk reads and which therefore travel with the suffix rows
     uint8_t* slot = A.block_img + (int64_t)u * A.block_lds;
-    bool fits = build_block_image(g, tbl, K, row_stride(K) / 4, out->num_orders, A.block_max, ambi_lds, A.block_scratch_lds, slot, A.block_lds, H,
-                                  A.stage_clk ? A.stage_clk + (int64_t)u * kStageSlots : nullptr);
-    if (!fits && A.block_dfs) {
-        // one directory entry per block does not fit (many rows): the directory-free image -- [build tables][suffix rows],
-        // walked block by block at emission (emit_blocks_dfs_wave) -- with the largest block size whose suffix rows fit
-        BuildTables dummy;
-        const int64_t scr = carve_build_tables(ambi_lds, tbl.counter[0], tbl.counter[1], dummy);
-        const int64_t budget = (int64_t)A.block_lds - kDfsStateBytes - scr;
-        for (int bm = A.block_max; bm >= 8 && !fits && budget > 0 && scr <= A.block_scratch_lds; bm >>= 1) {
-            __syncthreads();
-            fits = build_block_image(g, tbl, K, row_stride(K) / 4, out->num_orders, bm, ambi_lds, A.block_scratch_lds, slot + scr, budget, H, nullptr, false);
-        }
-        if (fits) {   // the tables the walk reads travel with the suffix rows
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(ambi_lds);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(slot);
-            for (int64_t i = threadIdx.x; i < scr / 4; i += blockDim.x) dst[i] = src[i];
-            H.pad = (int32_t)scr;
-            H.image_bytes += (int32_t)scr;
-        }
+    BuildTables dummy;
+    const int64_t scr = carve_build_tables(ambi_lds, tbl.counter[0], tbl.counter[1], dummy);
+    const int kind = build_unit_image(g, tbl, out->K, out->num_orders, A.block_max, A.block_dfs, ambi_lds, A.block_scratch_lds, slot, A.block_lds,
+                                      scr, (int64_t)A.block_lds - kDfsStateBytes - scr, H, A.stage_clk ? A.stage_clk + (int64_t)u * kStageSlots : nullptr);
+    if (kind == 2) {
+        copy_words(g, reinterpret_cast<uint32_t*>(slot), reinterpret_cast<const uint32_t*>(ambi_lds), scr / 4);
+        H.pad = (int32_t)scr;
+        H.image_bytes += (int32_t)scr;
     }
     if (threadIdx.x == 0) {
         *reinterpret_cast<BlockImageHeader*>(A.block_hdr + 8 * (int64_t)u) = H;
-        A.unit_fallback[u] = fits ? 0 : 1;
+        A.unit_fallback[u] = kind ? 0 : 1;
     }
 }
 
-// Fast path: block emission (ambi_enum_blocks.hpp).  One workgroup per work block of 256*T rows; the workgroup copies
-// the unit's image (block directory + suffix rows) from HBM into LDS, then every wave streams its 64*T rows block by
-// block: four LDS reads, four ORs and one fully coalesced 16-byte store per lane and step.
+// Fast path: block emission (ambi_enum_blocks.hpp).  One workgroup per work block of 256*T rows; the workgroup brings the
+// unit's image (block directory + suffix rows) into LDS (stage_unit_image), then every wave streams its share of the rows
+// block by block (emit_work_block): four LDS reads, four ORs and one fully coalesced 16-byte store per lane and step.
 // A unit with ONE work block has no image in HBM: its workgroup builds the image right here in LDS (automaton copy in
 // front, image behind it) -- the build is a latency-bound chain that hides under the store stream of the other
 // workgroups of the CU -- and the separate build kernel only serves the units that several workgroups share.
-// LDS: [block_lds] image (+ automaton copy while building).
+// LDS: [block_lds] image (+ automaton copy while building); the directory-free walk's state (per wave) in its last kDfsStateBytes.
 template <int CLS>
 __global__ __launch_bounds__(1024) AMBI_ENUM_ATTR void ambi_enumerate_blocks_kernel(BatchArgs A) {
     __shared__ int scratch[40];
     BlockGroup g(scratch);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     uint8_t* tmem = ambi_lds;
-    const uint32_t* image = reinterpret_cast<const uint32_t*>(tmem);
     const int64_t total = A.blk_off[A.n_units];
     int staged_unit = -1;
-    bool fits = false;
-    int nB = 0;
-    // directory-free images (header fits == 2): tables at the front of the image, suffix rows behind; per-wave walk state
-    // in the last kDfsStateBytes of the workgroup's group memory
-    bool dfs = false;
-    int dfs_block_max = 0;
-    BuildTables Bt;
-    const uint32_t* dfs_suf = nullptr;
+    StagedUnit S;
     uint8_t* wave_state = tmem + A.block_lds - kDfsStateBytes + wave * kDfsWaveStride;
     for (int64_t b = (int64_t)blockIdx.x; b < total; b += (int64_t)gridDim.x) {
-        int lo = 0, hi = A.n_units;
-        if (b < A.n_units && A.blk_off[b] == b && A.blk_off[b + 1] == b + 1) lo = (int)b;   // one work block per unit so far: two independent reads
-        else while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (A.blk_off[mid] <= b) lo = mid; else hi = mid; }
-        const int u = A.unit_base + lo;
+        const int lo = unit_of_work_block(A, b), u = A.unit_base + lo;
         const UnitOut* out = unit_out(A.results, u);
         const int K = out->K, T = A.rows_per_lane[u];
         if (enum_class_of(K) != CLS) continue;
@@ -481,105 +414,26 @@ __global__ __launch_bounds__(1024) AMBI_ENUM_ATTR void ambi_enumerate_blocks_ker
             copy_first_rows(g, A.first_rows + (int64_t)u * A.first_budget * kFirstRowStride, K, out->num_orders, A.order_arena + out->order_off);
             continue;
         }
-        if (u != staged_unit) {
-            g.sync();
-            if (A.build_in_emit && A.blk_off[lo + 1] - A.blk_off[lo] == 1) {
-                const IdealTable tbl = unit_ideal_table(A, u);
-                BuildTables dummy;
-                const int64_t scr = carve_build_tables(tmem, tbl.counter[0], tbl.counter[1], dummy);
-                BlockImageHeader H;
-                fits = scr < A.block_lds &&
-                       build_block_image(g, tbl, K, row_stride(K) / 4, out->num_orders, A.block_max, tmem, scr, tmem + scr, A.block_lds - scr, H);
-                dfs = false;
-                if (!fits && A.block_dfs) {   // directory too large: tables + suffix rows, walked at emission (as the build kernel does)
-                    const int64_t budget = (int64_t)A.block_lds - kDfsStateBytes - scr;
-                    for (int bm = A.block_max; bm >= 8 && !fits && budget > 0; bm >>= 1) {
-                        g.sync();
-                        fits = build_block_image(g, tbl, K, row_stride(K) / 4, out->num_orders, bm, tmem, scr, tmem + scr, budget, H, nullptr, false);
-                    }
-                    if (fits) {
-                        dfs = true;
-                        (void)carve_build_tables(tmem, tbl.counter[0], tbl.counter[1], Bt);
-                        dfs_suf = reinterpret_cast<const uint32_t*>(tmem + scr);
-                        dfs_block_max = H.block_max;
-                    }
-                }
-                nB = H.nB;
-                image = reinterpret_cast<const uint32_t*>(tmem + scr);
-                if (!fits && threadIdx.x == 0) A.unit_fallback[u] = 1;   // the general enumerate kernel takes the unit
-                if (threadIdx.x == 0) {   // what this unit's workgroup really needs of its group memory (the host sizes later launches by it)
-                    int32_t* hdr = A.block_hdr + 8 * (int64_t)u;
-                    hdr[0] = fits ? (dfs ? 2 : 1) : 0;
-                    hdr[3] = (int32_t)(scr + (fits ? H.image_bytes : 0) + (dfs ? kDfsStateBytes : 0));
-                }
-            } else {
-                const BlockImageHeader* hdr = reinterpret_cast<const BlockImageHeader*>(A.block_hdr + 8 * (int64_t)u);
-                fits = hdr->fits != 0;
-                dfs = hdr->fits == 2;
-                nB = hdr->nB;
-                image = reinterpret_cast<const uint32_t*>(tmem);
-                if (dfs) {
-                    (void)carve_build_tables(tmem, hdr->nI, hdr->nC, Bt);
-                    dfs_suf = reinterpret_cast<const uint32_t*>(tmem + hdr->pad);
-                    dfs_block_max = hdr->block_max;
-                }
-                if (fits) {   // coalesced copy of the unit's image into LDS
-                    const int64_t nvec = ((int64_t)hdr->image_bytes + 15) >> 4;
-                    const uint4* src = reinterpret_cast<const uint4*>(A.block_img + (int64_t)u * A.block_lds);
-                    uint4* dst = reinterpret_cast<uint4*>(tmem);
-                    for (int64_t i = threadIdx.x; i < nvec; i += blockDim.x) dst[i] = src[i];
-                }
-            }
-            staged_unit = u;
-            g.sync();
-        }
-        if (!fits) continue;
-        const int64_t R = out->num_orders;   // < 2^32 for every unit that has an image
-        // the rows of this work block, split evenly over the workgroup's waves (any row boundary will do: emission
-        // handles unaligned heads and tails)
-        const int64_t blo = (b - A.blk_off[lo]) * 256ll * T;
-        int64_t bhi = blo + 256ll * T;
-        if (bhi > R) bhi = R;
-        const int nwave = (int)(blockDim.x >> 6);
-        const int64_t per = (bhi - blo + nwave - 1) / nwave;
-        const int64_t wlo = blo + (int64_t)wave * per;
-        int64_t whi = wlo + per;
-        if (whi > bhi) whi = bhi;
-        if (!dfs && A.emit_interleave) {   // the blocks of the whole work block dealt round-robin to the waves
-            if (blo < bhi)
-                emit_blocks_dispatch<CLS>(image, nB, K, (uint32_t)blo, (uint32_t)bhi, A.order_arena + out->order_off, lane, lane + 1, wave, nwave);
-        } else if (wlo < whi) {
-            if (dfs)
-                emit_blocks_dfs_dispatch<CLS>(Bt, dfs_suf, K, dfs_block_max, (uint32_t)wlo, (uint32_t)whi, A.order_arena + out->order_off,
-                                              reinterpret_cast<uint16_t*>(wave_state), reinterpret_cast<uint32_t*>(wave_state + 128), lane, lane + 1);
-            else
-                emit_blocks_dispatch<CLS>(image, nB, K, (uint32_t)wlo, (uint32_t)whi,
-                                          A.order_arena + out->order_off, lane, lane + 1);
-        }
+        if (u != staged_unit) { stage_unit_image(g, A, lo, tmem, S); staged_unit = u; }
+        if (!S.fits) continue;
+        emit_work_block<CLS>(S, K, out->num_orders, T, b - A.blk_off[lo], A.order_arena + out->order_off, A.emit_interleave, wave,
+                             (int)(blockDim.x >> 6), lane, lane + 1, wave_state);
     }
 }
 
-// Order tables of the wide units (64..127 nodes, row class 3): 64 workgroups per wide unit, one thread per row -- the row is
-// unranked from the unit's completion counts (unrank_wide) and written as 128 or 256 bytes (nodes, then 0xFF).  Rare units, at most
-// kWideMaxOrders rows each: written for correctness, not for the roofline.
+// Order tables of the wide units (64..127 nodes, row class 3): 64 workgroups per wide unit, one thread per row (write_wide_row).
+// Rare units, at most kWideMaxOrders rows each: written for correctness, not for the roofline.
 __global__ __launch_bounds__(256) void ambi_enumerate_wide_kernel(BatchArgs A, const int32_t* wide_units, int n_wide) {
     const int w = blockIdx.y;
     if (w >= n_wide) return;
     const int u = wide_units[w];
-    if (u < A.unit_base || u >= A.unit_base + A.n_units) return;   // another slice's unit (its WideUnit may be being rebuilt right now)
+    if (u < A.unit_base || u >= A.unit_base + A.n_units) return;   // not a unit of this launch
     const UnitOut* out = unit_out(A.results, u);
     if (out->order_off < 0 || out->num_orders <= 0) return;
     const WideUnit& X = A.wide[A.wide_index[u]];
-    const int K = out->K, stride = row_stride(K);
     uint8_t* rows = A.order_arena + out->order_off;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < out->num_orders; r += (int64_t)gridDim.x * blockDim.x) {
-        alignas(16) uint8_t row[kWideNodeCap];
-        unrank_wide(X, (uint64_t)r, row);
-        for (int d = K; d < stride; d++) row[d] = 0xFF;
-        uint4* dst = reinterpret_cast<uint4*>(rows + r * stride);
-        const uint4* src = reinterpret_cast<const uint4*>(row);
-        for (int q = 0; q < stride / 16; q++) dst[q] = src[q];
-    }
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < out->num_orders; r += (int64_t)gridDim.x * blockDim.x)
+        write_wide_row(X, r, out->K, rows);
 }
 
 __global__ __launch_bounds__(64) AMBI_FIRST_ATTR void ambi_first_kernel(BatchArgs A) {
@@ -1446,8 +1300,7 @@ class HipBackend : public Backend {
             enum_stack_lds_ = (int)enum_stack_bytes(mk);
         }
         lds_enum_ = 4 * (enum_stack_lds_ + enum_auto_lds_);
-        { const char* env = ambi_env("AMBI_BLOCK_LDS"); block_lds_ = env ? atoi(env) : cfg.block_lds; if (block_lds_ < 64) block_lds_ = 64; block_lds_ = (block_lds_ + 15) & ~15; }
-        { const char* env = ambi_env("AMBI_BLOCK_MAX"); block_max_ = env ? atoi(env) : cfg.block_max; if (block_max_ < 1) block_max_ = 1; if (block_max_ > kBlockMaxLimit) block_max_ = kBlockMaxLimit; }
+        { const BlockLimits bl = block_limits(cfg.block_max, cfg.block_lds); block_max_ = bl.block_max; block_lds_ = bl.block_lds; }
         lds_blocks_ = block_lds_;
         const int kLdsLimit = 160 * 1024 - 1024;
         emit_lds_auto_ = !ambi_env("AMBI_BLOCK_LDS");
@@ -1747,6 +1600,17 @@ class HipBackend : public Backend {
         if (grid < 32) grid = 32;
         return grid < U ? (int)grid : U;
     }
+    // the table kernels of a run: block emission per row class, the general path for the units it flagged, the wide units
+    void launch_tables(hipStream_t st, const BatchArgs& A, int lds_emit, bool general) {
+        const int grid = enum_grid_;
+        if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
+        if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
+        if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
+        if ((enum_classes_ & 1) && general) hipLaunchKernelGGL(ambi_enumerate_kernel<0>, dim3(grid), dim3(256), lds_enum_, st, A);
+        if ((enum_classes_ & 2) && general) hipLaunchKernelGGL(ambi_enumerate_kernel<1>, dim3(grid), dim3(256), lds_enum_, st, A);
+        if ((enum_classes_ & 4) && general) hipLaunchKernelGGL(ambi_enumerate_kernel<2>, dim3(grid), dim3(256), lds_enum_, st, A);
+        if (n_wide_ > 0) hipLaunchKernelGGL(ambi_enumerate_wide_kernel, dim3(64, n_wide_), dim3(256), 0, st, A, (const int32_t*)d_wide_units_, n_wide_);
+    }
     void launch_back(const BatchArgs& A) {    // enumerate, first valid order, finish
         hipStream_t st = stream_;
         const int U = A.n_units;
@@ -1770,17 +1634,7 @@ class HipBackend : public Backend {
             (void)hipEventRecord(ev_first_, sb);
         }
         tick("ambi_enumerate_kernel", 3, true);
-        const int lds_emit = lds_blocks_;
-        if (lazy_) {}   // the tables are written on demand (materialise_tables)
-        else {
-        if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
-        if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
-        if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(kEnumThreads), lds_emit, st, A);
-        if ((enum_classes_ & 1) && general_path_ != 0) hipLaunchKernelGGL(ambi_enumerate_kernel<0>, dim3(grid), dim3(256), lds_enum_, st, A);
-        if ((enum_classes_ & 2) && general_path_ != 0) hipLaunchKernelGGL(ambi_enumerate_kernel<1>, dim3(grid), dim3(256), lds_enum_, st, A);
-        if ((enum_classes_ & 4) && general_path_ != 0) hipLaunchKernelGGL(ambi_enumerate_kernel<2>, dim3(grid), dim3(256), lds_enum_, st, A);
-        if (n_wide_ > 0) hipLaunchKernelGGL(ambi_enumerate_wide_kernel, dim3(64, n_wide_), dim3(256), 0, st, A, (const int32_t*)d_wide_units_, n_wide_);
-        }
+        if (!lazy_) launch_tables(st, A, lds_blocks_, general_path_ != 0);   // (lazy: the tables are written on demand, materialise_tables)
         tick("ambi_enumerate_kernel", 3, false);
         if (!overlap_back_) launch_first();   // behind the enumerate kernel on the caller's stream
         // units with deletion / duplication candidates go straight to the full finish stage, on a stream of their own beside
@@ -1921,14 +1775,7 @@ class HipBackend : public Backend {
             hipLaunchKernelGGL(ambi_plan_reset_kernel, dim3((A.n_units + 255) / 256), dim3(256), 0, stream_, A);
             hipLaunchKernelGGL(ambi_plan_kernel, dim3(1), dim3(1024), 0, stream_, A);
             hipLaunchKernelGGL(ambi_blocks_build_kernel, dim3(A.n_units), dim3(256), lds_build_, stream_, A);
-            const int grid = enum_grid_;
-            if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<0>, dim3(grid), dim3(kEnumThreads), lds_blocks_, stream_, A);
-            if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<1>, dim3(grid), dim3(kEnumThreads), lds_blocks_, stream_, A);
-            if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_blocks_kernel<2>, dim3(grid), dim3(kEnumThreads), lds_blocks_, stream_, A);
-            if (enum_classes_ & 1) hipLaunchKernelGGL(ambi_enumerate_kernel<0>, dim3(grid), dim3(256), lds_enum_, stream_, A);
-            if (enum_classes_ & 2) hipLaunchKernelGGL(ambi_enumerate_kernel<1>, dim3(grid), dim3(256), lds_enum_, stream_, A);
-            if (enum_classes_ & 4) hipLaunchKernelGGL(ambi_enumerate_kernel<2>, dim3(grid), dim3(256), lds_enum_, stream_, A);
-            if (n_wide_ > 0) hipLaunchKernelGGL(ambi_enumerate_wide_kernel, dim3(64, n_wide_), dim3(256), 0, stream_, A, (const int32_t*)d_wide_units_, n_wide_);
+            launch_tables(stream_, A, lds_blocks_, true);
             HIP_CK(hipGetLastError());
             HIP_CK(hipStreamSynchronize(stream_));
             const int64_t need = h_needed_[0];

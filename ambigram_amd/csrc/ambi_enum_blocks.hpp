@@ -28,6 +28,16 @@ namespace ambi {
 constexpr bool kEmitRows = true;     // narrow rows leave one row per lane (emit_piece_rows); false: the 16-byte-group form for every width
 constexpr int kBlockMaxLimit = 1024;   // upper bound of BatchArgs::block_max (keeps in-block dword offsets < 2^15)
 
+// BatchArgs::block_max / block_lds of a batch (host code, every backend): the configured values unless env AMBI_BLOCK_MAX /
+// AMBI_BLOCK_LDS say otherwise; block_max in [1, kBlockMaxLimit], block_lds at least 64 bytes and a multiple of 16
+struct BlockLimits { int block_max, block_lds; };
+inline BlockLimits block_limits(int cfg_block_max, int cfg_block_lds) {
+    const char* em = ambi_env("AMBI_BLOCK_MAX");
+    const char* el = ambi_env("AMBI_BLOCK_LDS");
+    const int bm = em ? atoi(em) : cfg_block_max, bl = el ? atoi(el) : cfg_block_lds;
+    return BlockLimits{bm < 1 ? 1 : (bm > kBlockMaxLimit ? kBlockMaxLimit : bm), ((bl < 64 ? 64 : bl) + 15) & ~15};
+}
+
 // wave-uniform value: broadcast lane 0's copy so that the compiler keeps it in scalar registers
 AMBI_HD int uni(int x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -117,7 +127,7 @@ AMBI_HD bool build_block_image(const G& g, const IdealTable& T, int K, int NW, i
     clk_mark(g, clk, 31);
     const int nI = T.counter[0], nC = T.counter[1];
     H.fits = 0; H.nB = 0; H.suf_words = 0; H.image_bytes = 0; H.nI = nI; H.nC = nC; H.block_max = block_max; H.pad = 0;
-    if (nC >= 65535 || nI >= 65535 || R <= 0 || R > 0xFFFFFFF0ll) return false;
+    if (nC >= 65535 || nI >= 65535 || R <= 0 || R > 0xFFFFFFF0ll || image_bytes <= 0) return false;   // (no room at all: the scratch may not be there either)
     if (block_max < 1) block_max = 1;
     if (block_max > kBlockMaxLimit) block_max = kBlockMaxLimit;
     BuildTables B;

@@ -421,10 +421,11 @@ AMBI_HD void plan_serial(const BatchArgs& A) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// stage_enumerate: one work block = 64*T consecutive ranks of one unit = one wavefront; lane l writes rows
-// [base + l*T, base + (l+1)*T) straight from registers (ambi_orders.hpp: enumerate_rows).
-// Per-lane DFS stacks live in group memory; the automaton is read from a compact LDS copy when it fits
-// (LdsAuto) and from HBM/L2 otherwise (GlobalAuto).
+// stage_enumerate: the order table.  Fast path: block emission from a per-unit image (ambi_enum_blocks.hpp; which image a
+// unit gets: build_unit_image; per workgroup: stage_unit_image, per wave: emit_work_block).  General path
+// (enumerate_general_block): a wavefront takes 64*T consecutive ranks; lane l writes rows [base + l*T, base + (l+1)*T)
+// straight from registers (ambi_orders.hpp: enumerate_rows).  Per-lane DFS stacks live in group memory; the automaton
+// is read from a compact LDS copy when it fits (LdsAuto) and from HBM/L2 otherwise (GlobalAuto).
 // ---------------------------------------------------------------------------------------------
 AMBI_HD int64_t enum_stack_bytes(int K) { return pad8(int64_t(64) * K * 3); }
 
@@ -523,6 +524,174 @@ AMBI_HD void enumerate_lane_dispatch(const AUTO32& a32, const AUTO64& a64, const
         if (nw == 12) enumerate_lane<12, uint64_t>(a64, V, K, R, first_rank, T, stack_mem, lane, lanes, unit_rows);
         else if (nw == 16) enumerate_lane<16, uint64_t>(a64, V, K, R, first_rank, T, stack_mem, lane, lanes, unit_rows);
     }
+}
+
+// ---- What the four table kernels (ambi_engine.hip) and the host simulation's enumerate_all run.  A work block = 256*T consecutive
+// rows of one unit = one workgroup.  The position inside the workgroup comes as arguments: `wave` of `nwave`, and the lanes a call
+// stands for, [lane, lane + 1) on the GPU, [0, 64) on the host (the general path: one lane per call). ----
+
+AMBI_HD void copy4(uint32_t* dst, const uint32_t* src) { uint32_t a, b, c, d; load4(src, a, b, c, d); store4(dst, a, b, c, d); }   // 16 bytes
+
+// local index of the unit that work block b belongs to: the last i with blk_off[i] <= b
+AMBI_HD int unit_of_work_block(const BatchArgs& A, int64_t b) {
+    int lo = 0, hi = A.n_units;
+    if (b < A.n_units && A.blk_off[b] == b && A.blk_off[b + 1] == b + 1) lo = (int)b;   // one work block per unit so far: two independent reads
+    else while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (A.blk_off[mid] <= b) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// Which image a unit gets: the directory image if it fits `dir_cap` bytes at image_mem; else (block_dfs) the directory-free
+// image -- the build tables (tables_mem, they stay there for the walk) + suffix rows, walked block by block at emission
+// (emit_blocks_dfs_wave) -- with the largest block size, block_max halved down to 8, whose suffix rows fit `dfs_cap` bytes at
+// image_mem + dfs_off.  Returns 0: none (general path), 1: directory image, 2: directory-free image; H describes the image.
+template <class G>
+AMBI_HD int build_unit_image(const G& g, const IdealTable& tbl, int K, int64_t R, int block_max, int block_dfs, uint8_t* tables_mem,
+                             int64_t tables_cap, uint8_t* image_mem, int64_t dir_cap, int64_t dfs_off, int64_t dfs_cap,
+                             BlockImageHeader& H, int64_t* clk) {
+    const int NW = row_stride(K) / 4;
+    bool fits = build_block_image(g, tbl, K, NW, R, block_max, tables_mem, tables_cap, image_mem, dir_cap, H, clk);
+    if (!fits && block_dfs) {
+        BuildTables dummy;
+        const int64_t scr = carve_build_tables(tables_mem, tbl.counter[0], tbl.counter[1], dummy);
+        for (int bm = block_max; bm >= 8 && !fits && dfs_cap > 0 && scr <= tables_cap; bm >>= 1) {
+            g.sync();
+            fits = build_block_image(g, tbl, K, NW, R, bm, tables_mem, tables_cap, image_mem + dfs_off, dfs_cap, H, nullptr, false);
+        }
+    }
+    return fits ? H.fits : 0;
+}
+
+// a unit as an emitting workgroup holds it across its work blocks
+struct StagedUnit {
+    bool fits = false, dfs = false;       // has an image / a directory-free one
+    int nB = 0, dfs_block_max = 0;        // blocks of the directory / block size of the directory-free image
+    int nI = 0, nC = 0;                   // directory-free image: the build tables the walk reads, at the front of the group memory ...
+    uint8_t* tables = nullptr;
+    const uint32_t* dfs_suf = nullptr;    // ... and its suffix rows
+    const uint32_t* image = nullptr;      // directory image
+    // from the image's header and where its parts lie: the build tables; the image (a directory-free image's suffix rows: H.pad bytes in)
+    AMBI_HD void set(const BlockImageHeader& H, uint8_t* tables_mem, const uint8_t* image_mem) {
+        fits = H.fits != 0; dfs = H.fits == 2; nB = H.nB; nI = H.nI; nC = H.nC; dfs_block_max = H.block_max;
+        tables = tables_mem;
+        image = reinterpret_cast<const uint32_t*>(image_mem); dfs_suf = reinterpret_cast<const uint32_t*>(image_mem + H.pad);
+    }
+};
+// Brings unit A.unit_base + lo into the workgroup's `tmem` (A.block_lds bytes of group memory): built right here (build_in_emit,
+// a unit with ONE work block has no image in HBM), tables in front and the image behind them, and unit_fallback / block_hdr[0] /
+// [3] set for the general kernel and the host; or the header read and the image copied from block_img.  Barriers in front and behind.
+template <class G>
+AMBI_HD void stage_unit_image(const G& g, const BatchArgs& A, int lo, uint8_t* tmem, StagedUnit& S) {
+    const int u = A.unit_base + lo;
+    g.sync();
+    if (A.build_in_emit && A.blk_off[lo + 1] - A.blk_off[lo] == 1) {
+        const UnitOut* out = unit_out(A.results, u);
+        const IdealTable tbl = unit_ideal_table(A, u);
+        BuildTables dummy;
+        const int64_t scr = carve_build_tables(tmem, tbl.counter[0], tbl.counter[1], dummy);
+        BlockImageHeader H;
+        const int kind = build_unit_image(g, tbl, out->K, out->num_orders, A.block_max, A.block_dfs, tmem, scr, tmem + scr, A.block_lds - scr, 0,
+                                          (int64_t)A.block_lds - kDfsStateBytes - scr, H, nullptr);
+        S.set(H, tmem, tmem + scr);
+        if (g.tid() == 0) {
+            if (!S.fits) A.unit_fallback[u] = 1;   // the general enumerate kernel takes the unit
+            int32_t* hdr = A.block_hdr + 8 * (int64_t)u;   // what this unit's workgroup really needs of its group memory (the host sizes later launches by it)
+            hdr[0] = kind;
+            hdr[3] = (int32_t)(scr + (S.fits ? H.image_bytes : 0) + (S.dfs ? kDfsStateBytes : 0));
+        }
+    } else {
+        const BlockImageHeader* hdr = reinterpret_cast<const BlockImageHeader*>(A.block_hdr + 8 * (int64_t)u);
+        S.set(*hdr, tmem, tmem);
+        if (S.fits) {   // coalesced copy of the unit's image into group memory, 16 bytes per thread and step
+            const int64_t nvec = ((int64_t)hdr->image_bytes + 15) >> 4;
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(A.block_img + (int64_t)u * A.block_lds);
+            for (int64_t i = g.tid(); i < nvec; i += g.size()) copy4(reinterpret_cast<uint32_t*>(tmem) + 4 * i, src + 4 * i);
+        }
+    }
+    g.sync();
+}
+
+// One wave's share of work block `blk` (counted inside the unit) of a staged unit: the blocks of the whole work block dealt
+// round-robin to the waves (directory image, `interleave`), or a contiguous nwave-th of its rows (any row boundary will do: emission
+// handles unaligned heads and tails).  wave_state: kDfsWaveBytes of this wave's own in group memory (the directory-free walk).
+template <int CLS>
+AMBI_HD void emit_work_block(const StagedUnit& S, int K, int64_t R /* < 2^32 for every unit that has an image */, int T, int64_t blk,
+                             uint8_t* unit_rows, int interleave, int wave, int nwave, int lane_lo, int lane_hi, uint8_t* wave_state) {
+    const int64_t blo = blk * 256ll * T;
+    int64_t bhi = blo + 256ll * T;
+    if (bhi > R) bhi = R;
+    const int64_t per = (bhi - blo + nwave - 1) / nwave;
+    const int64_t wlo = blo + (int64_t)wave * per;
+    int64_t whi = wlo + per;
+    if (whi > bhi) whi = bhi;
+    if (!S.dfs && interleave) {
+        if (blo < bhi) emit_blocks_dispatch<CLS>(S.image, S.nB, K, (uint32_t)blo, (uint32_t)bhi, unit_rows, lane_lo, lane_hi, wave, nwave);
+    } else if (wlo < whi) {
+        if (S.dfs) {
+            BuildTables Bt;
+            (void)carve_build_tables(S.tables, S.nI, S.nC, Bt);
+            emit_blocks_dfs_dispatch<CLS>(Bt, S.dfs_suf, K, S.dfs_block_max, (uint32_t)wlo, (uint32_t)whi, unit_rows,
+                                          reinterpret_cast<uint16_t*>(wave_state), reinterpret_cast<uint32_t*>(wave_state + 128), lane_lo, lane_hi);
+        } else
+            emit_blocks_dispatch<CLS>(S.image, S.nB, K, (uint32_t)wlo, (uint32_t)whi, unit_rows, lane_lo, lane_hi);
+    }
+}
+
+// General path, one lane's T rows of work block `blk` of unit u: lane l of wave w unranks rank base + (64 w + l) T and walks T
+// lexicographic successors.  g: the wave.  stacks: [A.enum_stack_lds] per-lane DFS stacks (depth-major); amem: [A.enum_auto_lds] compact
+// copy of the automaton (avail masks, child bases, child links), staged once per unit (S) when it fits, else it is read through L2.
+struct StagedAuto { int unit = -1; bool in_lds = false; };
+template <int CLS, class G>
+AMBI_HD void enumerate_general_block(const G& g, const BatchArgs& A, int u, int64_t blk, StagedAuto& S, uint8_t* stacks, uint8_t* amem,
+                                     int wave, int lane) {
+    const UnitOut* out = unit_out(A.results, u);
+    const int K = out->K, T = A.rows_per_lane[u];
+    const int64_t R = out->num_orders;
+    const int64_t base_rank = blk * 256ll * T + (int64_t)wave * 64 * T;
+    const IdealTable tbl = unit_ideal_table(A, u);
+    const AutoView V = auto_view(tbl);
+    const int nI = V.nI, nC = tbl.counter[1];
+    const bool wide = K > 32;
+    const int msz = wide ? 8 : 4;
+    uint8_t* av_l = amem;
+    uint32_t* rec_l = reinterpret_cast<uint32_t*>(amem + (size_t)nI * msz);
+    uint16_t* cb_l = reinterpret_cast<uint16_t*>(rec_l + nI);
+    uint16_t* ch_l = cb_l + nI;
+    if (u != S.unit) {
+        g.sync();
+        const int64_t need = (int64_t)nI * (msz + 6) + 2ll * nC + 16;
+        S.in_lds = need <= A.enum_auto_lds && nC < 65536;
+        if (S.in_lds) {
+            for (int i = g.tid(); i < nI; i += g.size()) {
+                const uint64_t av = V.avail[i];
+                if (wide) reinterpret_cast<uint64_t*>(av_l)[i] = av;
+                else reinterpret_cast<uint32_t*>(av_l)[i] = (uint32_t)av;
+                cb_l[i] = (uint16_t)V.cbase[i];
+                rec_l[i] = av ? make_rec(av, V.child[V.cbase[i]]) : 0u;
+            }
+            for (int i = g.tid(); i < nC; i += g.size()) ch_l[i] = V.child[i];
+        }
+        S.unit = u;
+        g.sync();
+    }
+    uint8_t* rows = A.order_arena + out->order_off;   // 16-byte aligned; lane ranges start at multiples of 4 rows
+    const int64_t first = base_rank + (int64_t)lane * T;
+    if (S.in_lds) {
+        LdsAuto<uint32_t> a32{reinterpret_cast<const uint32_t*>(av_l), rec_l, cb_l, ch_l};
+        LdsAuto<uint64_t> a64{reinterpret_cast<const uint64_t*>(av_l), rec_l, cb_l, ch_l};
+        enumerate_lane_dispatch<CLS>(a32, a64, V, K, R, first, T, stacks, lane, 64, rows);
+    } else {
+        GlobalAuto ga{V};
+        enumerate_lane_dispatch<CLS>(ga, ga, V, K, R, first, T, stacks, lane, 64, rows);
+    }
+}
+
+// Row r of a wide unit's table (64..255 nodes, 128 or 256 bytes): unranked from the unit's completion counts, the nodes, then 0xFF
+AMBI_HD void write_wide_row(const WideUnit& X, int64_t r, int K, uint8_t* rows) {
+    const int stride = row_stride(K);
+    alignas(16) uint8_t row[kWideNodeCap];
+    unrank_wide(X, (uint64_t)r, row);
+    for (int d = K; d < stride; d++) row[d] = 0xFF;
+    for (int q = 0; q < stride / 4; q += 4) copy4(reinterpret_cast<uint32_t*>(rows + r * stride) + q, reinterpret_cast<const uint32_t*>(row) + q);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -65,10 +65,11 @@ class HostSimBackend : public Backend {
     }
 
     void bind(uint32_t flags) {
-        A_.n_units = (int32_t)units_.size(); A_.unit_base = 0; A_.arena_base = 0;   // one slice
+        A_.n_units = (int32_t)units_.size(); A_.unit_base = 0; A_.arena_base = 0;   // one launch over the whole batch
         A_.flags = flags; A_.order_align = 4096 /* as HipBackend's default */; A_.first_budget = cfg_.first_budget; A_.target_lanes = cfg_.target_lanes;
-        { const char* envm = ambi_env("AMBI_BLOCK_MAX"); int bm = envm ? atoi(envm) : cfg_.block_max;   // as HipBackend::upload
-          if (bm < 1) bm = 1; if (bm > kBlockMaxLimit) bm = kBlockMaxLimit; A_.block_max = bm; }
+        { const BlockLimits bl = block_limits(cfg_.block_max, cfg_.block_lds); A_.block_max = bl.block_max; A_.block_lds = bl.block_lds; }
+        { const char* e = ambi_env("AMBI_EMIT_INTERLEAVE"); A_.emit_interleave = e ? (atoi(e) != 0) : 1; }   // as HipBackend::upload
+        A_.enum_auto_lds = 4096;   // (HipBackend's budget: the general path reads small automata from its compact copy here too)
         A_.ideal_pos = ipos_.data(); A_.auto_avail = aavail_.data(); A_.auto_cnt = acnt_.data();
         A_.auto_cbase = acbase_.data(); A_.auto_child = achild_.data(); A_.auto_nblk = anblk_.data(); A_.auto_depth = adepth_.data();
         A_.units = units_.data(); A_.seg_cn = hb_.seg_cn.data(); A_.junc_cn = hb_.junc_cn.data(); A_.junc_ends = hb_.junc_ends.data(); A_.elems = hb_.elems.data();
@@ -93,80 +94,47 @@ class HostSimBackend : public Backend {
         }
     }
 
+    // the order tables: stage_enumerate (ambi_stages.hpp) as the table kernels run it, work block by work block and, inside one, wave by
+    // wave (four of 64 lanes, as launched); every image built as ambi_blocks_build_kernel does (tables and image in buffers of their own)
     void enumerate_all() {
         HostGroup g;
+        const int nwave = 4;
         const int64_t total = blk_off_[units_.size()];
-        std::vector<uint8_t> stacks((size_t)enum_stack_bytes(64));
-        const char* env = ambi_env("AMBI_BLOCK_LDS");
-        const int64_t block_lds = env ? atoll(env) : cfg_.block_lds;
-        const int block_max = A_.block_max;
-        std::vector<uint8_t> image((size_t)(block_lds > 64 ? block_lds : 64));
-        std::vector<uint8_t> bscratch((size_t)cfg_.block_scratch_lds);
+        std::vector<uint8_t> stacks((size_t)enum_stack_bytes(64)), amem((size_t)A_.enum_auto_lds + 16), wave_state((size_t)kDfsWaveStride);
+        std::vector<uint8_t> image((size_t)A_.block_lds), bscratch((size_t)cfg_.block_scratch_lds);
+        const bool trace = ambi_env("AMBI_HOSTSIM_TRACE") != nullptr;
         int built_unit = -1;
-        BlockImageHeader H{};
-        bool fast = false, dfs = false;
-        BuildTables Bt{};
-        std::vector<uint16_t> dfs_stack(64);
-        std::vector<uint32_t> dfs_pw(20);
+        StagedUnit S;
+        StagedAuto SA;
         for (int64_t b = 0; b < total; b++) {
-            int lo = 0, hi = (int)units_.size();
-            while (hi - lo > 1) { int mid = (lo + hi) / 2; if (blk_off_[mid] <= b) lo = mid; else hi = mid; }
-            const int u = lo;
-            UnitOut* out = unit_out(A_.results, u);
+            const int u = unit_of_work_block(A_, b);
+            const UnitOut* out = unit_out(A_.results, u);
             const int K = out->K, T = rows_per_lane_[u];
-            const int64_t R = out->num_orders, base_rank = (b - blk_off_[u]) * 256ll * T;
-            IdealTable tbl = unit_ideal_table(A_, u);
-            AutoView V = auto_view(tbl);
+            const int64_t R = out->num_orders, blk = b - blk_off_[u];
             uint8_t* rows = A_.order_arena + out->order_off;
-            if (K > kMaxNodes) {   // ambi_enumerate_wide_kernel: every row unranked from the wide unit's counts (once per unit)
-                if (b == blk_off_[u]) {
-                    const WideUnit& X = A_.wide[A_.wide_index[u]];
-                    const int stride = row_stride(K);
-                    for (int64_t r = 0; r < R; r++) {
-                        uint8_t row[kWideNodeCap];
-                        unrank_wide(X, (uint64_t)r, row);
-                        for (int d = K; d < stride; d++) row[d] = 0xFF;
-                        memcpy(rows + r * stride, row, (size_t)stride);
-                    }
-                }
+            if (K > kMaxNodes) {   // ambi_enumerate_wide_kernel (once per unit)
+                for (int64_t r = 0; r < R && blk == 0; r++) write_wide_row(A_.wide[A_.wide_index[u]], r, K, rows);
                 continue;
             }
             if (A_.first_rows && R <= A_.first_budget) {   // as ambi_enumerate_blocks_kernel: the table is a copy of the first rows
                 copy_first_rows(g, A_.first_rows + (int64_t)u * A_.first_budget * kFirstRowStride, K, R, rows);
                 continue;
             }
-            if (u != built_unit) {   // ambi_blocks_build_kernel: once per unit
-                fast = build_block_image(g, tbl, K, row_stride(K) / 4, R, block_max, bscratch.data(), (int64_t)bscratch.size(),
-                                         image.data(), block_lds, H);
-                dfs = false;
-                if (ambi_env("AMBI_HOSTSIM_TRACE")) { BuildTables d2; fprintf(stderr, "hostsim: unit %d K=%d R=%lld nI=%d nC=%d nB=%d suf_words=%d image_bytes=%d scratch=%lld\n", u, K, (long long)R, H.nI, H.nC, H.nB, H.suf_words, H.image_bytes, (long long)carve_build_tables(bscratch.data(), H.nI, H.nC, d2)); }
-                if (!fast) {   // ambi_blocks_build_kernel's second form: tables + suffix rows, walked at emission
-                    BuildTables dummy;
-                    const int64_t scr = carve_build_tables(bscratch.data(), tbl.counter[0], tbl.counter[1], dummy);
-                    const int64_t budget = block_lds - kDfsStateBytes - scr;
-                    for (int bm = block_max; bm >= 8 && !fast && budget > 0 && scr <= (int64_t)bscratch.size(); bm >>= 1)
-                        fast = build_block_image(g, tbl, K, row_stride(K) / 4, R, bm, bscratch.data(), (int64_t)bscratch.size(),
-                                                 image.data(), budget, H, nullptr, false);
-                    if (fast) { dfs = true; (void)carve_build_tables(bscratch.data(), tbl.counter[0], tbl.counter[1], Bt); }
-                    if (ambi_env("AMBI_HOSTSIM_TRACE")) fprintf(stderr, "hostsim: unit %d (K=%d, R=%lld): %s\n", u, K, (long long)R, fast ? "directory-free block walk" : "general path");
-                }
+            if (u != built_unit) {
+                const IdealTable tbl = unit_ideal_table(A_, u);
+                BlockImageHeader H;
+                BuildTables dummy;
+                const int64_t scr = carve_build_tables(bscratch.data(), tbl.counter[0], tbl.counter[1], dummy);
+                const int kind = build_unit_image(g, tbl, K, R, A_.block_max, /* block_dfs */ 1, bscratch.data(), (int64_t)bscratch.size(), image.data(), A_.block_lds, 0,
+                                                  (int64_t)A_.block_lds - kDfsStateBytes - scr, H, nullptr);
+                S.set(H, bscratch.data(), image.data());
+                if (trace) fprintf(stderr, "hostsim: unit %d K=%d R=%lld nI=%d nC=%d nB=%d suf_words=%d image_bytes=%d scratch=%lld\n", u, K, (long long)R, H.nI, H.nC, H.nB, H.suf_words, H.image_bytes, (long long)scr);
+                if (trace && kind != 1) fprintf(stderr, "hostsim: unit %d (K=%d, R=%lld): %s\n", u, K, (long long)R, kind ? "directory-free block walk" : "general path");
                 built_unit = u;
             }
-            for (int w = 0; w < 4; w++) {
-                const int64_t wlo = base_rank + (int64_t)w * 64 * T;
-                int64_t whi = wlo + 64ll * T;
-                if (whi > R) whi = R;
-                if (wlo >= R) break;
-                if (fast && dfs) {
-                    emit_blocks_dfs_dispatch<-1>(Bt, reinterpret_cast<const uint32_t*>(image.data()), K, H.block_max, (uint32_t)wlo, (uint32_t)whi, rows,
-                                                 dfs_stack.data(), dfs_pw.data(), 0, 64);
-                } else if (fast) {
-                    emit_blocks_dispatch<-1>(reinterpret_cast<const uint32_t*>(image.data()), H.nB, K, (uint32_t)wlo, (uint32_t)whi, rows, 0, 64);
-                } else {
-                    GlobalAuto ga{V};
-                    for (int lane = 0; lane < 64; lane++)
-                        enumerate_lane_dispatch<-1>(ga, ga, V, K, R, wlo + (int64_t)lane * T, T, stacks.data(), lane, 64, rows);
-                }
+            for (int wave = 0; wave < nwave; wave++) {
+                if (S.fits) emit_work_block<-1>(S, K, R, T, blk, rows, A_.emit_interleave, wave, nwave, 0, 64, wave_state.data());
+                else for (int lane = 0; lane < 64; lane++) enumerate_general_block<-1>(g, A_, u, blk, SA, stacks.data(), amem.data(), wave, lane);
             }
         }
     }
