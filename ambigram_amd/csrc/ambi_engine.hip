@@ -442,30 +442,13 @@ __global__ __launch_bounds__(64) AMBI_FIRST_ATTR void ambi_first_kernel(BatchArg
 }
 
 // Slow path: units whose first-valid scan ran out of budget.  One wave per chunk of `chunk` consecutive orders
-// (ambi_stages.hpp: stage_search_chunk / stage_resolve).
-struct SearchArgs {
-    const int32_t* pending;      // [np] unit indices
-    const int64_t* chunk_off;    // [np+1] prefix of chunk counts
-    SearchSlot* slots;           // [np] per pass: least valid index / least undefined index
-    int32_t np, chunk, forward, wave_lds;
-};
+// (ambi_stages.hpp: search_item / stage_resolve).
 __global__ __launch_bounds__(256) void ambi_search_kernel(BatchArgs A, SearchArgs S) {
     const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     uint8_t* work = ambi_lds + (size_t)wave * S.wave_lds;
     WaveGroup g;
     const int64_t total = S.chunk_off[S.np];
-    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < total; c += (int64_t)gridDim.x * wpb) {
-        int lo = 0, hi = S.np;
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (S.chunk_off[mid] <= c) lo = mid; else hi = mid; }
-        const int p = lo, u = S.pending[p];
-        const UnitIn& U = A.units[u];
-        if (unit_out(A.results, u)->status != ST_PENDING) continue;   // resolved by the previous pass
-        const int64_t first = (c - S.chunk_off[p]) * S.chunk;
-        if (first >= search_limit(load_now_i64(&S.slots[p].found), load_now_i64(&S.slots[p].err_key))) continue;   // an earlier hit is already known
-        FirstWork W = carve_first(work, U.n_seg, U.bkp_cap, U.n_elem > kMaxNodes);
-        load_first_work(g, A, u, W);
-        stage_search_chunk(g, A, u, W, first, S.chunk, S.forward != 0, &S.slots[p]);
-    }
+    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < total; c += (int64_t)gridDim.x * wpb) search_item(g, A, S, c, work);
 }
 __global__ void ambi_search_init_kernel(SearchSlot* slots, int np) {
     const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -478,104 +461,33 @@ __global__ __launch_bounds__(64) void ambi_resolve_kernel(BatchArgs A, SearchArg
     stage_resolve(g, A, S.pending[p], ambi_lds, &S.slots[p], S.forward != 0, pass);
 }
 
-// --all (LGM.cpp:3672-3695), fused enumerate + evaluate (ambi_stages.hpp: stage_all_chunk): one wave per 64 consecutive
-// orders of a unit, all units of the batch in ONE launch per pass; the orders are unranked from the automaton by the
-// lanes, never read from the table.  Output: one 64-bit word of the unit's validity bitmap per wave-chunk.
-// Work item c of the launch = word c of the concatenated pass-0 maps (all_off is also the chunk prefix, up to the
-// factor 2 for the two passes).  LDS per wave: first-work area + 64 unranked rows.
-// One thread per order (stage_all_chunk_lanes) for units whose breakpoint path has at most lane_cap cells -- the rule on
-// real inputs (a path of ~100 cells at 256 segments); ambi_all_kernel below keeps the longer ones.
-// LDS per wave: DAG + fold-back map | 64 x 64 bytes of transposed orders | lane_cap x 64 cells.
-__global__ __launch_bounds__(256) void ambi_all_lanes_kernel(BatchArgs A, int pass, int wave_lds, int64_t total_chunks, int lane_cap, int head_bytes,
-                                                            int lane_cells, int auto_bytes, int rows_bytes) {
+// --all (LGM.cpp:3672-3695), fused enumerate + evaluate (ambi_stages.hpp: all_lanes_item / all_wave_item): one wave per 64
+// consecutive orders of a unit, all units of the batch in ONE launch per pass.  One thread per order for units whose breakpoint
+// path has at most lane_cap cells -- the rule on real inputs (a path of ~100 cells at 256 segments); ambi_all_kernel keeps the
+// longer ones.  LDS per wave: AllLaneGeom::wave_lds here, first-work area + 64 unranked rows in ambi_all_kernel.
+__global__ __launch_bounds__(256) void ambi_all_lanes_kernel(BatchArgs A, AllLaneGeom geom, int pass, int64_t total_chunks, int lane_cap) {
     const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    uint8_t* work = ambi_lds + (size_t)wave * wave_lds;
+    uint8_t* work = ambi_lds + (size_t)wave * geom.wave_lds;
     WaveGroup g;
-    int loaded = -1;
-    bool staged_ok = false;
-    AutoView SV{};
-    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < total_chunks; c += (int64_t)gridDim.x * wpb) {
-        int lo = 0, hi = A.n_units;
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (A.all_off[mid] <= 2 * c) lo = mid; else hi = mid; }
-        const int u = lo;
-        const UnitIn& U = A.units[u];
-        if (U.bkp_cap > lane_cap || U.n_elem > kMaxNodes) continue;   // (long breakpoint paths and wide units: ambi_all_kernel)
-        const int64_t R = unit_out(A.results, u)->num_orders;
-        if (!all_chunk_is_mine(A, c, c - A.all_off[u] / 2, R)) continue;   // another rank's chunk
-        if (pass == 1 && all_pass0_last_valid(A, u, R)) continue;
-        FirstWork W = carve_first(work, U.n_seg, 8);   // (the wavefront form's breakpoint area is not used here)
-        uint8_t* rows_t = work + head_bytes;
-        cell_t* cells = reinterpret_cast<cell_t*>(rows_t + rows_bytes);
-        // the unit's automaton behind the cells: every lane unranks its own order (K dependent steps), from group memory
-        // instead of 64 scattered walks through L2
-        uint8_t* amem = reinterpret_cast<uint8_t*>(cells) + (size_t)lane_cells * 64 * sizeof(cell_t);
-        if (u != loaded) {
-            g.sync();
-            load_first_work(g, A, u, W);
-            const IdealTable T = unit_ideal_table(A, u);
-            const int nI = T.counter[0], nC = T.counter[1];
-            const int64_t need = 16ll * nI + 4ll * (nI + 1) + 2ll * nC + 16;
-            staged_ok = need <= auto_bytes;
-            if (staged_ok) {
-                uint64_t* av = reinterpret_cast<uint64_t*>(amem);
-                uint64_t* cn = av + nI;
-                int32_t* cb = reinterpret_cast<int32_t*>(cn + nI);
-                uint16_t* ch = reinterpret_cast<uint16_t*>(cb + nI + 1);
-                for (int i = threadIdx.x & 63; i < nI; i += 64) { av[i] = T.a_avail[i]; cn[i] = T.a_cnt[i]; }
-                for (int i = threadIdx.x & 63; i <= nI; i += 64) cb[i] = T.a_cbase[i];
-                for (int i = threadIdx.x & 63; i < nC; i += 64) ch[i] = T.a_child[i];
-                SV = AutoView{av, cn, cb, ch, nI};
-            }
-            loaded = u;
-            g.sync();
-        }
-        stage_all_chunk_lanes(g, A, u, W, rows_t, cells, c - A.all_off[u] / 2, pass, staged_ok ? &SV : nullptr);
-        g.sync();
-    }
+    AllLaneState state;
+    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < total_chunks; c += (int64_t)gridDim.x * wpb) all_lanes_item(g, A, geom, c, pass, work, lane_cap, state);
 }
 __global__ __launch_bounds__(256) void ambi_all_kernel(BatchArgs A, int pass, int wave_lds, int64_t total_chunks, int lane_cap) {
     const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     uint8_t* work = ambi_lds + (size_t)wave * wave_lds;
     WaveGroup g;
-    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < total_chunks; c += (int64_t)gridDim.x * wpb) {
-        // all_off[u] = 2 * (chunks of the units before u)
-        int lo = 0, hi = A.n_units;
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (A.all_off[mid] <= 2 * c) lo = mid; else hi = mid; }
-        const int u = lo;
-        const int64_t R = unit_out(A.results, u)->num_orders;
-        if (pass == 1 && all_pass0_last_valid(A, u, R)) continue;   // no orientation flip for this unit (LGM.cpp:3691-3695)
-        const UnitIn& U = A.units[u];
-        const bool wide = U.n_elem > kMaxNodes;
-        if (U.bkp_cap <= lane_cap && !wide) continue;                // taken by ambi_all_lanes_kernel
-        if (!all_chunk_is_mine(A, c, c - A.all_off[u] / 2, R)) continue;   // another rank's chunk
-        FirstWork W = carve_first(work, U.n_seg, U.bkp_cap, wide);
-        uint8_t* rows = work + first_work_bytes(U.n_seg, U.bkp_cap, wide);
-        g.sync();
-        load_first_work(g, A, u, W);
-        stage_all_chunk(g, A, u, W, rows, c - A.all_off[u] / 2, pass);
-    }
+    for (int64_t c = (int64_t)blockIdx.x * wpb + wave; c < total_chunks; c += (int64_t)gridDim.x * wpb) all_wave_item(g, A, c, pass, work, lane_cap);
 }
 __global__ __launch_bounds__(256) void ambi_all_finalize_kernel(BatchArgs A) {
     const int u = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (u < A.n_units) all_finalize_unit(A, u);
 }
-// Paths of a list of orders of one unit (the valid ones, in print order): one wave per order, breakpoints in LDS,
-// the expanded path (absolute signed ids) straight to cells[j * stride ...], its length to lengths[j].
+// Paths of a list of orders of one unit (the valid ones, in print order): one wave per order, breakpoints in LDS
+// (ambi_stages.hpp: order_path_item).
 __global__ __launch_bounds__(64) void ambi_order_paths_kernel(BatchArgs A, int u, int forward, const int64_t* order_idx, int32_t* lengths,
                                                               int32_t* cells, int64_t stride) {
     WaveGroup g;
-    const UnitIn& U = A.units[u];
-    const int j = blockIdx.x;
-    const bool wide = U.n_elem > kMaxNodes;
-    FirstWork W = carve_first(ambi_lds, U.n_seg, U.bkp_cap, wide);
-    int32_t* offs = reinterpret_cast<int32_t*>(ambi_lds + first_work_bytes(U.n_seg, U.bkp_cap, wide));
-    load_first_work(g, A, u, W);
-    int L = 0;
-    const int v = eval_indexed(g, A, u, W, order_idx[j], forward != 0, &L);
-    if (gridDim.x == 1) debug_store_order(g, A, u, W.ord, unit_out(A.results, u)->K);   // (diagnostics: a request for ONE path also tells which row it was made from)
-    int P = -1;
-    if (v == 1) P = expand_bkp(g, W.bkp, L, (cell_t*)nullptr, (int)(stride < U.path_cap ? stride : U.path_cap), offs, cells + (int64_t)j * stride, U.seg_base);
-    if (g.tid() == 0) lengths[j] = P;
+    order_path_item(g, A, u, forward != 0, order_idx, (int64_t)blockIdx.x, gridDim.x == 1, lengths, cells, stride, ambi_lds);
 }
 
 // Full finish stage.  unit_list == nullptr: every unit of the batch (one workgroup each).  With a list: the listed units;
@@ -1895,8 +1807,7 @@ class HipBackend : public Backend {
         }
         if (pend.empty() && refin.empty()) return 0;
         const int np = (int)pend.size(), nfin = np + (int)refin.size(), chunk = 16;
-        std::vector<int64_t> coff(np + 1, 0);
-        for (int p = 0; p < np; p++) coff[p + 1] = coff[p] + (hdr[pend[p]].num_orders + chunk - 1) / chunk;
+        const std::vector<int64_t> coff = search_chunk_prefix(hdr.data(), pend, chunk);
         std::vector<int32_t> fin(pend);
         fin.insert(fin.end(), refin.begin(), refin.end());
         DevBuf b_pend, b_coff, b_slots;
@@ -2271,25 +2182,18 @@ class HipBackend : public Backend {
         const int U = (int)hb().units.size();
         std::vector<UnitOut> hdr(U);
         HIP_CK(hipMemcpy(hdr.data(), d_results_, U * sizeof(UnitOut), hipMemcpyDeviceToHost));
-        all_off_.assign(U + 1, 0);
-        for (int u = 0; u < U; u++) {
-            const bool live = hdr[u].status == ST_OK && hdr[u].num_orders > 0 && hdr[u].num_orders < (int64_t)kCountSat;
-            all_off_[u + 1] = all_off_[u] + (live ? 2 * all_words(hdr[u].num_orders) : 0);
-        }
+        const AllPlan plan = all_plan(hdr.data(), U, all_off_);
         all_R_.resize(U);
         for (int u = 0; u < U; u++) all_R_[u] = hdr[u].num_orders;
         all_cache_.assign(U, {});
         all_idx_[0].assign(U, {}); all_idx_[1].assign(U, {});
         all_counts_.assign(2 * (size_t)U, 0);
-        const int64_t words = all_off_[U], chunks = words / 2;
-        // one pool: [bitmaps: words x 8 bytes][flags: U x 4 bytes] -- what ranks merge with ONE reduction when a wide sample's
-        // orders are dealt over them (ambi_batch_all_device)
-        const int64_t pool_words = words + ((int64_t)U + 1) / 2 + 1;
+        const int64_t words = plan.words, chunks = words / 2, pool_words = plan.pool_words;
         if (d_all_bits_ && all_bits_cap_ < pool_words) { (void)hipFree(d_all_bits_); d_all_bits_ = nullptr; }
         if (!d_all_off_) { if (int rc = dalloc(&d_all_off_, (size_t)U + 1)) return rc; if (int rc = dalloc(&d_all_count_, 2 * (size_t)U)) return rc; }
         if (!d_all_bits_) { HIP_CK(hipMalloc((void**)&d_all_bits_, (size_t)pool_words * sizeof(uint64_t))); all_bits_cap_ = pool_words; }
         d_all_flags_ = reinterpret_cast<int32_t*>(d_all_bits_ + words);
-        all_pool_bytes_ = (words + ((int64_t)U + 1) / 2) * (int64_t)sizeof(uint64_t);
+        all_pool_bytes_ = plan.pool_bytes;
         HIP_CK(hipMemcpyAsync(d_all_off_, all_off_.data(), (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
         HIP_CK(hipMemsetAsync(d_all_bits_, 0, (size_t)pool_words * sizeof(uint64_t), stream_));
         HIP_CK(hipMemsetAsync(d_all_count_, 0, 2 * (size_t)U * sizeof(int32_t), stream_));
@@ -2304,28 +2208,16 @@ class HipBackend : public Backend {
             hipEvent_t& ea = ev.a; hipEvent_t& eb = ev.b;
             if (timing_) { HIP_CK(hipEventCreate(&ea)); HIP_CK(hipEventCreate(&eb)); HIP_CK(hipEventRecord(ea, stream_)); }
             // units with a short breakpoint path (the rule): one thread per order; the others: one wavefront per order
-            int lane_cap = 0, lanes_units = 0, wave_units = 0;
-            { const char* e = ambi_env("AMBI_ALL_LANES"); lane_cap = (e && atoi(e) == 0) ? 0 : kAllLaneMaxCells; }
-            auto lane_unit = [&](int u) { return hb().units[u].bkp_cap <= lane_cap && hb().units[u].n_elem <= kMaxNodes; };
-            for (int u = 0; u < U; u++) if (all_off_[u + 1] > all_off_[u]) { if (lane_unit(u)) lanes_units++; else wave_units++; }
-            int max_lane_cells = 8;
-            for (int u = 0; u < U; u++) if (lane_unit(u) && hb().units[u].bkp_cap > max_lane_cells) max_lane_cells = hb().units[u].bkp_cap;
-            const int head_bytes = (int)((first_work_bytes(hb().max_n, 8) + 15) & ~15);
-            // group memory for a staged copy of the unit's automaton (env AMBI_ALL_AUTO_LDS): 0 = the lanes unrank through L2.
-            // Measured (4096 bench units): 0 / 4096 / 8192 bytes = 561 / 489 / 390 M orders/s -- the kernel lives on the number
-            // of resident wavefronts (group-memory latency), and every KB of group memory costs some.
-            int auto_bytes = 0;
-            { const char* e = ambi_env("AMBI_ALL_AUTO_LDS"); if (e) auto_bytes = atoi(e) & ~15; if (auto_bytes < 0) auto_bytes = 0; }
-            int max_k_lane = 1;
-            for (const UnitIn& un : hb().units) if (un.n_elem <= kMaxNodes && un.n_elem > max_k_lane) max_k_lane = un.n_elem;   // (wide units: ambi_all_kernel)
-            const int rows_bytes = 64 * ((max_k_lane + 3) & ~3);   // transposed orders: one 64-lane row per position
-            const int lane_wave_lds = (head_bytes + rows_bytes + max_lane_cells * 64 * (int)sizeof(cell_t) + auto_bytes + 15) & ~15;
+            const int lane_cap = all_lane_cap();
+            int lanes_units = 0, wave_units = 0;
+            for (int u = 0; u < U; u++) if (all_off_[u + 1] > all_off_[u]) { if (all_lane_unit(hb().units[u], lane_cap)) lanes_units++; else wave_units++; }
+            const AllLaneGeom geom = all_lane_geom(hb().units, hb().max_n, lane_cap);
             int lane_waves = 1;   // wavefronts per workgroup (measured 1 / 2 / 4 = 563 / 553 / 379 M orders/s: group-memory allocation granularity)
             { const char* e = ambi_env("AMBI_ALL_WAVES"); if (e && atoi(e) >= 1 && atoi(e) <= 4) lane_waves = atoi(e); }
             int64_t lblk = (chunks + lane_waves - 1) / lane_waves;
             if (lblk > (1 << 20)) lblk = 1 << 20;
             for (int pass = 0; pass < 2; pass++) {
-                if (lanes_units) hipLaunchKernelGGL(ambi_all_lanes_kernel, dim3((unsigned)lblk), dim3(64 * lane_waves), lane_waves * lane_wave_lds, stream_, A_, pass, lane_wave_lds, chunks, lane_cap, head_bytes, max_lane_cells, auto_bytes, rows_bytes);
+                if (lanes_units) hipLaunchKernelGGL(ambi_all_lanes_kernel, dim3((unsigned)lblk), dim3(64 * lane_waves), lane_waves * geom.wave_lds, stream_, A_, geom, pass, chunks, lane_cap);
                 if (wave_units) hipLaunchKernelGGL(ambi_all_kernel, dim3((unsigned)nblk), dim3(64 * waves), waves * wave_lds, stream_, A_, pass, wave_lds, chunks, lane_cap);
             }
             if (timing_) HIP_CK(hipEventRecord(eb, stream_));
@@ -2366,14 +2258,7 @@ class HipBackend : public Backend {
             all_cache_[unit].resize((size_t)(all_off_[unit + 1] - all_off_[unit]));
             HIP_CK(hipMemcpy(all_cache_[unit].data(), d_all_bits_ + all_off_[unit], all_cache_[unit].size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
             const int64_t nw = all_words(all_R_[unit]);
-            for (int ps = 0; ps < 2; ps++) {
-                auto& v = all_idx_[ps][unit];
-                v.clear();
-                for (int64_t w = 0; w < nw; w++) {
-                    uint64_t x = all_cache_[unit][(size_t)(ps * nw + w)];
-                    while (x) { v.push_back(w * 64 + __builtin_ctzll(x)); x &= x - 1; }
-                }
-            }
+            for (int ps = 0; ps < 2; ps++) all_bits_to_indices(all_cache_[unit].data() + ps * nw, nw, all_idx_[ps][unit]);
         }
         *out = &all_idx_[pass][unit];
         return 0;
@@ -2409,7 +2294,7 @@ class HipBackend : public Backend {
         HIP_CK(b_cells.alloc((size_t)count * (size_t)stride * sizeof(int32_t)));
         int64_t* d_idx = b_idx.as<int64_t>(); int32_t* d_len = b_len.as<int32_t>(); int32_t* d_cells = b_cells.as<int32_t>();
         HIP_CK(hipMemcpy(d_idx, v.data() + first, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice));
-        const int lds = (int)(first_work_bytes(Uin.n_seg, Uin.bkp_cap, Uin.n_elem > kMaxNodes) + 4ll * (Uin.bkp_cap / 2 + 2) + 16);
+        const int lds = (int)order_path_work_bytes(Uin);
         hipLaunchKernelGGL(ambi_order_paths_kernel, dim3((unsigned)count), dim3(64), lds, stream_, A_, unit, fwd ? 1 : 0, (const int64_t*)d_idx, d_len,
                            d_cells, stride);
         HIP_CK(hipGetLastError());

@@ -10,6 +10,8 @@
 //   stage_finish_lean  bkp -> path, indelBFB, output junctions, from the runs of the breakpoint path (every unit)
 //   stage_finish    the same with the path cells in group memory: units whose SVs chain or edit the path
 #pragma once
+#include <vector>
+
 #include "ambi_batch.hpp"
 #include "ambi_enum_blocks.hpp"
 #include "ambi_eval.hpp"
@@ -532,12 +534,16 @@ AMBI_HD void enumerate_lane_dispatch(const AUTO32& a32, const AUTO64& a64, const
 
 AMBI_HD void copy4(uint32_t* dst, const uint32_t* src) { uint32_t a, b, c, d; load4(src, a, b, c, d); store4(dst, a, b, c, d); }   // 16 bytes
 
-// local index of the unit that work block b belongs to: the last i with blk_off[i] <= b
-AMBI_HD int unit_of_work_block(const BatchArgs& A, int64_t b) {
-    int lo = 0, hi = A.n_units;
-    if (b < A.n_units && A.blk_off[b] == b && A.blk_off[b + 1] == b + 1) lo = (int)b;   // one work block per unit so far: two independent reads
-    else while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (A.blk_off[mid] <= b) lo = mid; else hi = mid; }
+// the last i in [0, n) with off[i] <= key (off: a prefix of counts, off[0] = 0 <= key): whose work item `key` is
+AMBI_HD int prefix_find(const int64_t* off, int n, int64_t key) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (off[mid] <= key) lo = mid; else hi = mid; }
     return lo;
+}
+// local index of the unit that work block b belongs to
+AMBI_HD int unit_of_work_block(const BatchArgs& A, int64_t b) {
+    if (b < A.n_units && A.blk_off[b] == b && A.blk_off[b + 1] == b + 1) return (int)b;   // one work block per unit so far: two independent reads
+    return prefix_find(A.blk_off, A.n_units, b);
 }
 
 // Which image a unit gets: the directory image if it fits `dir_cap` bytes at image_mem; else (block_dfs) the directory-free
@@ -889,6 +895,31 @@ AMBI_HD void stage_search_chunk(const G& g, const BatchArgs& A, int u, const Fir
     }
     g.sync();
 }
+// One pass of the search over all pending units, as ambi_search_kernel and the host simulation run it
+struct SearchArgs {
+    const int32_t* pending;      // [np] unit indices
+    const int64_t* chunk_off;    // [np+1] prefix of chunk counts (search_chunk_prefix)
+    SearchSlot* slots;           // [np] per pass: least valid index / least undefined index
+    int32_t np, chunk, forward, wave_lds;
+};
+// work item c of a pass = one chunk of one pending unit; `work`: first_work_bytes of group memory
+template <class G>
+AMBI_HD void search_item(const G& g, const BatchArgs& A, const SearchArgs& S, int64_t c, uint8_t* work) {
+    const int p = prefix_find(S.chunk_off, S.np, c), u = S.pending[p];
+    const UnitIn& U = A.units[u];
+    if (unit_out(A.results, u)->status != ST_PENDING) return;   // resolved by the previous pass
+    const int64_t first = (c - S.chunk_off[p]) * S.chunk;
+    if (first >= search_limit(load_now_i64(&S.slots[p].found), load_now_i64(&S.slots[p].err_key))) return;   // an earlier hit is already known
+    FirstWork W = carve_first(work, U.n_seg, U.bkp_cap, U.n_elem > kMaxNodes);
+    load_first_work(g, A, u, W);
+    stage_search_chunk(g, A, u, W, first, S.chunk, S.forward != 0, &S.slots[p]);
+}
+// host code, every backend: the chunk prefix of the pending units (hdr: the batch's headers)
+inline std::vector<int64_t> search_chunk_prefix(const UnitOut* hdr, const std::vector<int32_t>& pend, int chunk) {
+    std::vector<int64_t> coff(pend.size() + 1, 0);
+    for (size_t p = 0; p < pend.size(); p++) coff[p + 1] = coff[p] + (hdr[pend[p]].num_orders + chunk - 1) / chunk;
+    return coff;
+}
 
 // after a pass of the search: the unit's verdict, or nothing when the pass found nothing and the other orientation is
 // still to come.  `work`: first_work_bytes of group memory.
@@ -1032,6 +1063,123 @@ AMBI_HD void all_finalize_unit(const BatchArgs& A, int u) {
     }
     out->evaluated = (int32_t)(all_pass0_last_valid(A, u, R) ? R : 2 * R);
     if (A.all_flags[u]) out->status = ST_ERR_REF_UB;
+}
+
+// ---- What ambi_all_lanes_kernel / ambi_all_kernel / ambi_order_paths_kernel and the host simulation run.  Work item c of a pass =
+// word c of the concatenated pass-0 maps: all_off[u] = 2 * (chunks of the units before u), for the two passes.  Both kernels
+// walk every c of the launch and each takes the chunks of its own units. ----
+// one thread per order for this unit (short breakpoint path, ordinary width), else one wavefront per order
+AMBI_HD bool all_lane_unit(const UnitIn& U, int lane_cap) { return U.bkp_cap <= lane_cap && U.n_elem <= kMaxNodes; }
+// group memory of one wavefront of the lane form, wave_lds bytes: [head_bytes] DAG + fold-back map | [rows_bytes] transposed orders |
+// [lane_cells x 64] cells | [auto_bytes] the unit's automaton.  AllLaneState: what a wavefront keeps from one chunk to the next.
+struct AllLaneGeom { int32_t head_bytes, rows_bytes, lane_cells, auto_bytes, wave_lds; };
+struct AllLaneState { int loaded = -1; bool staged_ok = false; AutoView SV{}; };   // unit whose head is loaded; its automaton if it fitted auto_bytes
+template <class G>
+AMBI_HD void all_lanes_item(const G& g, const BatchArgs& A, const AllLaneGeom& geom, int64_t c, int pass, uint8_t* work, int lane_cap, AllLaneState& S) {
+    const int u = prefix_find(A.all_off, A.n_units, 2 * c);
+    const UnitIn& U = A.units[u];
+    if (!all_lane_unit(U, lane_cap)) return;   // (long breakpoint paths and wide units: all_wave_item)
+    const int64_t R = unit_out(A.results, u)->num_orders;
+    if (!all_chunk_is_mine(A, c, c - A.all_off[u] / 2, R)) return;   // another rank's chunk
+    if (pass == 1 && all_pass0_last_valid(A, u, R)) return;          // no orientation flip for this unit (LGM.cpp:3691-3695)
+    FirstWork W = carve_first(work, U.n_seg, 8);   // (the wavefront form's breakpoint area is not used here)
+    uint8_t* rows_t = work + geom.head_bytes;
+    cell_t* cells = reinterpret_cast<cell_t*>(rows_t + geom.rows_bytes);
+    // the unit's automaton behind the cells: every lane unranks its own order (K dependent steps), from group memory
+    // instead of 64 scattered walks through L2
+    uint8_t* amem = reinterpret_cast<uint8_t*>(cells) + (size_t)geom.lane_cells * 64 * sizeof(cell_t);
+    if (u != S.loaded) {
+        g.sync();
+        load_first_work(g, A, u, W);
+        const IdealTable T = unit_ideal_table(A, u);
+        const int nI = T.counter[0], nC = T.counter[1];
+        S.staged_ok = 16ll * nI + 4ll * (nI + 1) + 2ll * nC + 16 <= geom.auto_bytes;   // avail and cnt | cbase | child
+        if (S.staged_ok) {
+            uint64_t* av = reinterpret_cast<uint64_t*>(amem);
+            uint64_t* cn = av + nI;
+            int32_t* cb = reinterpret_cast<int32_t*>(cn + nI);
+            uint16_t* ch = reinterpret_cast<uint16_t*>(cb + nI + 1);
+            for (int i = g.tid(); i < nI; i += g.size()) { av[i] = T.a_avail[i]; cn[i] = T.a_cnt[i]; }
+            for (int i = g.tid(); i <= nI; i += g.size()) cb[i] = T.a_cbase[i];
+            for (int i = g.tid(); i < nC; i += g.size()) ch[i] = T.a_child[i];
+            S.SV = AutoView{av, cn, cb, ch, nI};
+        }
+        S.loaded = u;
+        g.sync();
+    }
+    stage_all_chunk_lanes(g, A, u, W, rows_t, cells, c - A.all_off[u] / 2, pass, S.staged_ok ? &S.SV : nullptr);
+    g.sync();
+}
+// `work`: the batch's first-work area + 64 * kFirstRowStride bytes of unranked rows
+template <class G>
+AMBI_HD void all_wave_item(const G& g, const BatchArgs& A, int64_t c, int pass, uint8_t* work, int lane_cap) {
+    const int u = prefix_find(A.all_off, A.n_units, 2 * c);
+    const int64_t R = unit_out(A.results, u)->num_orders;
+    if (pass == 1 && all_pass0_last_valid(A, u, R)) return;   // no orientation flip for this unit (LGM.cpp:3691-3695)
+    const UnitIn& U = A.units[u];
+    if (all_lane_unit(U, lane_cap)) return;                   // taken by all_lanes_item
+    if (!all_chunk_is_mine(A, c, c - A.all_off[u] / 2, R)) return;   // another rank's chunk
+    const bool wide = U.n_elem > kMaxNodes;
+    FirstWork W = carve_first(work, U.n_seg, U.bkp_cap, wide);
+    uint8_t* rows = work + first_work_bytes(U.n_seg, U.bkp_cap, wide);
+    g.sync();
+    load_first_work(g, A, u, W);
+    stage_all_chunk(g, A, u, W, rows, c - A.all_off[u] / 2, pass);
+}
+// The path of order order_idx[j] of unit u (absolute signed ids) to cells[j * stride ...], its length (-1: not valid) to lengths[j].
+// `work`: order_path_work_bytes of group memory.  single: a request for ONE path also tells which row it was made from (diagnostics).
+AMBI_HD int64_t order_path_work_bytes(const UnitIn& U) { return first_work_bytes(U.n_seg, U.bkp_cap, U.n_elem > kMaxNodes) + 4ll * (U.bkp_cap / 2 + 2) + 16; }
+template <class G>
+AMBI_HD void order_path_item(const G& g, const BatchArgs& A, int u, bool forward, const int64_t* order_idx, int64_t j, bool single, int32_t* lengths,
+                             int32_t* cells, int64_t stride, uint8_t* work) {
+    const UnitIn& U = A.units[u];
+    const bool wide = U.n_elem > kMaxNodes;
+    FirstWork W = carve_first(work, U.n_seg, U.bkp_cap, wide);
+    int32_t* offs = reinterpret_cast<int32_t*>(work + first_work_bytes(U.n_seg, U.bkp_cap, wide));
+    load_first_work(g, A, u, W);
+    int L = 0;
+    const int v = eval_indexed(g, A, u, W, order_idx[j], forward, &L);
+    if (single) debug_store_order(g, A, u, W.ord, unit_out(A.results, u)->K);
+    int P = -1;
+    if (v == 1) P = expand_bkp(g, W.bkp, L, (cell_t*)nullptr, (int)(stride < U.path_cap ? stride : U.path_cap), offs, cells + j * stride, U.seg_base);
+    if (g.tid() == 0) lengths[j] = P;
+}
+
+// Host code of --all, every backend.  lane_cap: the longest breakpoint path the lane form takes (env AMBI_ALL_LANES=0: no unit, the wavefront form for all)
+inline int all_lane_cap() { const char* e = ambi_env("AMBI_ALL_LANES"); return (e && atoi(e) == 0) ? 0 : kAllLaneMaxCells; }
+// Lane geometry of a batch, from its maxima.  auto_bytes (env AMBI_ALL_AUTO_LDS, default 0 = the lanes unrank through L2): measured
+// on 4096 bench units 0 / 4096 / 8192 bytes = 561 / 489 / 390 M orders/s -- the lane kernel lives on the number of resident
+// wavefronts (group-memory latency), and every KB of group memory costs some.
+inline AllLaneGeom all_lane_geom(const std::vector<UnitIn>& units, int max_n, int lane_cap) {
+    AllLaneGeom G{};
+    int max_k = 1; G.lane_cells = 8;
+    for (const UnitIn& U : units) {
+        if (all_lane_unit(U, lane_cap) && U.bkp_cap > G.lane_cells) G.lane_cells = U.bkp_cap;
+        if (U.n_elem <= kMaxNodes && U.n_elem > max_k) max_k = U.n_elem;   // (wide units: the wavefront form)
+    }
+    G.head_bytes = (int)((first_work_bytes(max_n, 8) + 15) & ~15);
+    G.rows_bytes = 64 * ((max_k + 3) & ~3);   // transposed orders: one 64-lane row per position
+    { const char* e = ambi_env("AMBI_ALL_AUTO_LDS"); if (e) G.auto_bytes = atoi(e) & ~15; if (G.auto_bytes < 0) G.auto_bytes = 0; }
+    G.wave_lds = (G.head_bytes + G.rows_bytes + G.lane_cells * 64 * (int)sizeof(cell_t) + G.auto_bytes + 15) & ~15;
+    return G;
+}
+// Bitmap plan from the headers: a unit that was reconstructed and whose orders are counted gets 2 x all_words(R) words (pass 0, pass 1).
+// One pool, [bitmaps: words x 8 bytes][flags: U x 4 bytes] -- what ranks merge with ONE reduction when a wide sample's orders are
+// dealt over them (ambi_batch_all_device); pool_words is what to allocate and clear, pool_bytes what the ranks merge.
+struct AllPlan { int64_t words, pool_words, pool_bytes; };
+inline AllPlan all_plan(const UnitOut* hdr, int U, std::vector<int64_t>& off /* [U + 1]: BatchArgs::all_off */) {
+    off.assign((size_t)U + 1, 0);
+    for (int u = 0; u < U; u++) {
+        const bool live = hdr[u].status == ST_OK && hdr[u].num_orders > 0 && hdr[u].num_orders < (int64_t)kCountSat;
+        off[u + 1] = off[u] + (live ? 2 * all_words(hdr[u].num_orders) : 0);
+    }
+    const int64_t words = off[U], flag_words = ((int64_t)U + 1) / 2;
+    return AllPlan{words, words + flag_words + 1, (words + flag_words) * (int64_t)sizeof(uint64_t)};
+}
+// the set bits of one pass's bitmap (nw words) as order indices, ascending
+inline void all_bits_to_indices(const uint64_t* words, int64_t nw, std::vector<int64_t>& out) {
+    out.clear();
+    for (int64_t w = 0; w < nw; w++) for (uint64_t x = words[w]; x; x &= x - 1) out.push_back(w * 64 + __builtin_ctzll(x));
 }
 
 // ---------------------------------------------------------------------------------------------

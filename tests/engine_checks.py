@@ -489,7 +489,9 @@ def check_injected_validity(lib, oracle, workdir):
 def check_all_two_forms(lib, workdir, seeds=range(300, 420)):
     """--all evaluates an order with one THREAD (ambi_eval_lane.hpp, units with a short breakpoint path) or with one
     WAVEFRONT (ambi_eval.hpp): the same valid-order lists, counts, flip decisions and statuses from both, on random
-    decompositions (most orders invalid, both orientations) and on wide synthetic samples (every order valid)."""
+    decompositions (most orders invalid, both orientations) and on wide synthetic samples (every order valid).  The lane
+    form also with the unit's automaton staged in group memory (AMBI_ALL_AUTO_LDS bytes; a unit needs 16 nI + 4 (nI + 1) +
+    2 nC + 16): 16384 holds every unit of this batch, 1024 the small ones only, the others are read through."""
     import os
     from ambigram_amd import synth
     items = []
@@ -500,11 +502,16 @@ def check_all_two_forms(lib, workdir, seeds=range(300, 420)):
         s = synth.make_sample(64, 128, tier, K, seed=8800 + i, imperfect=i % 2)
         lh, sols = s.write(workdir, "tf%d" % i)
         items.append((lh, sols[0]))
-    saved = os.environ.get("AMBI_ALL_LANES")
+    names = ("AMBI_ALL_LANES", "AMBI_ALL_AUTO_LDS")
+    saved = {n: os.environ.get(n) for n in names}
+    forms = {"1": ("1", None), "0": ("0", None), "staged all": ("1", "16384"), "staged small": ("1", "1024")}
     got = {}
     try:
-        for form in ("1", "0"):
-            os.environ["AMBI_ALL_LANES"] = form
+        for form, values in forms.items():
+            for n, v in zip(names, values):
+                os.environ.pop(n, None)
+                if v is not None:
+                    os.environ[n] = v
             for rev in (0, api.FLAG_REVERSED):
                 graphs, b = [], api.Batch(lib)
                 for lh, sol in items:
@@ -520,13 +527,14 @@ def check_all_two_forms(lib, workdir, seeds=range(300, 420)):
                 for g in graphs:
                     g.close()
     finally:
-        os.environ.pop("AMBI_ALL_LANES", None)
-        if saved is not None:
-            os.environ["AMBI_ALL_LANES"] = saved
+        for n in names:
+            os.environ.pop(n, None)
+            if saved[n] is not None:
+                os.environ[n] = saved[n]
     for rev in (0, api.FLAG_REVERSED):
-        a, c = got[("1", rev)], got[("0", rev)]
-        for u, (x, y) in enumerate(zip(a, c)):
-            assert x == y, (rev, u, items[u][0], x[:2], y[:2])
+        for form in forms:
+            for u, (x, y) in enumerate(zip(got[("1", rev)], got[(form, rev)])):
+                assert x == y, (form, rev, u, items[u][0], x[:2], y[:2])
     assert sum(1 for x in got[("1", 0)] if x[0] == 0 and len(x[2]) > 1) >= 2
 
 

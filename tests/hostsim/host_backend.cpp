@@ -139,38 +139,35 @@ class HostSimBackend : public Backend {
         }
     }
 
-    // slow path of the first-valid search (LGM.cpp:3519-3696): the engine's own chunked search (stage_search_chunk /
-    // stage_resolve), the chunks taken in the order AMBI_HOSTSIM_SEARCH_ORDER asks for -- "asc" (default), "desc" (a late
-    // chunk always reports before an early one) or "shuffle" -- which is what concurrency on the GPU amounts to.
+    // slow path of the first-valid search (LGM.cpp:3519-3696): the engine's own chunked search as HipBackend::slow_path queues it --
+    // per pass the slots cleared, the chunk items of ALL pending units (search_item), then stage_resolve per unit -- the chunks
+    // taken in the order AMBI_HOSTSIM_SEARCH_ORDER asks for: "asc" (default), "desc" (a late chunk always reports before an
+    // early one) or "shuffle", which is what concurrency on the GPU amounts to.
     void search_pending() {
         HostGroup g;
         const char* ord = ambi_env("AMBI_HOSTSIM_SEARCH_ORDER");
         const int mode = !ord ? 0 : (!strcmp(ord, "desc") ? 1 : (!strcmp(ord, "shuffle") ? 2 : 0));
-        const int chunk = 16;
+        std::vector<int32_t> pend;
         for (size_t u = 0; u < units_.size(); u++) {
-            UnitOut* out = unit_out(A_.results, (int)u);
-            if (out->status != ST_PENDING) continue;
-            if (out->order_off < 0) continue;   // no table to search (the plan stage had no room): the finish stage behind turns this into ORDERS_CAPACITY, as on the device, where the finish kernels run before the search
-            const UnitIn& U = units_[u];
-            const bool wide = U.n_elem > kMaxNodes;
-            std::vector<uint8_t> work((size_t)first_work_bytes(U.n_seg, U.bkp_cap, wide));
-            FirstWork W = carve_first(work.data(), U.n_seg, U.bkp_cap, wide);
-            load_first_work(g, A_, (int)u, W);
-            const int64_t R = out->num_orders, nchunks = (R + chunk - 1) / chunk;
-            std::vector<int64_t> order((size_t)nchunks);
-            for (int64_t c = 0; c < nchunks; c++) order[(size_t)c] = mode == 1 ? nchunks - 1 - c : c;
-            if (mode == 2) { uint64_t x = 88172645463325252ull + u; for (int64_t c = nchunks - 1; c > 0; c--) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; std::swap(order[(size_t)c], order[(size_t)(x % (uint64_t)(c + 1))]); } }
-            bool fwd = !(A_.flags & FLAG_REVERSED);
-            for (int pass = 0; pass < 2 && out->status == ST_PENDING; pass++) {
-                SearchSlot slot{kSearchNone, kSearchNone};
-                for (int64_t c : order) {
-                    if (c * chunk >= search_limit(slot.found, slot.err_key)) continue;   // as ambi_search_kernel
-                    stage_search_chunk(g, A_, (int)u, W, c * chunk, chunk, fwd, &slot);
-                }
-                std::vector<uint8_t> work2((size_t)first_work_bytes(U.n_seg, U.bkp_cap, wide));
-                stage_resolve(g, A_, (int)u, work2.data(), &slot, fwd, pass);
-                fwd = !fwd;
-            }
+            const UnitOut* out = unit_out(A_.results, (int)u);
+            // order_off < 0: no table to search (the plan stage had no room): the finish stage behind turns this into ORDERS_CAPACITY, as on the device, where the finish kernels run before the search
+            if (out->status == ST_PENDING && out->order_off >= 0) pend.push_back((int32_t)u);
+        }
+        const int np = (int)pend.size(), chunk = 16, lds_first = (int)first_work_bytes(hb_.max_n, hb_.max_bkp, hb_.n_wide > 0);
+        const std::vector<int64_t> coff = search_chunk_prefix(unit_out(A_.results, 0), pend, chunk);
+        const int64_t nchunks = coff[(size_t)np];
+        std::vector<int64_t> order((size_t)nchunks);
+        for (int64_t c = 0; c < nchunks; c++) order[(size_t)c] = mode == 1 ? nchunks - 1 - c : c;
+        if (mode == 2) { uint64_t x = 88172645463325252ull; for (int64_t c = nchunks - 1; c > 0; c--) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; std::swap(order[(size_t)c], order[(size_t)(x % (uint64_t)(c + 1))]); } }
+        std::vector<SearchSlot> slots((size_t)np + 1);
+        std::vector<uint8_t> work((size_t)lds_first);
+        bool fwd = !(A_.flags & FLAG_REVERSED);
+        for (int pass = 0; pass < 2; pass++) {
+            for (SearchSlot& s : slots) s = SearchSlot{kSearchNone, kSearchNone};   // ambi_search_init_kernel
+            const SearchArgs S{pend.data(), coff.data(), slots.data(), np, chunk, fwd ? 1 : 0, lds_first};
+            for (int64_t c : order) search_item(g, A_, S, c, work.data());
+            for (int p = 0; p < np; p++) stage_resolve(g, A_, pend[(size_t)p], work.data(), &slots[(size_t)p], fwd, pass);
+            fwd = !fwd;
         }
     }
 
@@ -260,8 +257,8 @@ class HostSimBackend : public Backend {
         if (flags & FLAG_ALL) compute_all();
         return 0;
     }
-    // --all: the engine's fused unrank + evaluate stage (stage_all_chunk), one 64-order chunk after the other; bitmaps,
-    // counts and flags as the HIP backend keeps them
+    // --all: the engine's fused unrank + evaluate items as the two kernels run them, every chunk of the launch handed to both, in
+    // buffers of exactly the kernels' group-memory sizes; bitmaps, counts and flags as the HIP backend keeps them
     std::vector<std::vector<int64_t>> all_idx_[2];
     std::vector<uint64_t> all_bits_; std::vector<int64_t> all_off_; std::vector<int32_t> all_count_;
     int64_t all_pool_bytes_ = 0; int all_rank_ = 0, all_world_ = 1;
@@ -271,41 +268,26 @@ class HostSimBackend : public Backend {
     void compute_all() {
         HostGroup g;
         const int Un = (int)units_.size();
-        all_idx_[0].assign(Un, {}); all_idx_[1].assign(Un, {});
-        all_off_.assign(Un + 1, 0);
-        for (int u = 0; u < Un; u++) {
-            const UnitOut* out = unit_out(A_.results, u);
-            const bool live = out->status == ST_OK && out->num_orders > 0 && out->num_orders < (int64_t)kCountSat;
-            all_off_[u + 1] = all_off_[u] + (live ? 2 * all_words(out->num_orders) : 0);
-        }
-        // one pool as in the HIP backend: [bitmaps][flags]
-        const int64_t words = all_off_[Un];
-        all_bits_.assign((size_t)(words + (Un + 1) / 2 + 1), 0); all_count_.assign(2 * (size_t)Un, 0);
-        all_pool_bytes_ = (words + (Un + 1) / 2) * 8;
+        const AllPlan plan = all_plan(unit_out(A_.results, 0), Un, all_off_);
+        all_bits_.assign((size_t)plan.pool_words, 0); all_count_.assign(2 * (size_t)Un, 0);
+        all_pool_bytes_ = plan.pool_bytes;
         A_.all_bits = all_bits_.data(); A_.all_off = all_off_.data(); A_.all_count = all_count_.data();
-        A_.all_flags = reinterpret_cast<int32_t*>(all_bits_.data() + words);
+        A_.all_flags = reinterpret_cast<int32_t*>(all_bits_.data() + plan.words);
         A_.all_rank = all_rank_; A_.all_world = all_world_; A_.all_rows_from_table = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            for (int u = 0; u < Un; u++) {
-                if (all_off_[u + 1] == all_off_[u]) continue;
-                const UnitIn& U = units_[u];
-                const int64_t R = unit_out(A_.results, u)->num_orders;
-                if (pass == 1 && all_pass0_last_valid(A_, u, R)) continue;
-                const bool wide = U.n_elem > kMaxNodes;
-                std::vector<uint8_t> work((size_t)first_work_bytes(U.n_seg, U.bkp_cap, wide)), rows(64 * kFirstRowStride);
-                FirstWork W = carve_first(work.data(), U.n_seg, U.bkp_cap, wide);
-                load_first_work(g, A_, u, W);
-                // as the HIP backend: one thread per order for units with a short breakpoint path, the wavefront form otherwise
-                const char* el = ambi_env("AMBI_ALL_LANES");
-                const bool lanes = !(el && atoi(el) == 0) && U.bkp_cap <= kAllLaneMaxCells && !wide;
-                std::vector<cell_t> cells(lanes ? (size_t)U.bkp_cap * 64 : 1);
-                for (int64_t c = 0; c < all_words(R); c++) {
-                    if (!all_chunk_is_mine(A_, all_off_[u] / 2 + c, c, R)) continue;   // another rank's chunk
-                    if (lanes) stage_all_chunk_lanes(g, A_, u, W, rows.data(), cells.data(), c, pass);
-                    else stage_all_chunk(g, A_, u, W, rows.data(), c, pass);
+        const int lane_cap = all_lane_cap();
+        const AllLaneGeom geom = all_lane_geom(units_, hb_.max_n, lane_cap);
+        // the chunks dealt to up to 64 wavefronts as the grid-stride loops deal them: group memory (cleared) and state of its own for each,
+        // so that a unit is met both with nothing loaded and with its head and automaton still there
+        const int64_t chunks = plan.words / 2, nwave = chunks < 64 ? chunks : 64;
+        for (int pass = 0; pass < 2; pass++)
+            for (int64_t w = 0; w < nwave; w++) {
+                std::vector<uint8_t> lane_work((size_t)geom.wave_lds), wave_work((size_t)first_work_bytes(hb_.max_n, hb_.max_bkp, hb_.n_wide > 0) + 64 * kFirstRowStride);
+                AllLaneState state;
+                for (int64_t c = w; c < chunks; c += nwave) {
+                    all_lanes_item(g, A_, geom, c, pass, lane_work.data(), lane_cap, state);
+                    all_wave_item(g, A_, c, pass, wave_work.data(), lane_cap);
                 }
             }
-        }
         finalize_all();
     }
     void finalize_all() {
@@ -315,11 +297,7 @@ class HostSimBackend : public Backend {
             all_finalize_unit(A_, u);
             if (all_off_[u + 1] == all_off_[u]) continue;
             const int64_t nw = all_words(unit_out(A_.results, u)->num_orders);
-            for (int ps = 0; ps < 2; ps++)
-                for (int64_t w = 0; w < nw; w++) {
-                    uint64_t x = all_bits_[(size_t)(all_off_[u] + ps * nw + w)];
-                    while (x) { all_idx_[ps][u].push_back(w * 64 + __builtin_ctzll(x)); x &= x - 1; }
-                }
+            for (int ps = 0; ps < 2; ps++) all_bits_to_indices(all_bits_.data() + all_off_[u] + ps * nw, nw, all_idx_[ps][u]);
         }
     }
     int all_count(int unit, int pass, int64_t* count) override {
@@ -339,21 +317,9 @@ class HostSimBackend : public Backend {
         const auto& v = all_idx_[pass][unit];
         if (first < 0 || count < 0 || first + count > (int64_t)v.size() || stride <= 0) return ST_ERR_BAD_INPUT;
         HostGroup g;
-        const UnitIn& U = units_[unit];
-        const bool wide = U.n_elem > kMaxNodes;
-        std::vector<uint8_t> work((size_t)first_work_bytes(U.n_seg, U.bkp_cap, wide));
-        std::vector<int32_t> offs((size_t)U.bkp_cap / 2 + 2);
-        FirstWork W = carve_first(work.data(), U.n_seg, U.bkp_cap, wide);
-        load_first_work(g, A_, unit, W);
+        std::vector<uint8_t> work((size_t)order_path_work_bytes(units_[unit]));
         const bool fwd0 = !(A_.flags & FLAG_REVERSED), fwd = pass == 0 ? fwd0 : !fwd0;
-        for (int64_t j = 0; j < count; j++) {
-            int L = 0;
-            const int ok = eval_indexed(g, A_, unit, W, v[first + j], fwd, &L);
-            if (count == 1) debug_store_order(g, A_, unit, W.ord, unit_out(A_.results, unit)->K);   // as ambi_order_paths_kernel
-            lengths[j] = ok == 1 ? expand_bkp(g, W.bkp, L, (cell_t*)nullptr, (int)(stride < U.path_cap ? stride : U.path_cap), offs.data(),
-                                              cells + j * stride, U.seg_base)
-                                 : -1;
-        }
+        for (int64_t j = 0; j < count; j++) order_path_item(g, A_, unit, fwd, v.data() + first, j, count == 1, lengths, cells, stride, work.data());
         return 0;
     }
     int wait() override { return 0; }
