@@ -34,6 +34,11 @@ class RunsView(C.Structure):     # ambi_runs_view_t
                 ("run_start", C.POINTER(C.c_int32)), ("run_len", C.POINTER(C.c_int32)), ("run_off", C.POINTER(C.c_int64))]
 
 
+class UnitProfile(C.Structure):     # ambi_unit_profile_t
+    _fields_ = [("status", C.c_int32), ("cells", C.c_int32), ("runs", C.c_int32), ("turns", C.c_int32), ("max_cn", C.c_int32),
+                ("n_uncovered", C.c_int32), ("n_off_target", C.c_int32), ("n_off_input", C.c_int32), ("l1_target", C.c_int64)]
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -96,6 +101,11 @@ def _declare(L):
         "ambi_batch_runs_to_host": (C.c_int, [vp, i32, i32, vp]),
         "ambi_batch_runs_wait": (C.c_int, [vp, i32, _P(RunsView)]),
         "ambi_batch_runs_unit_path": (C.c_int, [vp, i32, i32, pi32, i32]),
+        "ambi_batch_profile": (C.c_int, [vp, i32, vp]),
+        "ambi_batch_profile_wait": (C.c_int, [vp]),
+        "ambi_batch_unit_profile": (C.c_int, [vp, i32, _P(UnitProfile)]),
+        "ambi_batch_unit_path_cn": (C.c_int, [vp, i32, pi32, pi32, i32]),
+        "ambi_batch_profile_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_batch_unit_result": (C.c_int, [vp, i32, _P(UnitResult)]),
         "ambi_batch_unit_path": (C.c_int, [vp, i32, i32, pi32, i32]),
         "ambi_batch_unit_bkp": (C.c_int, [vp, i32, pi32, i32]),
@@ -472,6 +482,32 @@ class Batch:
         self.lib.ambi_batch_runs_unit_path(self.h, slot, u, buf.ctypes.data_as(_P(C.c_int32)), n)
         return buf[:n]
 
+    def profile(self, which=1, stream=None):
+        """Queues the copy-number profile of the last run's paths behind that run (ambi_batch_profile): per segment how often the
+        path (which: 0 getBFB's, 1 the final one) crosses it on either strand, and a summary per unit; `stream` is not blocked."""
+        self._ck(self.lib.ambi_batch_profile(self.h, which, C.c_void_p(stream or 0)), "profile")
+
+    def profile_wait(self):
+        """Waits for the profile in host memory (the run's results are final first); unit_profile / unit_path_cn answer afterwards."""
+        self._ck(self.lib.ambi_batch_profile_wait(self.h), "profile_wait")
+
+    def unit_profile(self, u):
+        r = UnitProfile()
+        self._ck(self.lib.ambi_batch_unit_profile(self.h, u, C.byref(r)), "unit_profile")
+        return {k: getattr(r, k) for k, _ in UnitProfile._fields_}
+
+    def unit_path_cn(self, u, n_seg):
+        """(fwd, rev): int32 arrays of n_seg + 1 traversal counts per LOCAL segment id, slot 0 zero."""
+        fwd = np.zeros(n_seg + 1, np.int32); rev = np.zeros(n_seg + 1, np.int32)
+        self._ck(self.lib.ambi_batch_unit_path_cn(self.h, u, fwd.ctypes.data_as(_P(C.c_int32)), rev.ctypes.data_as(_P(C.c_int32)), n_seg + 1), "unit_path_cn")
+        return fwd, rev
+
+    def profile_device(self):
+        """(address, bytes) of the profile block in device memory (ambi_batch_profile_device), for collectives."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._ck(self.lib.ambi_batch_profile_device(self.h, C.byref(p), C.byref(n)), "profile_device")
+        return p.value or 0, n.value
+
     def pack_paths(self, which, dev_lengths_ptr, dev_cells_ptr, cell_cap, dev_total_ptr, stream=None):
         self._ck(self.lib.ambi_batch_pack_paths(self.h, which, C.c_void_p(dev_lengths_ptr), C.c_void_p(dev_cells_ptr), cell_cap,
                                                  C.c_void_p(dev_total_ptr), C.c_void_p(stream or 0)), "pack_paths")
@@ -643,9 +679,11 @@ def merge_out_juncs(acc, unit_list, increase=True):
 
 
 def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, first_budget=0, order_arena_bytes=-1,
-                       target_lanes=0, keep_orders=False):
+                       target_lanes=0, keep_orders=False, profile=False):
     """Host-side mirror of `Ambigram --op bfb` (localhap.cpp:49-388) with the external `cbc` call replaced by the given
-    .sol files (one per chromosome that reaches the ILP, in order).  Returns a dict shaped like the oracle's dump."""
+    .sol files (one per chromosome that reaches the ILP, in order).  Returns a dict shaped like the oracle's dump.
+    profile=True: every chromosome's dict gains path_cn_fwd / path_cn_rev (traversal counts of the final path per local segment
+    id, slot 0 unused) and profile (the unit's summary), computed on the device (Batch.profile)."""
     g = Graph(lib, lh)
     trx_before = g.trx_before() is not None
     if trx_before:   # PROP I1 / C1: the reference leaves the rebuilt graph in ./new.lh (and says "write seg"); here: a scratch file
@@ -681,6 +719,8 @@ def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, fir
     b.upload(); b.run(flags); b.download()
     # the final paths a second way: in run-length form as the finish kernels leave them for the host (ambi_batch_runs_to_host)
     b.runs_to_host(1, 0); b.runs_wait(0)
+    if profile:
+        b.profile(1); b.profile_wait()
     res = dict(ok=True, err="", log=log, chr=[], paths=[], out_juncs=[], trx_run=False, trx_path=[])
     out_acc = []
     for c in range(g.n_chr):
@@ -701,6 +741,9 @@ def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, fir
                   junc_cn=prep["junc_cn"], seg_cn=prep["seg_cn"], target_cn=prep["target_cn"], inv_junc=prep["inv_junc"],
                   indel_printed=bool(r["indel_printed"]), shortcut=r["status"] == ST_SHORTCUT,
                   infeasible=r["status"] == ST_INFEASIBLE)
+        if profile:
+            fwd, rev = b.unit_path_cn(c, e - s + 1)
+            st.update(path_cn_fwd=fwd, path_cn_rev=rev, profile=b.unit_profile(c))
         if r["status"] == ST_OK:
             pat, loop, succ = b.unit_dag(c, r["n_nodes"])
             st.update(node2pat=pat.tolist(), node2loop=loop.tolist(), succ=[int(x) for x in succ])

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ambi_pack.hpp"
+#include "ambi_profile.hpp"
 
 namespace ambi {
 
@@ -80,6 +81,63 @@ class Backend {
     virtual int all_device(void** ptr, int64_t* bytes) = 0;
     virtual int all_finish() = 0;
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
+
+    // ---- copy-number profile of every unit's path (ambi_profile.hpp; which: 0 getBFB, 1 after indelBFB) ----
+    // profile() queues the profile of the last run's results behind that run, profile_wait() waits for it in host memory; the
+    // getters below then answer from that copy.  The default runs stage_path_profile on the host over the downloaded blob (the
+    // host simulation); the HIP engine overrides both with ambi_path_profile_kernel and never reaches it.
+    // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
+    void profile_bind(const HostBatch* hb) { prof_hb_ = hb; prof_view_ = nullptr; }
+    virtual int profile(int which, void* stream) {
+        (void)stream;
+        if (!prof_hb_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
+        std::vector<uint8_t> blob;
+        if (int rc = download(blob)) return rc;
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        prof_bytes_ = profile_block_layout(units, prof_off_);
+        prof_blob_.assign((size_t)prof_bytes_, 0);
+        const char* e = ambi_env("AMBI_PROFILE_WINDOW");
+        const int window = profile_window(prof_hb_->max_n, e ? atoi(e) : 0);
+        std::vector<int32_t> bins((size_t)(2 * window));
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++) profile_unit(g, units.data(), blob.data(), (int)u, which, window, bins.data(), prof_blob_.data(), prof_off_.data());
+        prof_view_ = nullptr;
+        return 0;
+    }
+    virtual int profile_wait() {
+        if (prof_blob_.empty()) return ST_ERR_BAD_INPUT;
+        prof_view_ = prof_blob_.data();
+        return 0;
+    }
+    // the profile block where the collectives of the caller can read it (device memory of the HIP engine), valid after profile_wait()
+    virtual int profile_device(void** ptr, int64_t* bytes) {
+        if (!prof_view_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = prof_blob_.data();
+        if (bytes) *bytes = prof_bytes_;
+        return 0;
+    }
+    int profile_summary(int unit, UnitProfile* out) const {
+        if (!prof_view_ || unit < 0 || unit >= (int)prof_off_.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitProfile*>(prof_view_)[unit];
+        return 0;
+    }
+    int profile_counts(int unit, int32_t* fwd, int32_t* rev, int cap) const {   // n + 1 counts each; returns n + 1
+        if (!prof_view_ || !prof_hb_ || unit < 0 || unit >= (int)prof_off_.size()) return ST_ERR_BAD_INPUT;
+        const int n = prof_hb_->units[(size_t)unit].n_seg;
+        if (cap < n + 1) return ST_ERR_BAD_INPUT;
+        const uint8_t* p = prof_view_ + prof_off_[(size_t)unit];
+        if (fwd) memcpy(fwd, p, sizeof(int32_t) * (size_t)(n + 1));
+        if (rev) memcpy(rev, p + profile_rev_off(n), sizeof(int32_t) * (size_t)(n + 1));
+        return n + 1;
+    }
+
+  protected:
+    const HostBatch* prof_hb_ = nullptr;
+    std::vector<int64_t> prof_off_;      // byte offset of every unit's fwd array in the profile block (profile_block_layout)
+    int64_t prof_bytes_ = 0;             // bytes of the block
+    const uint8_t* prof_view_ = nullptr; // the block in host memory once profile_wait() has returned (nullptr: no profile to read)
+  private:
+    std::vector<uint8_t> prof_blob_;     // the default implementation's block
 };
 
 Backend* make_backend();   // defined by the linked backend

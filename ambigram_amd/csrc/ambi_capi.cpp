@@ -114,6 +114,8 @@ struct ambi_batch {
     RunsView runs[2] = {};                              // ambi_batch_runs_wait: what arrived in the slot
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
+    bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
+    bool profiled = false;    // ambi_batch_profile_wait has returned for the last run: the profile getters answer
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
 };
 
@@ -404,15 +406,19 @@ int ambi_batch_upload(ambi_batch_t* b) {
     if (!b) return AMBI_ERR_ARG;
     if (b->hb.units.empty() || !b->shards.empty()) return AMBI_ERR_STATE;
     b->hb.finalize();
+    b->be->profile_bind(&b->hb);
     int rc = b->be->upload(b->hb, b->cfg);
     if (rc == 0) b->uploaded = true;
+    b->ran = false; b->profiled = false;
     return rc;
 }
 int ambi_batch_run(ambi_batch_t* b, uint32_t flags, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!b->uploaded) return AMBI_ERR_STATE;
-    b->downloaded = false; b->mail_view = false;
-    return b->be->run(flags, hip_stream);
+    b->downloaded = false; b->mail_view = false; b->profiled = false;
+    const int rc = b->be->run(flags, hip_stream);
+    if (rc == 0) b->ran = true;
+    return rc;
 }
 int ambi_batch_wait(ambi_batch_t* b) { return b ? b->be->wait() : AMBI_ERR_ARG; }
 int ambi_batch_wait_results(ambi_batch_t* b) { return b ? b->be->wait_results() : AMBI_ERR_ARG; }
@@ -459,6 +465,7 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
             s->device = devs[k];
             s->hb.ideal_cap = b->hb.ideal_cap;
             s->be.reset(make_backend());
+            s->be->profile_bind(&s->hb);
             b->shards.push_back(std::move(s));
         }
         for (int u = 0; u < U; u++) {
@@ -471,7 +478,7 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
         for (auto& s : b->shards) s->hb.finalize();
     }
     b->hb.finalize();
-    b->downloaded = false; b->mail_view = false; b->sharded_ready = false;
+    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled = false;
     // every share on its own (resident) thread, the first one too: set_device changes the current device of the thread that calls it,
     // and the caller's thread keeps the device it had.  Nothing is merged: the getters read a unit where its share left it.
     for (auto& s : b->shards) s->start(flags, &b->cfg);
@@ -614,6 +621,48 @@ int ambi_batch_unit_path(const ambi_batch_t* b, int32_t unit, int32_t which, int
     int len = which ? h->path_indel_len : h->path_len;
     if (out) for (int i = 0; i < len && i < cap; i++) out[i] = abs_cell(src[i], U.seg_base);   // the blob holds local ids
     return len;
+}
+// ---- copy-number profile of the paths (ambi_profile.hpp; localhap.cpp:318-351) ----
+int ambi_batch_profile(ambi_batch_t* b, int32_t which, void* hip_stream) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
+    if (which < 0 || which > 1) return AMBI_ERR_ARG;
+    b->profiled = false;
+    if (!b->sharded_ready) return b->be->profile(which, hip_stream);
+    for (auto& s : b->shards)   // every share on its own stream (the backend selects its device for the call)
+        if (!s->units.empty()) { if (int rc = s->be->profile(which, s->be->own_stream())) return rc; }
+    return 0;
+}
+int ambi_batch_profile_wait(ambi_batch_t* b) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
+    if (!b->sharded_ready) { if (int rc = b->be->profile_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
+    else for (auto& s : b->shards)
+        if (!s->units.empty()) { if (int rc = s->be->profile_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
+    b->profiled = true;
+    return 0;
+}
+int ambi_batch_unit_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_profile_t* out) {
+    if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled) return AMBI_ERR_STATE;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    static_assert(sizeof(ambi_unit_profile_t) == sizeof(UnitProfile), "ambi_unit_profile_t is ambi::UnitProfile");
+    return be->profile_summary(local, reinterpret_cast<UnitProfile*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_unit_path_cn(const ambi_batch_t* b, int32_t unit, int32_t* fwd, int32_t* rev, int32_t cap) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled) return AMBI_ERR_STATE;
+    if (cap < b->hb.units[unit].n_seg + 1) return AMBI_ERR_ARG;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    const int rc = be->profile_counts(local, fwd, rev, cap);
+    return rc < 0 ? AMBI_ERR_STATE : rc;
+}
+int ambi_batch_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!b->profiled || b->sharded_ready) return AMBI_ERR_STATE;
+    return b->be->profile_device(dev_ptr, bytes) ? AMBI_ERR_STATE : 0;
 }
 int ambi_batch_unit_bkp(const ambi_batch_t* b, int32_t unit, int32_t* out, int32_t cap) {
     const UnitOut* h = header(b, unit);

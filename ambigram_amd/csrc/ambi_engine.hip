@@ -14,6 +14,8 @@
 //   ambi_search/resolve_kernel    1 wave  / chunk of orders (only for units whose scan budget ran out)
 //   ambi_finish_kernel            1 block / unit   bkp -> path (LDS int16), indelBFB, output junctions
 //   ambi_pack_*                   optional end-of-batch packing of the paths for an RCCL gather
+//   ambi_path_profile_kernel      1 block / unit   on request: per-segment traversal counts of the path + summary
+//                                                  (ambi_profile.hpp)                              <- read-bound, 2 bytes / cell
 // Every kernel is a wrapper around the stage functions of ambi_stages.hpp, the four table kernels (blocks_build,
 // enumerate_blocks, enumerate, enumerate_wide) included: their logic is under that file's stage_enumerate banner.
 #include <hip/hip_runtime.h>
@@ -661,6 +663,18 @@ __global__ __launch_bounds__(256) void ambi_pack_runs_write_kernel(BatchArgs A, 
         __syncthreads();
     }
 }
+// ---- copy-number profile of the paths (ambi_profile.hpp; launched by HipBackend::profile only) ----
+// One workgroup of 256 threads per unit, grid-stride over the units.  Group memory: 256 bytes for the group's reductions, then
+// the two difference arrays of `window` segments.
+constexpr int kProfileThreads = 256, kProfileScratchBytes = 256;
+__global__ __launch_bounds__(kProfileThreads) void ambi_path_profile_kernel(BatchArgs A, int which, int window, uint8_t* block, const int64_t* off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    int32_t* bins = reinterpret_cast<int32_t*>(ambi_lds + kProfileScratchBytes);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        profile_unit(g, A.units, A.results, u, which, window, bins, block, off);
+        __syncthreads();
+    }
+}
 // one wavefront per run
 __global__ __launch_bounds__(256) void ambi_expand_runs_kernel(const int32_t* run_start, const int32_t* run_len, const int64_t* cell_off, int64_t n_runs,
                                                                int32_t* cells, int64_t cap) {
@@ -767,12 +781,17 @@ struct Lease {
     uint8_t* h_runs[2] = {nullptr, nullptr}; int64_t h_runs_bytes[2] = {0, 0};
     hipStream_t run_stream = nullptr;   // own_stream(): for callers without a stream (ambi_batch_run_sharded's shares)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
+    // copy-number profile (HipBackend::profile): the profile block [UnitProfile[U]][per unit fwd, rev] with the units' offsets behind it,
+    // its pinned twin, and three events (the run's stream reached / kernel done / block arrived)
+    uint8_t* d_prof = nullptr; int64_t d_prof_bytes = 0;
+    uint8_t* h_prof = nullptr; int64_t h_prof_bytes = 0;
+    hipEvent_t ev_prof_src = nullptr, ev_prof_packed = nullptr, ev_prof_done = nullptr;
     std::vector<TimingEvents> evs;
     long uses = 0;
     int32_t seq = 0;   // run sequence numbers (the kernels report completion by storing the run's number into a pinned word)
 };
 // what stays cached in a lease between batches (larger blocks go back to the device when the batch is destroyed)
-constexpr int64_t kKeepBlock = 64ll << 20, kKeepArena = 256ll << 20, kKeepCells = 64ll << 20, kKeepStage = 16ll << 20, kKeepMail = 8ll << 20, kKeepRuns = 16ll << 20;
+constexpr int64_t kKeepBlock = 64ll << 20, kKeepArena = 256ll << 20, kKeepCells = 64ll << 20, kKeepStage = 16ll << 20, kKeepMail = 8ll << 20, kKeepRuns = 16ll << 20, kKeepProfile = 16ll << 20;
 
 class DevicePool {
     std::mutex mu_;                       // the free list and the contexts' table: never held during a probe
@@ -1064,6 +1083,8 @@ class HipBackend : public Backend {
         if (!lease_) return;
         if (inflight_) { (void)hipStreamSynchronize(stream_); inflight_ = false; }
         for (hipStream_t s : {side_.lean, side_.full, side_.scan, lease_->copy_stream, lease_->run_stream}) if (s) (void)hipStreamSynchronize(s);
+        if (prof_queued_ && prof_stream_ != stream_) (void)hipStreamSynchronize(prof_stream_);   // (a profile queued on another stream than the run's)
+        prof_queued_ = false;
         (void)hipGetLastError();
     }
     // guard words around the pinned words the kernels write through (always) and around the path areas of the direct
@@ -1105,11 +1126,14 @@ class HipBackend : public Backend {
                 if (L->d_runs_bytes[k] > kKeepRuns) { (void)hipFree(L->d_runs[k]); L->d_runs[k] = nullptr; L->d_runs_bytes[k] = 0; }
                 if (L->h_runs_bytes[k] > kKeepRuns) { (void)hipHostFree(L->h_runs[k]); L->h_runs[k] = nullptr; L->h_runs_bytes[k] = 0; }
             }
+            if (L->d_prof_bytes > kKeepProfile) { (void)hipFree(L->d_prof); L->d_prof = nullptr; L->d_prof_bytes = 0; }
+            if (L->h_prof_bytes > kKeepProfile) { (void)hipHostFree(L->h_prof); L->h_prof = nullptr; L->h_prof_bytes = 0; }
             lease_ = nullptr;
             DevicePool::get().release(L);
         }
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
+        prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
         device_ = -1;
     }
 
@@ -1174,6 +1198,7 @@ class HipBackend : public Backend {
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -30;   // AMBI_ERR_NO_DEVICE: no CPU fallback
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
+        prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
         express_ = false;
         shared_units_ = -1;
         hbp_ = &hb_in; cfg_ = cfg;
@@ -2124,6 +2149,76 @@ class HipBackend : public Backend {
         out->headers = runs_hdr_[slot] ? L->h_runs[slot] + ((words * 4 + 15) & ~int64_t(15)) : nullptr;
         out->bytes = (4 + 2 * U + 2 * out->n_runs) * 4 + (runs_hdr_[slot] ? U * (int64_t)sizeof(UnitOut) : 0);   // what the payload needs (the copy moves the slot's capacity)
         out->copied_bytes = words * 4 + (runs_hdr_[slot] ? U * (int64_t)sizeof(UnitOut) : 0);
+        return 0;
+    }
+    // ---- copy-number profile of the paths (ambi_profile.hpp) ----
+    // profile() queues ambi_path_profile_kernel on `stream` behind everything that writes the result blob in the last run -- the
+    // caller's stream of that run, and explicitly the events "results complete" of the side streams (lean / list finish kernels,
+    // direct edit + full launch) and of the express kernel -- then ONE device-to-host copy of the profile block on the lease's copy
+    // stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes the results final (wait():
+    // the first run done again with a larger arena, units finished by the parallel search) and, if that moved the results' epoch
+    // after the kernel was queued, queues kernel and copy once more.
+    bool prof_queued_ = false, prof_laid_out_ = false;
+    int prof_which_ = 1; int64_t prof_epoch_ = -1; hipStream_t prof_stream_ = nullptr;
+    int64_t* d_prof_off_ = nullptr;
+    int profile_queue(int which, hipStream_t s) {
+        Lease* L = lease_;
+        const int64_t U = (int64_t)hb().units.size();
+        if (!prof_laid_out_) {
+            prof_bytes_ = profile_block_layout(hb().units, prof_off_);
+            const int64_t total = prof_bytes_ + U * (int64_t)sizeof(int64_t);   // (prof_bytes_ is a multiple of 16)
+            if (int rc = lease_device_block(&L->d_prof, &L->d_prof_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&L->h_prof, nullptr, &L->h_prof_bytes, total)) return rc;
+            if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
+            for (hipEvent_t* e : {&L->ev_prof_src, &L->ev_prof_packed, &L->ev_prof_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
+            memcpy(L->h_prof + prof_bytes_, prof_off_.data(), (size_t)U * sizeof(int64_t));
+            d_prof_off_ = reinterpret_cast<int64_t*>(L->d_prof + prof_bytes_);
+            HIP_CK(hipMemcpyAsync(d_prof_off_, L->h_prof + prof_bytes_, (size_t)U * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            prof_laid_out_ = true;
+        }
+        // behind the run: its caller's stream has waited for every side stream at the end of run(); the events themselves once more for
+        // a caller that profiles on another stream
+        if (s != stream_) { HIP_CK(hipEventRecord(L->ev_prof_src, stream_)); HIP_CK(hipStreamWaitEvent(s, L->ev_prof_src, 0)); }
+        if (overlap_back_) {
+            HIP_CK(hipStreamWaitEvent(s, ev_back_, 0));
+            if (direct_n_ > 0) HIP_CK(hipStreamWaitEvent(s, ev_full_, 0));
+        }
+        if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
+        const char* e = ambi_env("AMBI_PROFILE_WINDOW");
+        const int window = profile_window(hb().max_n, e ? atoi(e) : 0);
+        const int lds = kProfileScratchBytes + (int)profile_bins_bytes(window);
+        if (prof_queued_) HIP_CK(hipStreamWaitEvent(s, L->ev_prof_done, 0));   // (an earlier profile nobody waited for: its copy still reads the block)
+        const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
+        hipLaunchKernelGGL(ambi_path_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, window, L->d_prof, (const int64_t*)d_prof_off_);
+        HIP_CK(hipGetLastError());
+        HIP_CK(hipEventRecord(L->ev_prof_packed, s));
+        HIP_CK(hipStreamWaitEvent(L->copy_stream, L->ev_prof_packed, 0));
+        HIP_CK(hipMemcpyAsync(L->h_prof, L->d_prof, (size_t)prof_bytes_, hipMemcpyDeviceToHost, L->copy_stream));
+        HIP_CK(hipEventRecord(L->ev_prof_done, L->copy_stream));
+        prof_which_ = which; prof_stream_ = s; prof_epoch_ = epoch_; prof_queued_ = true;
+        prof_view_ = nullptr;
+        return 0;
+    }
+    int profile(int which, void* stream) override {
+        DeviceGuard dg_(device_);
+        if (!ran_ || !lease_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
+        prof_hb_ = hbp_;
+        return profile_queue(which, (hipStream_t)stream);
+    }
+    int profile_wait() override {
+        DeviceGuard dg_(device_);
+        if (!prof_queued_) return ST_ERR_BAD_INPUT;
+        if (int rc = wait()) return rc;
+        if (epoch_ != prof_epoch_) { if (int rc = profile_queue(prof_which_, prof_stream_)) return rc; }
+        HIP_CK(hipEventSynchronize(lease_->ev_prof_done));
+        prof_view_ = lease_->h_prof;
+        return 0;
+    }
+    int profile_device(void** ptr, int64_t* bytes) override {
+        if (!prof_view_ || !lease_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->d_prof;
+        if (bytes) *bytes = prof_bytes_;
         return 0;
     }
     int copy_orders(int unit, int64_t first, int64_t count, uint8_t* out) override {

@@ -243,12 +243,15 @@ int run_sc_bfb(Args& A) {
 // through its own ILP / solver stage in turn, then the chromosomes of ALL samples are reconstructed as ONE batch -- and
 // --devices N|all deals that batch over several GPUs (ambi_batch_run_sharded: one host thread per device, round-robin).
 // Every sample's stdout lines and side-file rows are what a run on that sample alone prints, in sample order.
+// --cn_profile <file> (what the reference's commented-out CN.txt writer meant to report, localhap.cpp:318-351): after the run, one
+// tab-separated row per segment -- sample, chromosome name, segment id, start, end, input CN, target CN, forward count, reverse
+// count, count - target -- from the device's copy-number profile of the final paths (ambi_batch_profile); stdout is unchanged.
 struct Sample {
     std::string lh;
     ambi_graph_t* g = nullptr;
     int32_t n_seg = 0, n_junc = 0, n_chr = 0, ins_mode = 0, con_mode = 0;
     char main_chr[256] = {0};
-    std::vector<double> cn_all;
+    std::vector<double> cn_all, cn_file;   // cn_file: the copy numbers as the .lh gives them (cn_all takes getIndelBias' edits)
     std::vector<int32_t> seg_start, seg_end;
     std::vector<std::string> head;       // lines the reference prints before a chromosome's path lines
     std::vector<int> unit;               // chromosome -> unit of the reconstruct batch
@@ -262,6 +265,7 @@ int run_bfb(Args& A) {
     const std::string prefix = A.kv["lp_prefix"], juncs = A.kv.count("juncdb") ? A.kv["juncdb"] : "";
     const bool junc_info = truthy(A.kv["junc_info"]), reversed = truthy(A.kv["reversed"]), all = truthy(A.kv["all"]);
     const double solver_timeout = A.kv.count("solver_timeout") ? atof(A.kv["solver_timeout"].c_str()) : 0;   // extension: seconds, 0 = none
+    const std::string cn_profile = A.kv.count("cn_profile") ? A.kv["cn_profile"] : "";
     int n_devices = 0;                   // 0: one device, the classic path; > 0: that many; -1: all visible
     std::vector<int32_t> device_list;    // or an explicit list of ordinals "0,1,1" (an ordinal may repeat: several shares on one device)
     if (A.kv.count("devices")) {
@@ -293,6 +297,14 @@ int run_bfb(Args& A) {
         if (rc != 0) return die(std::string("input error: ") + ambi_error_string(rc));
         ambi_graph_t* g = S.g;
         size_t printed = 0;
+        if (!cn_profile.empty()) {
+            // PROP I1 / C1 / I2 / C2: the printed paths are rebuilt on the host (virusBFB, translocationBFB) and are not the device's paths
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << "--cn_profile: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
+                return 2;
+            }
+        }
         // PROP I1 / C1 (TRX-BFB, localhap.cpp:79-88): the graph has been rebuilt while loading; the reference leaves it in ./new.lh
         S.trx_before = ambi_graph_trx_before(g, nullptr, 0) > 0;
         if (S.trx_before) { (void)ambi_graph_write_lh(g, "./new.lh"); if ((rc = ambi_graph_trx_original(g, &S.g_file)) != 0) return die(ambi_error_string(rc)); }
@@ -302,6 +314,7 @@ int run_bfb(Args& A) {
         ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
         S.cn_all.resize(S.n_seg); S.seg_start.resize(S.n_seg); S.seg_end.resize(S.n_seg);
         ambi_graph_segments(g, nullptr, nullptr, S.seg_start.data(), S.seg_end.data(), nullptr, S.cn_all.data());
+        S.cn_file = S.cn_all;
         S.head.assign(S.n_chr, ""); S.unit.assign(S.n_chr, -1);
         // Two batches, every chromosome a unit:
         //   probe batch   -- localhap.cpp:136-170 for all chromosomes of the sample at once: junction CNs, bias, getIndelBias, shortcut;
@@ -367,6 +380,27 @@ int run_bfb(Args& A) {
     if (n_devices != 0) rc = ambi_batch_run_sharded(b, flags, device_list.empty() ? nullptr : device_list.data(), n_devices);
     else if ((rc = ambi_batch_upload(b)) == 0 && (rc = ambi_batch_run(b, flags, nullptr)) == 0) rc = ambi_batch_download(b);
     if (rc != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+    if (!cn_profile.empty()) {
+        if ((rc = ambi_batch_profile(b, 1, nullptr)) != 0 || (rc = ambi_batch_profile_wait(b)) != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+        FILE* pf = fopen(cn_profile.c_str(), "w");
+        if (!pf) return die("Cannot open file " + cn_profile);
+        for (Sample& S : samples)
+            for (int c = 0; c < S.n_chr; c++) {
+                int32_t s, e;
+                ambi_graph_chromosome(S.g, c, &s, &e);
+                const int n = e - s + 1;
+                std::vector<int32_t> fwd(n + 1), rev(n + 1), target(n + 1);
+                if ((rc = ambi_batch_unit_path_cn(b, S.unit[c], fwd.data(), rev.data(), n + 1)) < 0 ||
+                    (rc = ambi_batch_unit_prepare(b, S.unit[c], nullptr, nullptr, target.data(), nullptr)) < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                for (int i = 1; i <= n; i++) {
+                    const int id = s + i - 1;
+                    char nm[256]; ambi_graph_chrom_name(S.g, id, nm, sizeof(nm));
+                    fprintf(pf, "%s\t%s\t%d\t%d\t%d\t%g\t%d\t%d\t%d\t%d\n", S.lh.c_str(), nm, id, S.seg_start[id - 1], S.seg_end[id - 1], S.cn_file[id - 1],
+                            target[i], fwd[i], rev[i], fwd[i] + rev[i] - target[i]);
+                }
+            }
+        fclose(pf);
+    }
     int refused_total = 0;
     for (Sample& S : samples) {
         ambi_graph_t* g = S.g;
@@ -502,8 +536,10 @@ int main(int argc, char** argv) {
     Args A = parse(argc, argv);
     if (A.help) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
-                     "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>]\n"
-                     "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n";
+                     "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>]\n"
+                     "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
+                     "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
+                     "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n";
         return 0;
     }
     const std::string op = A.kv.count("op") ? A.kv["op"] : "";
