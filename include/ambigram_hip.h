@@ -221,7 +221,9 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
 int ambi_batch_device_results(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
 /* Packs the final paths of all units into caller-provided DEVICE buffers: lengths[n_units] (int32) and the
  * concatenation of the paths (int32, absolute signed ids) -- the payload of the end-of-batch RCCL gather.
- * which: 0 = getBFB path, 1 = path after indelBFB.  total_cells receives the number of cells written (device int64). */
+ * which: 0 = getBFB path, 1 = path after indelBFB.  dev_total_cells receives the number of cells the paths have (device
+ * int64), whatever cell_cap is; dev_lengths is always complete.  Capacity rule: the cells are clamped one by one -- of the
+ * concatenation exactly the first min(cell_cap, total) cells are written, and no word of dev_cells at or past cell_cap. */
 int ambi_batch_pack_paths(ambi_batch_t* b, int32_t which, int32_t* dev_lengths, int32_t* dev_cells, int64_t cell_cap,
                           int64_t* dev_total_cells, void* hip_stream);
 
@@ -230,7 +232,10 @@ int ambi_batch_pack_paths(ambi_batch_t* b, int32_t which, int32_t* dev_lengths, 
  * thousands of cells, so the exchange moves kilobytes instead of megabytes per sample and the receiving rank expands
  * the runs in its own memory (ambi_expand_runs).  Per unit: dev_lengths[u] = cells, dev_run_counts[u] = runs; the runs
  * of all units follow each other in dev_run_start / dev_run_len (int32 each, at most run_cap).  dev_totals (device,
- * int64[2]) receives {runs, cells}. */
+ * int64[2]) receives {runs, cells} the paths have, whatever run_cap is; dev_lengths and dev_run_counts are always complete.
+ * Capacity rule: a unit is written whole or not at all -- unit u, whose runs start at off = the sum of the run counts before
+ * it, is written when off + dev_run_counts[u] <= run_cap; of any other unit not one word is written, nor any word at or past
+ * run_cap (so run_cap = 0 only counts, and a caller that finds totals[0] > run_cap packs again with room for all). */
 int ambi_batch_pack_runs(ambi_batch_t* b, int32_t which, int32_t* dev_lengths, int32_t* dev_run_counts, int32_t* dev_run_start,
                          int32_t* dev_run_len, int64_t run_cap, int64_t* dev_totals, void* hip_stream);
 /* The final paths of every unit ON THE HOST, in that run-length form, without stopping the stream (the reference

@@ -355,9 +355,13 @@ class HostSimBackend : public Backend {
             const rcell_t* src = reinterpret_cast<const rcell_t*>(results_.data() + U.res_off + ((which && h->path_ind_stored) ? L.path_ind : L.path));
             lengths[u] = len;
             int n = 0;
-            for (int i = 0; i < len; i++) {
-                if (i == 0 || src[i] != src[i - 1] + 1) { if (off + n < cap) { run_start[off + n] = abs_cell(src[i], U.seg_base); run_len[off + n] = 0; } n++; }
-                if (off + n - 1 < cap) run_len[off + n - 1]++;
+            for (int i = 0; i < len; i++) n += (i == 0 || src[i] != src[i - 1] + 1) ? 1 : 0;
+            if (off + n <= cap) {   // (as ambi_pack_runs_write_kernel: a unit whose runs do not all fit is not written at all)
+                int64_t k = off - 1;
+                for (int i = 0; i < len; i++) {
+                    if (i == 0 || src[i] != src[i - 1] + 1) { k++; run_start[k] = abs_cell(src[i], U.seg_base); run_len[k] = 0; }
+                    run_len[k]++;
+                }
             }
             run_counts[u] = n;
             off += n; cells += len;
