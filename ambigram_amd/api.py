@@ -81,6 +81,7 @@ def _declare(L):
         "ambi_graph_trx_original": (C.c_int, [vp, _P(vp)]),
         "ambi_graph_trx_restore": (C.c_int, [vp, pi32, i32, i32, C.c_char_p, i64, pi64]),
         "ambi_ilp_build_sc": (C.c_int, [vp, i32, i32, pd, pd, _P(vp)]),
+        "ambi_ilp_build_sc_device": (C.c_int, [vp, i32, i32, pd, pd, _P(C.c_float), _P(vp)]),
         "ambi_batch_add_unit": (C.c_int, [vp, i32, i32, pd, i32, pi32, pi32, pi8, pi8, pd, i32, pi32, pi32, pi32, pi32, i32, i32]),
         "ambi_batch_size": (C.c_int, [vp, pi32]),
         "ambi_batch_configure": (C.c_int, [vp, i64, i32, i32, i32]),
@@ -930,13 +931,20 @@ class IlpModel:
         self._sizes()
 
     @classmethod
-    def joint(cls, lib, graph0, chr_, seg_cn, fold_cn):
-        """Joint model of `--op sc_bfb` (BFB_ILP_SC, LGM.cpp:4754-5093): seg_cn / fold_cn are G x n arrays (graph-major)."""
+    def joint(cls, lib, graph0, chr_, seg_cn, fold_cn, device=False):
+        """Joint model of `--op sc_bfb` (BFB_ILP_SC, LGM.cpp:4754-5093): seg_cn / fold_cn are G x n arrays (graph-major).
+        device=True: the entries are written by ambi_ilp_fill_kernel on the GPU (kernel_ms = its mean device time)."""
         self = cls.__new__(cls)
         self.lib, self.h, self.kernel_ms = lib, C.c_void_p(), None
         sc = np.ascontiguousarray(seg_cn, np.float64)
         fc = np.ascontiguousarray(fold_cn, np.float64)
-        rc = lib.ambi_ilp_build_sc(graph0.h, chr_, sc.shape[0], sc.ctypes.data_as(_P(C.c_double)), fc.ctypes.data_as(_P(C.c_double)), C.byref(self.h))
+        if device:
+            ms = C.c_float()
+            rc = lib.ambi_ilp_build_sc_device(graph0.h, chr_, sc.shape[0], sc.ctypes.data_as(_P(C.c_double)), fc.ctypes.data_as(_P(C.c_double)),
+                                              C.byref(ms), C.byref(self.h))
+            self.kernel_ms = ms.value
+        else:
+            rc = lib.ambi_ilp_build_sc(graph0.h, chr_, sc.shape[0], sc.ctypes.data_as(_P(C.c_double)), fc.ctypes.data_as(_P(C.c_double)), C.byref(self.h))
         if rc != 0:
             raise AmbiError(lib, rc, "ilp_build_sc")
         self._sizes()

@@ -885,6 +885,20 @@ int ambi_ilp_build_sc(const ambi_graph_t* g0, int32_t chr, int32_t n_graphs, con
     *out = p;
     return 0;
 }
+int ambi_ilp_build_sc_device(const ambi_graph_t* g0, int32_t chr, int32_t n_graphs, const double* seg_cn, const double* fold_cn, float* kernel_ms,
+                             ambi_ilp_t** out) {
+    if (out) *out = nullptr;
+    if (!g0 || !seg_cn || !fold_cn || !out || n_graphs < 1 || chr < 0 || chr >= g0->g.n_chr()) return AMBI_ERR_ARG;
+    const int s = g0->g.source_ids[chr], e = g0->g.sink_ids[chr];
+    std::unique_ptr<ambi_ilp> p(new ambi_ilp());
+    std::vector<ambi::IlpRowDesc> rows;
+    if (!ambi::build_bfb_ilp_sc_rows(s, e, n_graphs, seg_cn, fold_cn, p->m, rows)) return AMBI_ERR_ARG;   // beyond the descriptor's limits
+    int rc = ambi::backend_ilp_fill(rows.data(), (int64_t)rows.size(), p->m.row_ptr.data(), s, e, nullptr, nullptr, 0, p->m.col.data(), p->m.val.data(),
+                                    kernel_ms);
+    if (rc) return rc;
+    *out = p.release();
+    return 0;
+}
 void ambi_ilp_destroy(ambi_ilp_t* p) { delete p; }
 int ambi_ilp_sizes(const ambi_ilp_t* p, int64_t* n_rows, int64_t* nnz, int32_t* n_cols, int32_t* n_int) {
     if (!p) return AMBI_ERR_ARG;

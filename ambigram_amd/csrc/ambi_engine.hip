@@ -2418,6 +2418,11 @@ Backend* make_backend() { return new HipBackend(); }
 #define AMBI_ILP_PER 4
 #endif
 constexpr int kIlpChunk = 1024, kIlpStage = kIlpChunk + 4, kIlpPer = AMBI_ILP_PER, kIlpThreads = kIlpChunk / kIlpPer;   // entries per thread (4 or 8), threads per workgroup
+static_assert(kIlpPer == 4 || kIlpPer == 8, "the 16-byte stores below take the entries of a thread four columns / two coefficients at a time");
+// JOINT: the rows may be those of the joint model of `--op sc_bfb` (BFB_ILP_SC; descriptor layout in ambi_ilp_rows.hpp) -- the same chunked
+// fill with the column fix-up per entry; its linking rows are three entries long, so the entry-by-entry branch serves them (under 1 % of the
+// entries).  JOINT = false is the single-graph kernel, instruction for instruction what it was before the joint rows existed.
+template <bool JOINT>
 __global__ __launch_bounds__(kIlpThreads) void ambi_ilp_fill_kernel(const IlpRowDesc* rows, const int64_t* row_ptr, const int32_t* chunk_row, int64_t nnz, IlpGeom G,
                                                             const int32_t* lit_col, const double* lit_val, int32_t* col, double* val) {
     __shared__ int32_t rel[kIlpStage];          // row offsets relative to the chunk's first position (rows are far shorter than 2^31)
@@ -2445,7 +2450,7 @@ __global__ __launch_bounds__(kIlpThreads) void ambi_ilp_fill_kernel(const IlpRow
 #if defined(AMBI_ILP_NOCOMPUTE)   // timing experiment: the stores without the entries
     if (true) { for (int k = 0; k < kIlpPer; k++) { c4[k] = p + k + r; v4[k] = 1.0; } }
 #else
-    if (want == kIlpPer && rel[r + 1] - p >= kIlpPer) ilp_row_entries<kIlpPer>(desc[r], G, p - rel[r], kIlpPer, lit_col, lit_val, c4, v4);
+    if (want == kIlpPer && rel[r + 1] - p >= kIlpPer) ilp_row_entries<kIlpPer, JOINT>(desc[r], G, p - rel[r], kIlpPer, lit_col, lit_val, c4, v4);
 #endif
     else {
 #pragma unroll
@@ -2453,7 +2458,7 @@ __global__ __launch_bounds__(kIlpThreads) void ambi_ilp_fill_kernel(const IlpRow
             const int q = p + k;
             if (k < want) {
                 while (q >= rel[r + 1]) r++;
-                ilp_row_entry(desc[r], G, (int64_t)(q - rel[r]), lit_col, lit_val, &c4[k], &v4[k]);
+                ilp_row_entry<JOINT>(desc[r], G, (int64_t)(q - rel[r]), lit_col, lit_val, &c4[k], &v4[k]);
             }
         }
     }
@@ -2515,11 +2520,13 @@ int backend_ilp_fill(const IlpRowDesc* rows, int64_t n_rows, const int64_t* row_
     HIP_CK(hipEventCreate(&ea)); HIP_CK(hipEventCreate(&eb));
     const int64_t grid = n_chunks > 0 ? n_chunks : 1;
     const int reps = kernel_ms ? 5 : 1;   // the timed figure is the mean of the last 4 of 5 launches
+    const bool joint = n_rows > 0 && (rows[0].family >> 8) != 0;   // a joint model opens with a row of its first graph
+    auto* kernel = joint ? ambi_ilp_fill_kernel<true> : ambi_ilp_fill_kernel<false>;
     float total = 0;
     for (int r = 0; r < reps; r++) {
         HIP_CK(hipEventRecord(ea, nullptr));
         if (n_chunks > 0)
-            hipLaunchKernelGGL(ambi_ilp_fill_kernel, dim3((unsigned)grid), dim3(256), 0, nullptr, (const IlpRowDesc*)d_rows, (const int64_t*)d_ptr, (const int32_t*)d_chunk, nnz,
+            hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kIlpThreads), 0, nullptr, (const IlpRowDesc*)d_rows, (const int64_t*)d_ptr, (const int32_t*)d_chunk, nnz,
                                ilp_geom(s, e), (const int32_t*)d_lc, (const double*)d_lv, d_col, d_val);
         HIP_CK(hipEventRecord(eb, nullptr));
         HIP_CK(hipEventSynchronize(eb));

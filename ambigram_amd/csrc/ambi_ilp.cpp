@@ -3,6 +3,7 @@
 #include "ambi_ilp_rows.hpp"
 
 #include <cfloat>
+#include <climits>
 #include <cstdio>
 #include <set>
 #include <utility>
@@ -270,6 +271,71 @@ void build_bfb_ilp_rows(int s, int e, const double* seg_cn, const double* fold_c
     for (int c = num_el; c < num_var - 1; c++) m.obj[c] = 1;
     m.col_lo[num_var - 1] = m.col_up[num_var - 1] = bias;
     m.obj[num_var - 1] = -1;
+}
+
+// The joint model as ROW DESCRIPTORS (layout and limits: ambi_ilp_rows.hpp): the rows of build_bfb_ilp_sc in its order, everything of
+// `m` except col/val.  O(rows) on the host.  false (and `m` empty): the model is beyond the limits of the descriptor.
+bool build_bfb_ilp_sc_rows(int s, int e, int n_graphs, const double* seg_cn, const double* fold_cn, IlpModel& m, std::vector<IlpRowDesc>& rows) {
+    const double INF = DBL_MAX;
+    m = IlpModel();
+    rows.clear();
+    if (n_graphs < 1 || n_graphs > kIlpMaxGraphs || e < s) return false;
+    const IlpGeom G = ilp_geom(s, e);
+    const int64_t n = G.n, num_pat = n * (n + 1) / 2, num_comp = 2 * num_pat, NG = n_graphs;
+    // sizes in 64 bits before anything is allocated: rows of one graph (4 n fit rows, numPat - 1 PA and LA rows each, numPat - n PB rows and
+    // LL / PC pairs), two linking rows per pair and element; G (G - 1) alone beyond int32 already means too many of them
+    const int64_t rows_per_graph = 4 * n + 2 * (num_pat - 1) + 5 * (num_pat - n);
+    if (NG * (NG - 1) > INT32_MAX) return false;
+    const int64_t link_rows = num_comp * NG * (NG - 1);
+    const int64_t n_rows = NG * rows_per_graph + link_rows;
+    const int64_t num_el = num_comp * NG, first_link_eps = num_el + 2 * n * NG;
+    const int64_t num_var = first_link_eps + NG * (NG - 1) * num_comp;
+    if (n_rows > INT32_MAX || 2 * num_var >= ((int64_t)1 << 31)) return false;   // (every epsilon a row names lies below num_var or n_rows / 2 + num_el)
+    m.n_cols = (int)num_var;
+    m.n_int = (int)num_el;
+    rows.reserve((size_t)n_rows);
+    m.row_ptr.reserve((size_t)n_rows + 1); m.row_lo.reserve((size_t)n_rows); m.row_up.reserve((size_t)n_rows);
+    m.row_ptr.push_back(0);
+    auto row = [&](int family, int a, int b, int rep, double lo, double up) {
+        IlpRowDesc d{family, a, b, rep};
+        rows.push_back(d);
+        m.row_ptr.push_back(m.row_ptr.back() + ilp_row_len(d, G));
+        m.row_lo.push_back(lo); m.row_up.push_back(up);
+    };
+    m.col_lo.assign((size_t)num_var, 0); m.col_up.assign((size_t)num_var, INF); m.obj.assign((size_t)num_var, 0);
+    for (int g = 0; g < n_graphs; g++) {
+        const int tag = (g + 1) << 8, off2 = (int)(g * num_comp) << 1;
+        const double* cn = seg_cn + (size_t)g * n;
+        const double* fold = fold_cn + (size_t)g * n;
+        auto eps = [&]() { return (int)(num_el + (int64_t)rows.size() / 2); };   // the running row counter (LGM.cpp:4815, :4821, :4858, :4864)
+        for (int i = s; i <= e; i++) {
+            const int k = i - s;
+            row(tag | ILP_CN, i, eps(), off2, cn[k], INF); row(tag | ILP_CN, i, eps(), off2 | 1, -INF, cn[k]);
+            row(tag | ILP_FB, i, eps(), off2, fold[k], INF); row(tag | ILP_FB, i, eps(), off2 | 1, -INF, fold[k]);
+        }
+        for (int a = s; a <= e; a++) for (int b = a; b <= e; b++) {
+            if (a > s || b < e) row(tag | ILP_PA, a, b, off2, 0, INF);
+            if (a < b) row(tag | ILP_PB, a, b, off2, 0, 2);
+        }
+        for (int a = s; a <= e; a++) for (int b = a; b <= e; b++)
+            if (a > s || b < e) row(tag | ILP_LA, a, b, off2, 0, INF);
+        for (int a = s; a <= e; a++) for (int b = a + 1; b <= e; b++) { row(tag | ILP_LL, a, b, off2, 0, 2); row(tag | ILP_LL, a, b, off2 | 1, 0, 2); }
+        for (int a = s; a <= e; a++) for (int b = a + 1; b <= e; b++) { row(tag | ILP_PC, a, b, off2, 0, 2); row(tag | ILP_PC, a, b, off2 | 1, 0, 2); }
+        double max_cn = 0;                                                    // loops <= CN sum of THIS graph's segments (:5012-5027)
+        for (int k = 0; k < n; k++) max_cn += cn[k];
+        const size_t off = (size_t)(g * num_comp);
+        for (int64_t c = 0; c < num_pat; c++) m.col_up[off + c] = 1;
+        for (int64_t c = num_pat; c < num_comp; c++) m.col_up[off + c] = max_cn;
+    }
+    int64_t cnt = 2 * first_link_eps;
+    for (int i = 0; i < n_graphs; i++) for (int j = i + 1; j < n_graphs; j++)   // localhap.cpp:430-434: every pair i < j
+        for (int c = 0; c < num_comp; c++)
+            for (int rep = 0; rep < 2; rep++, cnt++)
+                row(ILP_LINK, (int)(c + num_comp * i), (int)(c + num_comp * j), (int)(cnt / 2) << 1 | rep, rep == 0 ? 0 : -INF, rep == 0 ? INF : 0);
+    for (int64_t c = num_el; c < num_var; c++) m.obj[(size_t)c] = 1;
+    m.col.assign((size_t)m.row_ptr.back(), 0);
+    m.val.assign((size_t)m.row_ptr.back(), 0.0);
+    return true;
 }
 
 bool write_lp(const std::string& path, const IlpModel& m) {

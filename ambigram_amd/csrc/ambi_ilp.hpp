@@ -42,6 +42,11 @@ struct IlpRowDesc;
 void build_bfb_ilp_rows(int start_id, int end_id, const double* seg_cn, const double* junc_cn_fold, int bias, double max_cn_total,
                         const std::vector<std::vector<int32_t>>& components, bool juncs_info, IlpModel& m,
                         std::vector<IlpRowDesc>& rows, std::vector<int32_t>& lit_col, std::vector<double>& lit_val);
+// Row-descriptor form of the joint model with the linking rows of every pair i < j (localhap.cpp:430-434, the only `evolution` list the
+// reference makes): everything of `m` except the entries, in the row order of build_bfb_ilp_sc, each graph's loop bounds from its own CN sum.  Returns false and leaves `m` empty beyond the limits of the descriptor (ambi_ilp_rows.hpp): n_graphs < 1
+// or > 2^23 - 1, more than INT32_MAX rows, 2 * n_cols >= 2^31.
+bool build_bfb_ilp_sc_rows(int start_id, int end_id, int n_graphs, const double* seg_cn, const double* fold_cn, IlpModel& m,
+                           std::vector<IlpRowDesc>& rows);
 
 // CPLEX-LP text readable by `cbc <file>.lp solve solu <file>.sol`; columns are named x<j> as CoinUtils names them
 // (the .sol parser relies on it, localhap.cpp:204-205).  Rows whose lower bound 0 is implied (non-negative variables and

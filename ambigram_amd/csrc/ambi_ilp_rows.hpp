@@ -24,9 +24,24 @@ enum IlpFamily : int32_t {
     ILP_LA = 5,     // parents (p and l) of loop (a,b) - l(a,b) >= 0   (:4587-4612)
     ILP_LL = 6,     // child loops + l(a,b) (rep 0) / p(a,b) (rep 1) <= 2   (:4615-4646)
     ILP_PC = 7,     // p(a,b) + child loops/patterns <= 2, two mixes   (:4649-4681)
-    ILP_LIT = 8     // literal row (the .juncs components row, :4684-4703): entries at lit[a ...]
+    ILP_LIT = 8,    // literal row (the .juncs components row, :4684-4703): entries at lit[a ...]
+    ILP_LINK = 9    // joint model only: x_i - x_j +- eps of one element and one pair of graphs (LGM.cpp:5032-5072)
 };
 struct IlpRowDesc { int32_t family, a, b, rep; };
+
+// The JOINT model of G graphs (LocalGenomicMap::BFB_ILP_SC, LGM.cpp:4754-5093; build_bfb_ilp_sc_rows) in the same 16 bytes.  IlpGeom stays
+// the single-graph geometry of the chromosome (num_el = numComp, the columns of one graph's block).
+//   rows of graph g (ILP_CN, FB, PA, PB, LA, LL, PC; no bias row, no .juncs row):
+//       family = kind | (g + 1) << 8      the low byte is the kind; the bits above it are 0 in a single-graph model
+//       a, b                              as in the single-graph row; CN and FB rows use only a, so b = their epsilon COLUMN
+//                                         (numComp*G + idx/2 with idx the row's index in the model, LGM.cpp:4815 / :4858)
+//       rep    = (g * numComp) << 1 | rep the block offset of the graph's element columns above the 0 / 1 of the single-graph row
+//   ILP_LINK: a = first column (+1), b = second column (-1), rep = eps << 1 | sign (0: +1, 1: -1); always three entries
+// An entry of a graph row is the single-graph entry with its column fixed up: a column below num_el is an element and gets the block
+// offset ADDED (the 24-bit multiply never sees an offset), anything else is the row's epsilon, read from b.
+// Limits (build_bfb_ilp_sc_rows refuses beyond them): 1 <= G <= kIlpMaxGraphs (g + 1 in 23 bits of `family`), at most INT32_MAX rows (row
+// indices are int32 on the device), 2 * n_cols < 2^31 (a column shifted by one bit in `rep`).
+constexpr int32_t kIlpMaxGraphs = (1 << 23) - 1;
 
 // 24-bit multiply: full rate on the GPU where the 32-bit one is quarter rate; every product here stays far below 2^31 and every
 // factor below 2^24 (segment counts are <= 32767)
@@ -50,7 +65,7 @@ AMBI_HD IlpGeom ilp_geom(int s, int e) {
 
 AMBI_HD int64_t ilp_row_len(const IlpRowDesc& d, const IlpGeom& G) {
     const int s = G.s, e = G.e, a = d.a, b = d.b;
-    switch (d.family) {
+    switch (d.family & 0xff) {
         case ILP_CN: return 2ll * (a - s + 1) * (e - a + 1) + 1;
         case ILP_FB: return (int64_t)(a - s) + (a < e ? e - a + 1 : (a > s ? 1 : 0)) + (a - s) + (e - a + 1) + 1;
         case ILP_BIAS: return 1;
@@ -59,12 +74,13 @@ AMBI_HD int64_t ilp_row_len(const IlpRowDesc& d, const IlpGeom& G) {
         case ILP_LA: return 2ll * (a - s) + 2ll * (e - b) + 1;
         case ILP_LL: return 2ll * (b - a) + 1;
         case ILP_PC: return 2ll * (b - a) + 1;
+        case ILP_LINK: return 3;
         default: return d.b;   // ILP_LIT: b = number of literal entries
     }
 }
 
-// entry j (0-based) of the row: column and coefficient
-AMBI_HD void ilp_row_entry(const IlpRowDesc& d, const IlpGeom& G, int64_t j64, const int32_t* lit_col, const double* lit_val,
+// entry j (0-based) of a single-graph row: column and coefficient
+AMBI_HD void ilp_row_entry_1g(const IlpRowDesc& d, const IlpGeom& G, int64_t j64, const int32_t* lit_col, const double* lit_val,
                            int32_t* col, double* val) {
     const int s = G.s, e = G.e, a = d.a, b = d.b;
     const int j = (int)j64;
@@ -134,9 +150,9 @@ AMBI_HD void ilp_row_entry(const IlpRowDesc& d, const IlpGeom& G, int64_t j64, c
 // `cnt` (1..4) CONSECUTIVE entries j0 .. j0 + cnt - 1 of one row: the family is decided once, the pieces of the row (runs of entries
 // whose column follows one formula) are walked with the piece bounds and the triangle arithmetic shared between the entries, and the
 // one division of the CN rows (j / w, j % w) is done for the first entry only -- the others step (q, r) forward.  Same values as
-// ilp_row_entry, entry for entry (tests/test_ilp_model.py compares both with the host generator and the oracle).
+// ilp_row_entry_1g, entry for entry (tests/test_ilp_model.py compares both with the host generator and the oracle).
 template <int FIXED = 0>
-AMBI_HD void ilp_row_entries(const IlpRowDesc& d, const IlpGeom& G, int j0, int cnt_rt, const int32_t* lit_col, const double* lit_val,
+AMBI_HD void ilp_row_entries_1g(const IlpRowDesc& d, const IlpGeom& G, int j0, int cnt_rt, const int32_t* lit_col, const double* lit_val,
                              int32_t* col, double* val) {
     const int s = G.s, e = G.e, a = d.a, b = d.b;
     const int cnt = FIXED > 0 ? FIXED : cnt_rt;   // FIXED: the loops below unroll
@@ -207,6 +223,37 @@ AMBI_HD void ilp_row_entries(const IlpRowDesc& d, const IlpGeom& G, int j0, int 
             return;
         }
         default: AMBI_UNROLL_FIXED for (int k = 0; k < cnt; k++) { col[k] = lit_col[d.a + j0 + k]; val[k] = lit_val[d.a + j0 + k]; } return;
+    }
+}
+
+// entry j of a linking row of the joint model
+AMBI_HD void ilp_link_entry(const IlpRowDesc& d, int j, int32_t* col, double* val) {
+    if (j == 0) { *col = d.a; *val = 1; }
+    else if (j == 1) { *col = d.b; *val = -1; }
+    else { *col = d.rep >> 1; *val = (d.rep & 1) ? -1 : 1; }
+}
+// Entry j of a row of either model.  JOINT = false is the single-graph function and nothing else (the instantiation the single-graph
+// kernel runs); JOINT = true also decodes the rows of the joint model (layout above) and serves single-graph rows unchanged: the
+// single-graph arithmetic is walked ONCE for both models (no second copy of it in the kernel), then a graph row's column is fixed up.
+template <bool JOINT = true>
+AMBI_HD void ilp_row_entry(const IlpRowDesc& d, const IlpGeom& G, int64_t j, const int32_t* lit_col, const double* lit_val, int32_t* col, double* val) {
+    if (!JOINT) { ilp_row_entry_1g(d, G, j, lit_col, lit_val, col, val); return; }
+    if (d.family == ILP_LINK) { ilp_link_entry(d, (int)j, col, val); return; }
+    const IlpRowDesc d1{d.family & 0xff, d.a, d.b, d.rep & 1};
+    ilp_row_entry_1g(d1, G, j, lit_col, lit_val, col, val);
+    if (d.family >> 8) *col = *col < G.num_el ? *col + (d.rep >> 1) : d.b;
+}
+template <int FIXED = 0, bool JOINT = true>
+AMBI_HD void ilp_row_entries(const IlpRowDesc& d, const IlpGeom& G, int j0, int cnt_rt, const int32_t* lit_col, const double* lit_val,
+                             int32_t* col, double* val) {
+    if (!JOINT) { ilp_row_entries_1g<FIXED>(d, G, j0, cnt_rt, lit_col, lit_val, col, val); return; }
+    const int cnt = FIXED > 0 ? FIXED : cnt_rt;
+    if (d.family == ILP_LINK) { AMBI_UNROLL_FIXED for (int k = 0; k < cnt; k++) ilp_link_entry(d, j0 + k, col + k, val + k); return; }
+    const IlpRowDesc d1{d.family & 0xff, d.a, d.b, d.rep & 1};
+    ilp_row_entries_1g<FIXED>(d1, G, j0, cnt_rt, lit_col, lit_val, col, val);
+    if (d.family >> 8) {
+        const int off = d.rep >> 1;
+        AMBI_UNROLL_FIXED for (int k = 0; k < cnt; k++) col[k] = col[k] < G.num_el ? col[k] + off : d.b;
     }
 }
 

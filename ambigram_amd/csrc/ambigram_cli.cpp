@@ -132,7 +132,10 @@ int run_sc_bfb(Args& A) {
         }
         if (pr0.status == AMBI_ST_SHORTCUT) { plain[c] = 1; continue; }   // no fold-back in the first graph: reference paths, nothing printed (:505-512)
         ambi_ilp_t* ilp = nullptr;
-        if ((rc = ambi_ilp_build_sc(g0, c, G, seg.data(), fold.data(), &ilp)) != 0) return die(ambi_error_string(rc));
+        // BFB_ILP_SC (LGM.cpp:4754-5093): from 32 segments up the entries are written on the device, as for `--op bfb`
+        if (n >= 32) rc = ambi_ilp_build_sc_device(g0, c, G, seg.data(), fold.data(), nullptr, &ilp);
+        else rc = ambi_ilp_build_sc(g0, c, G, seg.data(), fold.data(), &ilp);
+        if (rc != 0) return die(ambi_error_string(rc));
         head[c] = "Declare done\n";
         for (int k = 0; k < G; k++) head[c] += "ILP formula done\n";
         head[c] += "Variable constrains done\n";

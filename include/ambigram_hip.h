@@ -413,6 +413,13 @@ int ambi_ilp_build_device(const ambi_graph_t* g, int32_t chr, const double* seg_
  * (localhap.cpp:430-434).  The matrix is the one the reference builds, including its use of the running row counter in
  * the epsilon columns (LocalGenomicMap.cpp:4815) -- see DESIGN.md. */
 int ambi_ilp_build_sc(const ambi_graph_t* g0, int32_t chr, int32_t n_graphs, const double* seg_cn, const double* fold_cn, ambi_ilp_t** out);
+/* The joint model with its entries written ON THE DEVICE: the host lists the rows (O(rows)), ambi_ilp_fill_kernel writes
+ * the 12 bytes per non-zero, the arrays come back to the host.  Bit-identical to ambi_ilp_build_sc.  kernel_ms as in
+ * ambi_ilp_build_device (optional; mean of the last 4 of 5 launches).  AMBI_ERR_NO_DEVICE without a GPU.  AMBI_ERR_ARG
+ * (and *out = NULL) beyond the limits of the row descriptor: n_graphs < 1 or > 2^23 - 1, a model of more than INT32_MAX
+ * rows, a model with 2 * n_cols >= 2^31. */
+int ambi_ilp_build_sc_device(const ambi_graph_t* g0, int32_t chr, int32_t n_graphs, const double* seg_cn, const double* fold_cn,
+                             float* kernel_ms, ambi_ilp_t** out);
 void ambi_ilp_destroy(ambi_ilp_t* p);
 int ambi_ilp_sizes(const ambi_ilp_t* p, int64_t* n_rows, int64_t* nnz, int32_t* n_cols, int32_t* n_int);
 /* CSR copy-out; infinity is +-DBL_MAX (OsiClp getInfinity()); any pointer may be NULL */
