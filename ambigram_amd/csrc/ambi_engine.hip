@@ -5,6 +5,7 @@
 //                                                  targetCN, constructDAG; order-ideal lattice (level-synchronous
 //                                                  search in LDS), completion counts, frozen automaton; R
 //   ambi_plan_kernel              1 block / batch  64-bit scans: order-table offsets, enumerate work blocks
+//                                                  (ambi_plan_reset_kernel in front of a second pass over the same headers)
 //   ambi_blocks_build_kernel      1 block / unit   block-emission image (block directory + suffix rows) -> HBM
 //   ambi_enumerate_blocks_kernel  1 block / work block: image -> LDS, rows streamed block by block with fully
 //                                                  coalesced 16-byte stores                       <- HBM-bound
@@ -13,11 +14,15 @@
 //   ambi_first_kernel             1 wave  / unit   getBFB scan for the first valid order, bkp in LDS
 //   ambi_search/resolve_kernel    1 wave  / chunk of orders (only for units whose scan budget ran out)
 //   ambi_finish_kernel            1 block / unit   bkp -> path (LDS int16), indelBFB, output junctions
-//   ambi_pack_*                   optional end-of-batch packing of the paths for an RCCL gather
+//   ambi_pack_scan/copy_kernel    optional end-of-batch packing of the paths for an RCCL gather, as cells ...
+//   ambi_pack_runs_count/scan/write_kernel          ... or as runs {start value, length}; ambi_expand_runs_kernel (1 wave /
+//                                                  run) turns runs back into cells on the receiving rank (ambi_exchange.hpp)
 //   ambi_path_profile_kernel      1 block / unit   on request: per-segment traversal counts of the path + summary
 //                                                  (ambi_profile.hpp)                              <- read-bound, 2 bytes / cell
-// Every kernel is a wrapper around the stage functions of ambi_stages.hpp, the four table kernels (blocks_build,
-// enumerate_blocks, enumerate, enumerate_wide) included: their logic is under that file's stage_enumerate banner.
+// Every kernel but the two plan kernels is a wrapper around the stage functions of ambi_stages.hpp (ambi_exchange.hpp,
+// ambi_profile.hpp for the pack / expand and profile kernels), which the host simulation runs as well, the four table kernels
+// (blocks_build, enumerate_blocks, enumerate, enumerate_wide; their logic is under stage_enumerate's banner) included.  The
+// plan kernel has a serial twin for the host simulation (plan_serial).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -28,6 +33,7 @@
 #include <vector>
 
 #include "ambi_backend.hpp"
+#include "ambi_exchange.hpp"
 #include "ambi_ilp_rows.hpp"
 #include "ambi_stages.hpp"
 
@@ -183,29 +189,6 @@ __global__ __launch_bounds__(64) void ambi_lattice_kernel(BatchArgs A) {
     stage_lattice(g, A, A.unit_base + (int)blockIdx.x, ambi_lds);
 }
 
-__device__ inline int64_t wave_incl_scan_i64(int64_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int64_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one int64 per thread (blockDim.x <= 1024); *total = sum
-__device__ inline int64_t block_exscan_i64(int64_t v, int64_t* total, int64_t* sh /*[17]*/) {
-    int64_t inc = wave_incl_scan_i64(v);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    int64_t base = 0, tot = 0;
-    for (int i = 0; i < nw; i++) { int64_t s = sh[i]; if (i < w) base += s; tot += s; }
-    *total = tot;
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(64) void ambi_lattice_own_kernel(BatchArgs A) {
     WaveGroup g;
     if (A.zero_pending && blockIdx.x == 0 && threadIdx.x == 0) { A.refin_count[0] = 0; A.refin_count[1] = 0; }   // (as ambi_lattice_kernel)
@@ -240,9 +223,11 @@ __global__ void ambi_plan_reset_kernel(BatchArgs A) {
     if (out->order_off >= 0 || out->order_off == kOrderOffNoRoom) out->order_off = kOrderOffWanted;
 }
 
-// Parallel form of plan_serial (ambi_stages.hpp): same prefix-sum semantics.
+// Parallel form of plan_serial (ambi_stages.hpp): same prefix-sum semantics; its body stays here (profiles/r11_notes.md: in the shared
+// form the kernel was 0.5 us slower).
 __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
-    __shared__ int64_t sh[17];
+    __shared__ __align__(16) int scratch[40];   // (exscan_i64 needs 8; 16 lets it read the wave totals as 16-byte words)
+    BlockGroup g(scratch);
     if (A.lat_R) {   // the lattice ran beside the express kernel: its outcome goes into the headers first
         for (int i = threadIdx.x; i < A.n_units; i += blockDim.x) plan_merge_lattice(A, A.unit_base + i);
         __threadfence();
@@ -276,7 +261,7 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
         for (int k = 0; k < kPlanPer; k++) if (wanted_[k] && R_[k] < (int64_t)kCountSat) my_rows += R_[k];
     }
     int64_t total_rows;
-    (void)block_exscan_i64(my_rows, &total_rows, sh);
+    (void)g.exscan_i64(my_rows, &total_rows);
     const int TL = rows_per_lane_for(total_rows, A.target_lanes);
     int64_t off_carry = 0, blk_carry = 0;
     for (int base = 0; base < A.n_units; base += chunk) {
@@ -298,7 +283,7 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
             sum_b += bytes[k];
         }
         int64_t tot_b, tot_k;
-        int64_t off = off_carry + block_exscan_i64(sum_b, &tot_b, sh);
+        int64_t off = off_carry + g.exscan_i64(sum_b, &tot_b);
         // a unit that does not fit contributes no work blocks (and still advances the offset: orders_needed is the true total)
         bool fits[kPlanPer];
         int64_t offs_[kPlanPer], sum_k = 0;
@@ -309,7 +294,7 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
             off += bytes[k];
             sum_k += fits[k] ? blocks[k] : 0;
         }
-        int64_t blk = blk_carry + block_exscan_i64(sum_k, &tot_k, sh);
+        int64_t blk = blk_carry + g.exscan_i64(sum_k, &tot_k);
 #pragma unroll
         for (int k = 0; k < kPlanPer; k++) {
             const int i = base + (int)threadIdx.x * kPlanPer + k;
@@ -567,101 +552,34 @@ __global__ __launch_bounds__(256) AMBI_LEAN_ATTR void ambi_finish_lean_kernel(Ba
     }
 }
 
+// ---- the final paths packed for the end-of-batch exchange (ambi_exchange.hpp): cells, or runs {start value, length} ----
+// Cells: one scan of the lengths, then one workgroup per unit copies.  Runs: one workgroup per unit counts, one scan, one
+// workgroup per unit writes.
 __global__ __launch_bounds__(1024) void ambi_pack_scan_kernel(BatchArgs A, int which, int32_t* lengths, int64_t* pack_off, int64_t* total) {
-    __shared__ int64_t sh[17];
-    int64_t carry = 0;
-    for (int base = 0; base < A.n_units; base += blockDim.x) {
-        const int u = base + (int)threadIdx.x;
-        int64_t len = 0;
-        if (u < A.n_units) {
-            const UnitOut* h = unit_out(A.results, u);
-            len = which ? h->path_indel_len : h->path_len;
-            lengths[u] = (int32_t)len;
-        }
-        int64_t tot;
-        int64_t ex = block_exscan_i64(len, &tot, sh);
-        if (u < A.n_units) pack_off[u] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) { pack_off[A.n_units] = carry; if (total) *total = carry; }
+    __shared__ __align__(16) int scratch[40];   // (exscan_i64 needs 8; 16 lets it read the wave totals as 16-byte words)
+    BlockGroup g(scratch);
+    pack_scan(g, A, which, lengths, pack_off, total);
 }
 __global__ __launch_bounds__(256) void ambi_pack_copy_kernel(BatchArgs A, int which, const int64_t* pack_off, int32_t* cells, int64_t cap) {
-    const int u = blockIdx.x;
-    const UnitIn& U = A.units[u];
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    const bool stored = which && unit_out(A.results, u)->path_ind_stored;   // else the edited path equals `path`
-    const rcell_t* src = reinterpret_cast<const rcell_t*>(A.results + U.res_off + (stored ? L.path_ind : L.path));
-    const int64_t off = pack_off[u], len = pack_off[u + 1] - off;
-    for (int64_t i = threadIdx.x; i < len; i += blockDim.x)
-        if (off + i < cap) cells[off + i] = abs_cell(src[i], U.seg_base);
-}
-
-// ---- run-length form of the final paths (payload of the end-of-batch exchange) ----
-// A run starts where a cell is not its predecessor + 1.  One workgroup per unit, two passes over the path in the result
-// blob: count the runs (all units) -> offsets (one scan) -> write {start value, length}.
-__device__ inline const rcell_t* unit_final_path(const BatchArgs& A, int u, int which, int* len) {
-    const UnitIn& U = A.units[u];
-    const UnitOut* h = unit_out(A.results, u);
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    const bool stored = which && h->path_ind_stored;   // else the edited path equals `path`
-    *len = which ? h->path_indel_len : h->path_len;
-    return reinterpret_cast<const rcell_t*>(A.results + U.res_off + (stored ? L.path_ind : L.path));
+    BlockGroup g(nullptr);   // (strided copy: no exchange between the threads)
+    pack_copy_unit(g, A, (int)blockIdx.x, which, pack_off, cells, cap);
 }
 __global__ __launch_bounds__(256) void ambi_pack_runs_count_kernel(BatchArgs A, int which, int32_t* lengths, int32_t* run_counts) {
     __shared__ int scratch[40];
     BlockGroup g(scratch);
-    const int u = blockIdx.x;
-    int P;
-    const rcell_t* src = unit_final_path(A, u, which, &P);
-    int mine = 0;
-    for (int i = threadIdx.x; i < P; i += blockDim.x) mine += (i == 0 || src[i] != src[i - 1] + 1) ? 1 : 0;
-    const int total = g.sum_i32(mine);
-    if (threadIdx.x == 0) { run_counts[u] = total; lengths[u] = P; }
+    pack_runs_count_unit(g, A, (int)blockIdx.x, which, lengths, run_counts);
 }
 __global__ __launch_bounds__(1024) void ambi_pack_runs_scan_kernel(BatchArgs A, const int32_t* lengths, const int32_t* run_counts, int64_t* run_off,
                                                                    int64_t* totals) {
-    __shared__ int64_t sh[17];
-    int64_t carry = 0, cells = 0;
-    for (int base = 0; base < A.n_units; base += blockDim.x) {
-        const int u = base + (int)threadIdx.x;
-        const int64_t c = u < A.n_units ? run_counts[u] : 0, l = u < A.n_units ? lengths[u] : 0;
-        int64_t tot, totl;
-        const int64_t ex = block_exscan_i64(c, &tot, sh);
-        (void)block_exscan_i64(l, &totl, sh);
-        if (u < A.n_units) run_off[u] = carry + ex;
-        carry += tot; cells += totl;
-    }
-    if (threadIdx.x == 0) { run_off[A.n_units] = carry; if (totals) { totals[0] = carry; totals[1] = cells; } }
+    __shared__ __align__(16) int scratch[40];   // (exscan_i64 needs 8; 16 lets it read the wave totals as 16-byte words)
+    BlockGroup g(scratch);
+    pack_runs_scan(g, A, lengths, run_counts, run_off, totals);
 }
 __global__ __launch_bounds__(256) void ambi_pack_runs_write_kernel(BatchArgs A, int which, const int64_t* run_off, int32_t* run_start,
                                                                    int32_t* run_len, int64_t cap) {
     __shared__ int scratch[40];
     BlockGroup g(scratch);
-    const int u = blockIdx.x;
-    int P;
-    const rcell_t* src = unit_final_path(A, u, which, &P);
-    const int64_t off = run_off[u];
-    const int n = (int)(run_off[u + 1] - off);
-    if (off + n > cap) return;   // the caller's buffers are too small: nothing is written for this unit (totals tell)
-    int done = 0;
-    for (int base = 0; base < P; base += blockDim.x) {      // run starts in path order: value and, for now, position
-        const int i = base + (int)threadIdx.x;
-        const int flag = (i < P && (i == 0 || src[i] != src[i - 1] + 1)) ? 1 : 0;
-        int tot;
-        const int ex = g.exscan_i32(flag, &tot);
-        if (flag) { run_start[off + done + ex] = abs_cell(src[i], A.units[u].seg_base); run_len[off + done + ex] = i; }
-        done += tot;
-    }
-    __syncthreads();
-    // positions -> lengths (the next run's position is read before anyone overwrites it: two phases)
-    for (int base = 0; base < n; base += blockDim.x) {
-        const int k = base + (int)threadIdx.x;
-        int len = 0;
-        if (k < n) len = (k + 1 < n ? run_len[off + k + 1] : P) - run_len[off + k];
-        __syncthreads();
-        if (k < n) run_len[off + k] = len;
-        __syncthreads();
-    }
+    pack_runs_write_unit(g, A, (int)blockIdx.x, which, run_off, run_start, run_len, cap);
 }
 // ---- copy-number profile of the paths (ambi_profile.hpp; launched by HipBackend::profile only) ----
 // One workgroup of 256 threads per unit, grid-stride over the units.  Group memory: 256 bytes for the group's reductions, then
@@ -678,13 +596,9 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_path_profile_kernel(Batc
 // one wavefront per run
 __global__ __launch_bounds__(256) void ambi_expand_runs_kernel(const int32_t* run_start, const int32_t* run_len, const int64_t* cell_off, int64_t n_runs,
                                                                int32_t* cells, int64_t cap) {
-    const int lane = threadIdx.x & 63;
+    WaveGroup g;
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t r = wave; r < n_runs; r += nwaves) {
-        const int32_t s = run_start[r], len = run_len[r];
-        const int64_t o = cell_off[r];
-        for (int k = lane; k < len; k += 64) if (o + k < cap) cells[o + k] = s + k;
-    }
+    for (int64_t r = wave; r < n_runs; r += nwaves) expand_run(g, run_start, run_len, cell_off, r, cells, cap);
 }
 
 // ---- do two streams dispatch side by side? ----

@@ -9,6 +9,9 @@
 //   HostGroup   1 thread, reductions are identities        -> CPU host simulation (tests, sanitizers)
 //   WaveGroup   one 64-lane CDNA wavefront, DPP/shuffle reductions, no LDS scratch needed
 //   BlockGroup  one workgroup of up to 1024 threads (wave reduce + LDS exchange)
+// A BlockGroup is given 40 ints of group memory for its exchanges.  exscan_i64 keeps 16 wave totals of 8 bytes there: a group
+// that calls it needs the array on an 8-byte boundary at least, and on a 16-byte one the totals are read back as 16-byte words
+// (ds_read_b128).  Declare it `__shared__ __align__(16) int scratch[40]`, as every kernel that scans 64-bit values does.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -61,6 +64,7 @@ struct HostGroup {
     AMBI_HD int first_flag(bool q) const { return q ? 0 : -1; }   // lowest thread with the flag set, -1 if none
     // exclusive prefix sum over the group in thread order; total returned through *total
     AMBI_HD int exscan_i32(int v, int* total) const { *total = v; return 0; }
+    AMBI_HD int64_t exscan_i64(int64_t v, int64_t* total) const { *total = v; return 0; }
     // sub-groups: runs of up to 64 consecutive threads (a wavefront on the GPU) that can rank flags without a barrier
     AMBI_HD int sub_size() const { return 1; }
     AMBI_HD int sub_id() const { return 0; }
@@ -123,6 +127,16 @@ struct WaveGroup {
         x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2 and 3
         return x;
     }
+    // the same for 64-bit values: shuffle form (a DPP move carries 32 bits)
+    __device__ inline int64_t incl_scan_i64(int64_t v) const {
+        const int lane = threadIdx.x & 63;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            int64_t t = __shfl_up(v, o, 64);
+            if (lane >= o) v += t;
+        }
+        return v;
+    }
     __device__ inline int sum_i32(int v) const { return __builtin_amdgcn_readlane(incl_scan_i32(v), 63); }
     __device__ inline bool any(bool p) const { return __ballot(p) != 0ull; }
     __device__ inline int bcast_i32(int v, int src) const { return __shfl(v, src, 64); }
@@ -151,7 +165,7 @@ struct WaveGroup {
     __device__ inline int flag_exscan(bool q, int* count) const { return flag_rank(q, count); }
 };
 
-// One workgroup. `scratch` points at >= 40 ints of LDS reserved for the reductions.
+// One workgroup. `scratch` points at >= 40 ints of LDS reserved for the reductions (16-byte aligned for exscan_i64, see above).
 struct BlockGroup {
     static constexpr bool kIsBlock = true;       // several wavefronts: group operations cost workgroup barriers
     static constexpr bool kLaneArrays = false;
@@ -196,6 +210,21 @@ struct BlockGroup {
         for (int i = 0; i < nw; i++) { int s = scratch[i]; if (i < me) base += s; tot += s; }
         *total = tot;
         return base + x;
+    }
+    // one int64 per thread (the plan and pack scans: byte offsets of a whole batch): shuffle scan per wave, the wave totals
+    // exchanged through scratch as 8-byte words (16 waves at most); scratch declared __align__(16)
+    __device__ inline int64_t exscan_i64(int64_t v, int64_t* total) const {
+        WaveGroup wg;
+        int64_t* sh = reinterpret_cast<int64_t*>(scratch);
+        int64_t inc = wg.incl_scan_i64(v);
+        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+        __syncthreads();
+        if (lane == 63) sh[w] = inc;
+        __syncthreads();
+        int64_t base = 0, tot = 0;
+        for (int i = 0; i < nw; i++) { int64_t s = sh[i]; if (i < w) base += s; tot += s; }
+        *total = tot;
+        return base + inc - v;
     }
     __device__ inline int sub_size() const { return 64; }
     __device__ inline int sub_id() const { return (int)(threadIdx.x >> 6); }

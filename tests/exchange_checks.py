@@ -1,7 +1,8 @@
 """Checks of the end-of-batch payload (ambi_batch_pack_paths, ambi_batch_pack_runs, ambi_expand_runs, ambi_batch_runs_to_host) shared
 by the CPU host-simulation tests and the GPU tests (same assertions, different library; tests/test_exchange_payload.py).  On the GPU
-these are the kernels ambi_pack_scan / _copy, ambi_pack_runs_count / _scan / _write and ambi_expand_runs of csrc/ambi_engine.hip, which
-share no source with the loops of tests/hostsim/host_backend.cpp: the CPU runs prove the test logic, the GPU runs test the kernels.
+these are the kernels ambi_pack_scan / _copy, ambi_pack_runs_count / _scan / _write and ambi_expand_runs of csrc/ambi_engine.hip: set-up
+around the functions of csrc/ambi_exchange.hpp, which tests/hostsim/host_backend.cpp calls in the same order with one thread.  The CPU
+runs check those functions (and the test logic), the GPU runs check them on workgroups and wavefronts and with the kernels' set-up.
 
 Expected values never come from the engine: the cells are the ORACLE's paths (`path` for which = 0, `path_indel` for which = 1), cut
 into runs and laid out with plain numpy (runs_of, Reference); the synthetic runs of check 4 are expanded with numpy.arange.  Every

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../ambigram_amd/csrc/ambi_backend.hpp"
+#include "../../ambigram_amd/csrc/ambi_exchange.hpp"
 #include "../../ambigram_amd/csrc/ambi_ilp_rows.hpp"
 #include "../../ambigram_amd/csrc/ambi_stages.hpp"
 
@@ -329,44 +330,30 @@ class HostSimBackend : public Backend {
         if (bytes) *bytes = (int64_t)results_.size();
         return 0;
     }
+    // the exchange stages (ambi_exchange.hpp) in the order HipBackend launches the kernels.  They read the units and the result
+    // blob only, so they get arguments of their own with just those: a pack call leaves the backend's state (A_) alone.
+    std::vector<int64_t> pack_off_;
+    BatchArgs pack_args() {
+        BatchArgs P{};
+        P.n_units = (int32_t)units_.size(); P.units = units_.data(); P.results = results_.data();
+        return P;
+    }
     int pack_paths(int which, int32_t* lengths, int32_t* cells, int64_t cap, int64_t* total, void*) override {
-        int64_t off = 0;
-        for (size_t u = 0; u < units_.size(); u++) {
-            const UnitOut* h = unit_out(results_.data(), (int)u);
-            const UnitIn& U = units_[u];
-            UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-            int len = which ? h->path_indel_len : h->path_len;
-            const rcell_t* src = reinterpret_cast<const rcell_t*>(results_.data() + U.res_off + ((which && h->path_ind_stored) ? L.path_ind : L.path));
-            lengths[u] = len;
-            for (int i = 0; i < len && off + i < cap; i++) cells[off + i] = abs_cell(src[i], U.seg_base);
-            off += len;
-        }
-        if (total) *total = off;
+        HostGroup g;
+        const BatchArgs P = pack_args();
+        pack_off_.assign(units_.size() + 1, 0);
+        pack_scan(g, P, which, lengths, pack_off_.data(), total);
+        for (int u = 0; u < P.n_units; u++) pack_copy_unit(g, P, u, which, pack_off_.data(), cells, cap);
         return 0;
     }
     int pack_runs(int which, int32_t* lengths, int32_t* run_counts, int32_t* run_start, int32_t* run_len, int64_t cap, int64_t* totals,
                   void*) override {
-        int64_t off = 0, cells = 0;
-        for (size_t u = 0; u < units_.size(); u++) {
-            const UnitOut* h = unit_out(results_.data(), (int)u);
-            const UnitIn& U = units_[u];
-            UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-            const int len = which ? h->path_indel_len : h->path_len;
-            const rcell_t* src = reinterpret_cast<const rcell_t*>(results_.data() + U.res_off + ((which && h->path_ind_stored) ? L.path_ind : L.path));
-            lengths[u] = len;
-            int n = 0;
-            for (int i = 0; i < len; i++) n += (i == 0 || src[i] != src[i - 1] + 1) ? 1 : 0;
-            if (off + n <= cap) {   // (as ambi_pack_runs_write_kernel: a unit whose runs do not all fit is not written at all)
-                int64_t k = off - 1;
-                for (int i = 0; i < len; i++) {
-                    if (i == 0 || src[i] != src[i - 1] + 1) { k++; run_start[k] = abs_cell(src[i], U.seg_base); run_len[k] = 0; }
-                    run_len[k]++;
-                }
-            }
-            run_counts[u] = n;
-            off += n; cells += len;
-        }
-        if (totals) { totals[0] = off; totals[1] = cells; }
+        HostGroup g;
+        const BatchArgs P = pack_args();
+        pack_off_.assign(units_.size() + 1, 0);
+        for (int u = 0; u < P.n_units; u++) pack_runs_count_unit(g, P, u, which, lengths, run_counts);
+        pack_runs_scan(g, P, lengths, run_counts, pack_off_.data(), totals);
+        for (int u = 0; u < P.n_units; u++) pack_runs_write_unit(g, P, u, which, pack_off_.data(), run_start, run_len, cap);
         return 0;
     }
     int copy_orders(int unit, int64_t first, int64_t count, uint8_t* out) override {
@@ -409,8 +396,7 @@ Backend* make_backend() { return new HostSimBackend(); }
 
 int backend_expand_runs(const int32_t* run_start, const int32_t* run_len, const int64_t* cell_off, int64_t n_runs, int32_t* cells,
                         int64_t cell_cap, void*) {
-    for (int64_t r = 0; r < n_runs; r++)
-        for (int k = 0; k < run_len[r]; k++) if (cell_off[r] + k < cell_cap) cells[cell_off[r] + k] = run_start[r] + k;
+    for (int64_t r = 0; r < n_runs; r++) expand_run(HostGroup{}, run_start, run_len, cell_off, r, cells, cell_cap);
     return 0;
 }
 

@@ -1,9 +1,10 @@
 """The end-of-batch payload at its edges (tests/exchange_checks.py): ambi_batch_pack_paths, ambi_batch_pack_runs, ambi_expand_runs,
 ambi_batch_runs_to_host and dist.RunExchange against plain numpy on the ORACLE's paths.  Every check runs on the CPU through the
-host simulation with CPU tensors -- that proves the test logic, the host simulation has loops of its own for these calls -- and,
-marked gpu, through the HIP engine with device tensors: there the kernels ambi_pack_scan / _copy, ambi_pack_runs_count / _scan /
-_write and ambi_expand_runs run with more than one block of 1024 units, more than one group of 256 runs per unit, empty paths,
-capacities that are too small and more runs than the expansion starts wavefronts."""
+host simulation with CPU tensors -- the functions of csrc/ambi_exchange.hpp that the kernels call, on one thread, so a thread's
+every trip through their loops -- and, marked gpu, through the HIP engine with device tensors: there the kernels ambi_pack_scan /
+_copy, ambi_pack_runs_count / _scan / _write and ambi_expand_runs run the same functions with more than one block of 1024 units,
+more than one group of 256 runs per unit, empty paths, capacities that are too small and more runs than the expansion starts
+wavefronts."""
 import pytest
 
 import exchange_checks as xc
