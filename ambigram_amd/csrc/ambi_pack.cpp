@@ -44,7 +44,9 @@ int HostBatch::add_unit(int n_seg, int seg_base, const double* cn_local, int n_j
     // every breakpoint pair expands to at most n cells (LGM.cpp:3661-3670).  indelBFB can only GROW the path through
     // a duplication (same-strand SV pointing backwards, LGM.cpp:3794-3805: repeats a stretch) or an insertion group
     // (:3820-3832: adds at most one cell per chained SV); size the head-room accordingly.
-    int64_t bound = std::max<int64_t>(64, ((L + 1) / 2) * (int64_t)n_seg);
+    // A unit without elements still gets a path: the shortcut and the infeasible ILP print the reference path 1+..n+
+    // (localhap.cpp:164-170, :213-220), n cells.
+    int64_t bound = std::max<int64_t>({64, (int64_t)n_seg, ((L + 1) / 2) * (int64_t)n_seg});
     int64_t n_sv = 0;
     bool may_dup = false;
     for (int j = 0; j < n_junc; j++) {

@@ -1265,8 +1265,27 @@ RunResult runBfb(const RunOptions& opt) {
         }
         constructDAG(variableIdx, elementCN, st.dag);
         std::vector<std::vector<int>> orders;
-        allTopologicalOrders(st.dag, orders, opt.maxOrders);
+        bool cyclic = false;
+        if (opt.dagOnly) {
+            // The "inherited" loop -> pattern edges can close a cycle.  Such a graph has no topological order, and the reference's
+            // recursion (LGM.cpp:3380-3409) finds that out by walking every prefix: minutes for 31 nodes.  Its answer is known without
+            // the walk: no order.  (Kahn's count of the nodes that can be removed.)
+            const int num = (int)st.dag.adj.size();
+            std::vector<int> indeg(num, 0), ready;
+            for (int i = 0; i < num; i++) for (int nx : st.dag.adj[i]) indeg[nx]++;
+            for (int i = 0; i < num; i++) if (indeg[i] == 0) ready.push_back(i);
+            int removed = 0;
+            while (!ready.empty()) { int i = ready.back(); ready.pop_back(); removed++; for (int nx : st.dag.adj[i]) if (--indeg[nx] == 0) ready.push_back(nx); }
+            cyclic = removed != num;
+        }
+        if (!cyclic) allTopologicalOrders(st.dag, orders, opt.maxOrders);
         st.numOrders = (long)orders.size();
+        if (opt.dagOnly) {   // test infrastructure: the DAG, the order count (up to maxOrders), targetCN and the orders; nothing is assembled
+            if (opt.keepOrders) st.orders = orders;
+            R.reconSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - tB).count();
+            R.chr.push_back(st);
+            continue;
+        }
         getBFB(g, orders, st.dag, inversions, opt.reversed, opt.all, st.bfb, R.log);
         if (opt.keepOrders) st.orders = orders;
         std::vector<int> path = st.bfb.path;
@@ -1290,7 +1309,7 @@ RunResult runBfb(const RunOptions& opt) {
         R.cnSum += s.cn;
         R.maxCN = (R.maxCN > s.cn) ? R.maxCN : s.cn;
     }
-    if (props.insMode == 2 || props.conMode == 2) {
+    if ((props.insMode == 2 || props.conMode == 2) && !opt.dagOnly) {
         if (props.mainChr.empty()) { R.err = "BFB-TRX without M:<chr> (reference segfaults)"; return R; }
         R.trxRun = true;
         translocationBFB(g, R.paths, R.trxPath, props.mainChr, R.log, &R.trxTrace);

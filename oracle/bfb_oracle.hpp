@@ -194,6 +194,8 @@ struct RunOptions {
     std::vector<std::string> solPerChr;            // .sol path for each chromosome that reaches the ILP, in order
     bool juncInfo = false, reversed = false, all = false;
     bool keepOrders = false;
+    bool dagOnly = false;                          // runBfb stops a chromosome after constructDAG + allTopologicalOrders: no getBFB,
+                                                   // no indelBFB, no path (and no BFB-TRX stitching afterwards)
     size_t maxOrders = SIZE_MAX;
 };
 struct RunResult {

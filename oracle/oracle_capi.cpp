@@ -54,12 +54,13 @@ void oracle_free(char* p) { free(p); }
 
 // Runs the whole `--op bfb` flow (localhap.cpp:49-388) with the cbc step replaced by the given .sol files
 // (comma separated, one per chromosome that reaches the ILP).  flags: bit0 reversed, bit1 all, bit2 junc_info,
-// bit3 keep orders in the dump, bit4 --all paths as distinct paths + an index per valid order.  Returns a malloc'ed JSON string (free with oracle_free).
+// bit3 keep orders in the dump, bit4 --all paths as distinct paths + an index per valid order, bit5 stop every chromosome after the DAG
+// and its orders (RunOptions::dagOnly).  Returns a malloc'ed JSON string (free with oracle_free).
 char* oracle_run_bfb(const char* lh, const char* juncs, const char* sols, int flags, long long maxOrders, double* seconds) {
     RunOptions opt;
     opt.lh = lh; opt.juncs = juncs ? juncs : "";
     opt.solPerChr = split(sols, ',');
-    opt.reversed = flags & 1; opt.all = flags & 2; opt.juncInfo = flags & 4; opt.keepOrders = flags & 8;
+    opt.reversed = flags & 1; opt.all = flags & 2; opt.juncInfo = flags & 4; opt.keepOrders = flags & 8; opt.dagOnly = flags & 32;
     if (maxOrders > 0) opt.maxOrders = (size_t)maxOrders;
     auto t0 = std::chrono::steady_clock::now();
     RunResult R;
@@ -123,6 +124,33 @@ char* oracle_run_bfb(const char* lh, const char* juncs, const char* sols, int fl
     }
     o << "]}";
     return dup(o.str());
+}
+
+// getJuncCN / the bias / getIndelBias / the fold-back sum (localhap.cpp:136-153) on ONE chromosome given as arrays: segments
+// 1..n_seg and the junctions exactly as listed.  Nothing passes through addJunction, so the list may hold what no .lh can: the
+// reader keeps one of i+ -> i+1+ and i+1- -> i- (Graph.cpp:489-499 calls them the same junction), a list may hold both.
+// sdir / tdir: > 0 is '+'.  Out: junc_cn[2 * (n_seg + 1)], seg_cn[n_seg + 1] after getIndelBias ([0] unused),
+// inv_junc[n_seg + 1] (junction index or -1), *bias, *inv_sum.
+void oracle_prepare_raw(int n_seg, const double* seg_cn_in, int n_junc, const int* src, const signed char* sdir, const int* tgt,
+                        const signed char* tdir, const double* cn, double* junc_cn, double* seg_cn, int* inv_junc, int* bias, double* inv_sum) {
+    Graph g;
+    g.sourceIds.push_back(1); g.sinkIds.push_back(n_seg);
+    for (int i = 1; i <= n_seg; i++) { Seg s; s.id = i; s.chrId = 0; s.chrom = "chr1"; s.cn = seg_cn_in[i - 1]; g.segs.push_back(s); }
+    for (int j = 0; j < n_junc; j++) {
+        Junc q; q.src = src[j]; q.tgt = tgt[j]; q.sdir = sdir[j] > 0 ? '+' : '-'; q.tdir = tdir[j] > 0 ? '+' : '-'; q.cn = cn[j];
+        g.juncs.push_back(q);
+    }
+    Inversions inv; std::vector<double> jc;
+    getJuncCN(g, 1, n_seg, inv, jc);
+    *bias = computeBias(g, 1, n_seg, inv, jc);
+    getIndelBias(g, 1, n_seg);
+    double s = 0;
+    for (int i = 0; i <= n_seg; i++) s += jc[i * 2 + 1];
+    *inv_sum = s;
+    for (int i = 0; i < 2 * (n_seg + 1); i++) junc_cn[i] = jc[i];
+    seg_cn[0] = 0;
+    for (int i = 1; i <= n_seg; i++) { seg_cn[i] = g.segs[i - 1].cn; }
+    for (int i = 0; i <= n_seg; i++) { auto it = inv.find(i); inv_junc[i] = it == inv.end() ? -1 : it->second; }
 }
 
 // ILP model of chromosome `chr` exactly as main() would hand it to BFB_ILP (localhap.cpp:111-173): graph loaded,

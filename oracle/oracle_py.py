@@ -16,6 +16,7 @@ FLAG_ALL = 2
 FLAG_JUNC_INFO = 4
 FLAG_KEEP_ORDERS = 8
 FLAG_ALL_DEDUP = 16
+FLAG_DAG_ONLY = 32
 
 
 def build(ref=True):
@@ -66,12 +67,15 @@ def lib_O0():
     return _LIB_O0
 
 
-def run_bfb(lh, sols, juncs="", reversed_=False, all_=False, junc_info=False, keep_orders=False, max_orders=0, O0=False, dedup_all=False):
+def run_bfb(lh, sols, juncs="", reversed_=False, all_=False, junc_info=False, keep_orders=False, max_orders=0, O0=False, dedup_all=False, dag_only=False):
     """Whole `--op bfb` flow on the CPU oracle. `sols`: list of .sol paths, one per chromosome reaching the ILP.
     `dedup_all`: the --all paths cross the binding as distinct paths + one index per valid order (units with tens of thousands of
-    orders that all give the same path); `all_paths` is the same list of lists either way (equal entries share one list)."""
+    orders that all give the same path); `all_paths` is the same list of lists either way (equal entries share one list).
+    `dag_only`: every chromosome stops after constructDAG and allTopologicalOrders (up to `max_orders`): its record has the DAG,
+    num_orders and (keep_orders) the orders, the run's target_cn is filled, nothing is assembled -- for element sets whose
+    assembly takes the CPU minutes."""
     flags = (FLAG_REVERSED if reversed_ else 0) | (FLAG_ALL if all_ else 0) | \
-            (FLAG_JUNC_INFO if junc_info else 0) | (FLAG_KEEP_ORDERS if keep_orders else 0) | (FLAG_ALL_DEDUP if dedup_all else 0)
+            (FLAG_JUNC_INFO if junc_info else 0) | (FLAG_KEEP_ORDERS if keep_orders else 0) | (FLAG_ALL_DEDUP if dedup_all else 0) | (FLAG_DAG_ONLY if dag_only else 0)
     sec = ctypes.c_double(0)
     p = (lib_O0() if O0 else lib()).oracle_run_bfb(lh.encode(), juncs.encode(), ",".join(sols).encode(), flags, max_orders,
                                                      ctypes.byref(sec))
@@ -81,6 +85,26 @@ def run_bfb(lh, sols, juncs="", reversed_=False, all_=False, junc_info=False, ke
         for c in out["chr"]:
             c["all_paths"] = [c["all_paths_unique"][i] for i in c["all_paths_ref"]]
     return out
+
+
+def prepare_raw(seg_cn, j_src, j_sdir, j_tgt, j_tdir, j_cn):
+    """getJuncCN, the bias, getIndelBias and the fold-back sum of ONE chromosome given as arrays (segments 1..n, the junctions as
+    listed, directions +1 / -1): the oracle's own functions on a graph no reader has deduplicated.  Returns numpy arrays
+    junc_cn (n+1, 2), seg_cn (n+1, [0] unused), inv_junc (n+1) and bias, inv_sum."""
+    import numpy as np
+    n, m = len(seg_cn), len(j_src)
+    sc = np.ascontiguousarray(seg_cn, np.float64)
+    js, jt = np.ascontiguousarray(j_src, np.int32), np.ascontiguousarray(j_tgt, np.int32)
+    sd, td = np.ascontiguousarray(j_sdir, np.int8), np.ascontiguousarray(j_tdir, np.int8)
+    jc = np.ascontiguousarray(j_cn, np.float64)
+    out_j, out_s, out_i = np.zeros(2 * (n + 1)), np.zeros(n + 1), np.zeros(n + 1, np.int32)
+    bias, inv_sum = ctypes.c_int(0), ctypes.c_double(0)
+    L = lib()
+    L.oracle_prepare_raw.restype = None
+    L.oracle_prepare_raw.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 8 + [ctypes.c_void_p, ctypes.c_void_p]
+    L.oracle_prepare_raw(n, sc.ctypes.data, m, js.ctypes.data, sd.ctypes.data, jt.ctypes.data, td.ctypes.data, jc.ctypes.data,
+                         out_j.ctypes.data, out_s.ctypes.data, out_i.ctypes.data, ctypes.addressof(bias), ctypes.addressof(inv_sum))
+    return dict(junc_cn=out_j.reshape(-1, 2), seg_cn=out_s, inv_junc=out_i, bias=bias.value, inv_sum=inv_sum.value)
 
 
 def run_sc_bfb(lhs, sols, reversed_=False, all_=False, max_orders=0):
