@@ -107,6 +107,15 @@ def _declare(L):
         "ambi_batch_unit_profile": (C.c_int, [vp, i32, _P(UnitProfile)]),
         "ambi_batch_unit_path_cn": (C.c_int, [vp, i32, pi32, pi32, i32]),
         "ambi_batch_profile_device": (C.c_int, [vp, _P(vp), pi64]),
+        "ambi_graph_set_sequences": (C.c_int, [vp, vp, pi64]),
+        "ambi_graph_read_fasta": (C.c_int, [vp, C.c_char_p]),
+        "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
+        "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
+        "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
+        "ambi_batch_sequence_wait": (C.c_int, [vp]),
+        "ambi_batch_unit_sequence_len": (C.c_int, [vp, i32, pi64]),
+        "ambi_batch_unit_sequence": (C.c_int, [vp, i32, i64, i64, vp]),
+        "ambi_batch_sequence_device": (C.c_int, [vp, _P(vp), pi64, pi64, i32]),
         "ambi_batch_unit_result": (C.c_int, [vp, i32, _P(UnitResult)]),
         "ambi_batch_unit_path": (C.c_int, [vp, i32, i32, pi32, i32]),
         "ambi_batch_unit_bkp": (C.c_int, [vp, i32, pi32, i32]),
@@ -229,6 +238,33 @@ class Graph:
         if rc != 0:
             raise AmbiError(self.lib, rc, "read_juncs")
         self._refresh()
+
+    def set_sequences(self, bases, seg_off):
+        """Attaches the segments' bases (ambi_graph_set_sequences): segment id i + 1 = bases[seg_off[i]:seg_off[i + 1]], any byte
+        values; before the chromosomes are added to a batch."""
+        raw = np.frombuffer(bytes(bases), np.uint8) if not isinstance(bases, np.ndarray) else np.ascontiguousarray(bases, np.uint8)
+        off, poff = _arr(seg_off, np.int64)
+        if len(off) != self.n_seg + 1:
+            raise ValueError("seg_off needs n_seg + 1 entries")
+        rc = self.lib.ambi_graph_set_sequences(self.h, C.c_void_p(raw.ctypes.data if raw.size else 0), poff)
+        if rc != 0:
+            raise AmbiError(self.lib, rc, "set_sequences")
+
+    def read_fasta(self, path):
+        """The same store from a FASTA file (ambi_graph_read_fasta): segment = chrom[start:end], 0-based and half-open."""
+        rc = self.lib.ambi_graph_read_fasta(self.h, path.encode())
+        if rc != 0:
+            raise AmbiError(self.lib, rc, "read_fasta(%s)" % path)
+
+    def sequences(self):
+        """(bases as bytes, seg_off int64[n_seg + 1]) of the attached store."""
+        off = np.zeros(self.n_seg + 1, np.int64)
+        n = self.lib.ambi_graph_sequences(self.h, None, 0, off.ctypes.data_as(_P(C.c_int64)))
+        if n < 0:
+            raise AmbiError(self.lib, int(n), "sequences")
+        buf = np.zeros(max(int(n), 1), np.uint8)
+        self.lib.ambi_graph_sequences(self.h, C.c_void_p(buf.ctypes.data), int(n), None)
+        return buf[:n].tobytes(), off
 
     def write_lh(self, path):
         """Graph::writeGraph (Graph.cpp:239-266): the graph as it stands, as .lh text"""
@@ -509,6 +545,42 @@ class Batch:
         self._ck(self.lib.ambi_batch_profile_device(self.h, C.byref(p), C.byref(n)), "profile_device")
         return p.value or 0, n.value
 
+    def set_unit_sequences(self, u, bases, seg_off):
+        """Bases of a unit added with add_unit (ambi_batch_set_unit_sequences): local segment i + 1 = bases[seg_off[i]:seg_off[i + 1]]."""
+        raw = np.frombuffer(bytes(bases), np.uint8) if not isinstance(bases, np.ndarray) else np.ascontiguousarray(bases, np.uint8)
+        off, poff = _arr(seg_off, np.int64)
+        self._ck(self.lib.ambi_batch_set_unit_sequences(self.h, u, C.c_void_p(raw.ctypes.data if raw.size else 0), poff), "set_unit_sequences")
+
+    def sequence(self, which=1, first_unit=0, n_units=None, max_bytes=0, stream=None):
+        """Assembles the nucleotide sequences of the paths of the units [first_unit, first_unit + n_units) on the device
+        (ambi_batch_sequence); AmbiError with code -34 and nothing assembled when they exceed max_bytes > 0."""
+        if n_units is None:
+            n_units = self.size() - first_unit
+        self._ck(self.lib.ambi_batch_sequence(self.h, which, first_unit, n_units, max_bytes, C.c_void_p(stream or 0)), "sequence")
+
+    def sequence_wait(self):
+        self._ck(self.lib.ambi_batch_sequence_wait(self.h), "sequence_wait")
+
+    def unit_sequence_len(self, u):
+        n = C.c_int64()
+        self._ck(self.lib.ambi_batch_unit_sequence_len(self.h, u, C.byref(n)), "unit_sequence_len")
+        return n.value
+
+    def unit_sequence(self, u, first=0, count=None):
+        """bytes [first, first + count) of unit u's sequence (all of it by default), as a bytes object."""
+        if count is None:
+            count = self.unit_sequence_len(u) - first
+        buf = np.zeros(max(count, 1), np.uint8)
+        self._ck(self.lib.ambi_batch_unit_sequence(self.h, u, first, count, C.c_void_p(buf.ctypes.data)), "unit_sequence")
+        return buf[:max(count, 0)].tobytes()
+
+    def sequence_device(self):
+        """(address, bytes, unit_off): the output block in device memory and every unit's byte offset in it (-1: not in the request)."""
+        p, n = C.c_void_p(), C.c_int64()
+        off = np.zeros(self.size(), np.int64)
+        self._ck(self.lib.ambi_batch_sequence_device(self.h, C.byref(p), C.byref(n), off.ctypes.data_as(_P(C.c_int64)), len(off)), "sequence_device")
+        return p.value or 0, n.value, off
+
     def pack_paths(self, which, dev_lengths_ptr, dev_cells_ptr, cell_cap, dev_total_ptr, stream=None):
         self._ck(self.lib.ambi_batch_pack_paths(self.h, which, C.c_void_p(dev_lengths_ptr), C.c_void_p(dev_cells_ptr), cell_cap,
                                                  C.c_void_p(dev_total_ptr), C.c_void_p(stream or 0)), "pack_paths")
@@ -680,12 +752,16 @@ def merge_out_juncs(acc, unit_list, increase=True):
 
 
 def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, first_budget=0, order_arena_bytes=-1,
-                       target_lanes=0, keep_orders=False, profile=False):
+                       target_lanes=0, keep_orders=False, profile=False, ref_fasta=None):
     """Host-side mirror of `Ambigram --op bfb` (localhap.cpp:49-388) with the external `cbc` call replaced by the given
     .sol files (one per chromosome that reaches the ILP, in order).  Returns a dict shaped like the oracle's dump.
     profile=True: every chromosome's dict gains path_cn_fwd / path_cn_rev (traversal counts of the final path per local segment
-    id, slot 0 unused) and profile (the unit's summary), computed on the device (Batch.profile)."""
+    id, slot 0 unused) and profile (the unit's summary), computed on the device (Batch.profile).
+    ref_fasta: every chromosome's dict gains sequence (bytes), the nucleotide sequence of its final path assembled on the device
+    (Batch.sequence) from the segments' bases in that FASTA file (chrom[start:end], 0-based and half-open)."""
     g = Graph(lib, lh)
+    if ref_fasta:
+        g.read_fasta(ref_fasta)
     trx_before = g.trx_before() is not None
     if trx_before:   # PROP I1 / C1: the reference leaves the rebuilt graph in ./new.lh (and says "write seg"); here: a scratch file
         import tempfile
@@ -722,6 +798,8 @@ def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, fir
     b.runs_to_host(1, 0); b.runs_wait(0)
     if profile:
         b.profile(1); b.profile_wait()
+    if ref_fasta:
+        b.sequence(1); b.sequence_wait()
     res = dict(ok=True, err="", log=log, chr=[], paths=[], out_juncs=[], trx_run=False, trx_path=[])
     out_acc = []
     for c in range(g.n_chr):
@@ -745,6 +823,8 @@ def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, fir
         if profile:
             fwd, rev = b.unit_path_cn(c, e - s + 1)
             st.update(path_cn_fwd=fwd, path_cn_rev=rev, profile=b.unit_profile(c))
+        if ref_fasta:
+            st["sequence"] = b.unit_sequence(c)
         if r["status"] == ST_OK:
             pat, loop, succ = b.unit_dag(c, r["n_nodes"])
             st.update(node2pat=pat.tolist(), node2loop=loop.tolist(), succ=[int(x) for x in succ])

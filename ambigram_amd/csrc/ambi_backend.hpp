@@ -8,6 +8,7 @@
 
 #include "ambi_pack.hpp"
 #include "ambi_profile.hpp"
+#include "ambi_sequence.hpp"
 
 namespace ambi {
 
@@ -131,13 +132,91 @@ class Backend {
         return n + 1;
     }
 
+    // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
+    // sequence() runs pass 0 of the extents stage behind the last run and fetches its totals (count x {bytes, runs}: the one small
+    // device-to-host trip of a request), sizes the extent arrays and the output block from them, and queues pass 1 and the fill
+    // stage; kSeqTooLarge, with nothing assembled and the lengths readable, when the lengths sum to more than max_bytes > 0.
+    // sequence_wait() makes the results final and assembles once more if that moved them.  The default runs the stages on the host
+    // over the downloaded blob (the host simulation); the HIP engine overrides the four virtual entries.  The batch's sequence
+    // image (HostBatch::seq of the bound inputs) must be sealed.
+    virtual int sequence(int which, int first, int count, int64_t max_bytes, void* stream) {
+        (void)stream;
+        seq_state_ = 0; seq_queued_ = false;
+        if (!prof_hb_ || !prof_hb_->seq.any || which < 0 || which > 1 || first < 0 || count < 1 || (size_t)first + (size_t)count > prof_hb_->units.size()) return ST_ERR_BAD_INPUT;
+        std::vector<uint8_t> blob;
+        if (int rc = download(blob)) return rc;
+        const SeqImage& I = prof_hb_->seq;
+        const SeqArgs S{I.bases.data(), I.seg_pos.data(), I.store_off.data(), I.pos_off.data()};
+        std::vector<int64_t> totals((size_t)(2 * count));
+        SeqPlan Q{};
+        Q.first = first; Q.count = count; Q.totals = totals.data();
+        HostGroup g;
+        for (int r = 0; r < count; r++) seq_extents_unit(g, prof_hb_->units.data(), blob.data(), S, Q, r, which, 0);
+        seq_layout(totals.data(), count, seq_lay_);
+        seq_first_ = first; seq_count_ = count; seq_state_ = 1;
+        if (max_bytes > 0 && seq_lay_.seq_bytes > max_bytes) return kSeqTooLarge;
+        std::vector<int64_t> ext_src((size_t)seq_lay_.slots), ext_out((size_t)seq_lay_.slots);
+        seq_out_.assign((size_t)(seq_lay_.out_bytes / 16), Seq16A{});
+        Q.ext_off = seq_lay_.ext_off.data(); Q.ext_src = ext_src.data(); Q.ext_out = ext_out.data();
+        Q.out_off = seq_lay_.out_off.data(); Q.tile_off = seq_lay_.tile_off.data();
+        Q.out = reinterpret_cast<uint8_t*>(seq_out_.data()); Q.out_bytes = seq_lay_.out_bytes;
+        for (int r = 0; r < count; r++) seq_extents_unit(g, prof_hb_->units.data(), blob.data(), S, Q, r, which, 1);
+        uint8_t table[256];
+        seq_build_table(g, table);
+        SeqCursor cur;
+        for (int64_t t = 0; t < seq_lay_.tiles; t++) seq_fill_tile(g, S, Q, table, t, cur);
+        seq_queued_ = true;
+        return 0;
+    }
+    virtual int sequence_wait() {
+        if (seq_state_ < 1 || !seq_queued_) return ST_ERR_BAD_INPUT;
+        seq_state_ = 2;
+        return 0;
+    }
+    // bytes [first, first + count) of a unit's sequence to host memory; valid after sequence_wait()
+    virtual int sequence_copy(int unit, int64_t first, int64_t count, uint8_t* out) {
+        const int r = unit - seq_first_;
+        if (seq_state_ < 2 || r < 0 || r >= seq_count_ || first < 0 || count < 0 || first + count > seq_lay_.len[(size_t)r] || (count > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (count > 0) memcpy(out, reinterpret_cast<const uint8_t*>(seq_out_.data()) + seq_lay_.out_off[(size_t)r] + first, (size_t)count);
+        return 0;
+    }
+    // the output block where it was assembled (device memory of the HIP engine) and every unit's byte offset in it (-1: a unit
+    // outside the request); valid after sequence_wait()
+    virtual int sequence_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) {
+        if (seq_state_ < 2 || !prof_hb_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = seq_out_.data();
+        return sequence_offsets(bytes, unit_off, cap);
+    }
+    // a unit's length: readable from sequence() on (also behind kSeqTooLarge), final after sequence_wait()
+    int sequence_len(int unit, int64_t* len) const {
+        const int r = unit - seq_first_;
+        if (seq_state_ < 1 || r < 0 || r >= seq_count_ || !len) return ST_ERR_BAD_INPUT;
+        *len = seq_lay_.len[(size_t)r];
+        return 0;
+    }
+    void sequence_reset() { seq_state_ = 0; seq_queued_ = false; }
+    void sequence_drop() { seq_queued_ = false; if (seq_state_ > 1) seq_state_ = 1; }   // the lengths stay, what was assembled is not read
+    bool sequence_known() const { return seq_state_ >= 1; }
+
   protected:
+    int sequence_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
+        const int U = (int)prof_hb_->units.size();
+        if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
+        if (bytes) *bytes = seq_lay_.out_bytes;
+        if (unit_off) for (int u = 0; u < U; u++) unit_off[u] = (u < seq_first_ || u >= seq_first_ + seq_count_) ? -1 : seq_lay_.out_off[(size_t)(u - seq_first_)];
+        return 0;
+    }
+    SeqLayout seq_lay_;                  // of the last request
+    int seq_first_ = 0, seq_count_ = 0;
+    int seq_state_ = 0;                  // 0: no request; 1: lengths known; 2: sequence_wait() has returned, the getters answer
+    bool seq_queued_ = false;            // the stages of the last request have been queued (false behind kSeqTooLarge)
     const HostBatch* prof_hb_ = nullptr;
     std::vector<int64_t> prof_off_;      // byte offset of every unit's fwd array in the profile block (profile_block_layout)
     int64_t prof_bytes_ = 0;             // bytes of the block
     const uint8_t* prof_view_ = nullptr; // the block in host memory once profile_wait() has returned (nullptr: no profile to read)
   private:
     std::vector<uint8_t> prof_blob_;     // the default implementation's block
+    std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };
 
 Backend* make_backend();   // defined by the linked backend

@@ -116,6 +116,8 @@ struct ambi_batch {
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
     bool profiled = false;    // ambi_batch_profile_wait has returned for the last run: the profile getters answer
+    bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
+    int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
 };
 
@@ -149,6 +151,7 @@ const char* ambi_error_string(int code) {
         case AMBI_ERR_HIP: return "HIP runtime error";
         case AMBI_ERR_STATE: return "call order violated";
         case AMBI_ERR_ARG: return "bad argument";
+        case AMBI_ERR_TOO_LARGE: return "the sequences of the unit range exceed max_bytes";
         default: return lh_error_string(code);
     }
 }
@@ -224,6 +227,23 @@ int ambi_graph_chromosome(const ambi_graph_t* g, int32_t chr, int32_t* source_id
 int ambi_graph_read_juncs(ambi_graph_t* g, const char* juncs_path) {
     if (!g) return AMBI_ERR_ARG;
     return read_juncs(g->g, juncs_path ? juncs_path : "");
+}
+int ambi_graph_set_sequences(ambi_graph_t* g, const uint8_t* bases, const int64_t* seg_off) {
+    if (!g || !seg_off) return AMBI_ERR_ARG;
+    return set_sequences(g->g, bases, seg_off) ? 0 : AMBI_ERR_ARG;
+}
+int ambi_graph_read_fasta(ambi_graph_t* g, const char* fasta_path) {
+    if (!g || !fasta_path) return AMBI_ERR_ARG;
+    return read_fasta(g->g, fasta_path);
+}
+int64_t ambi_graph_sequences(const ambi_graph_t* g, uint8_t* bases, int64_t cap, int64_t* seg_off) {
+    if (!g) return AMBI_ERR_ARG;
+    const LhGraph& G = g->g;
+    if (G.seq_off.empty()) return AMBI_ERR_STATE;
+    if (seg_off) memcpy(seg_off, G.seq_off.data(), G.seq_off.size() * sizeof(int64_t));
+    const int64_t n = (int64_t)G.seq_bases.size();
+    if (bases && cap > 0 && n > 0) memcpy(bases, G.seq_bases.data(), (size_t)(n < cap ? n : cap));
+    return n;
 }
 int64_t ambi_graph_log(const ambi_graph_t* g, char* buf, int64_t cap) {
     if (!g) return AMBI_ERR_ARG;
@@ -409,13 +429,15 @@ int ambi_batch_upload(ambi_batch_t* b) {
     b->be->profile_bind(&b->hb);
     int rc = b->be->upload(b->hb, b->cfg);
     if (rc == 0) b->uploaded = true;
-    b->ran = false; b->profiled = false;
+    b->ran = false; b->profiled = false; b->sequenced = false;
+    b->be->sequence_reset();
     return rc;
 }
 int ambi_batch_run(ambi_batch_t* b, uint32_t flags, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!b->uploaded) return AMBI_ERR_STATE;
-    b->downloaded = false; b->mail_view = false; b->profiled = false;
+    b->downloaded = false; b->mail_view = false; b->profiled = false; b->sequenced = false;
+    b->be->sequence_reset();
     const int rc = b->be->run(flags, hip_stream);
     if (rc == 0) b->ran = true;
     return rc;
@@ -478,7 +500,8 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
         for (auto& s : b->shards) s->hb.finalize();
     }
     b->hb.finalize();
-    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled = false;
+    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled = false; b->sequenced = false;
+    for (auto& s : b->shards) s->be->sequence_reset();
     // every share on its own (resident) thread, the first one too: set_device changes the current device of the thread that calls it,
     // and the caller's thread keeps the device it had.  Nothing is merged: the getters read a unit where its share left it.
     for (auto& s : b->shards) s->start(flags, &b->cfg);
@@ -663,6 +686,93 @@ int ambi_batch_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) {
     if (!b) return AMBI_ERR_ARG;
     if (!b->profiled || b->sharded_ready) return AMBI_ERR_STATE;
     return b->be->profile_device(dev_ptr, bytes) ? AMBI_ERR_STATE : 0;
+}
+// ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
+int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size() || !seg_off || seg_off[0] < 0) return AMBI_ERR_ARG;
+    if (!b->shards.empty()) return AMBI_ERR_STATE;   // (the shares hold copies of their units' bases)
+    const int n = b->hb.units[unit].n_seg;
+    for (int i = 0; i < n; i++) if (seg_off[i + 1] < seg_off[i]) return AMBI_ERR_ARG;
+    if (!bases && seg_off[n] > seg_off[0]) return AMBI_ERR_ARG;
+    b->hb.seq.set((size_t)unit, n, bases, seg_off);
+    b->sequenced = false;
+    b->be->sequence_reset();
+    return 0;
+}
+// the units of [first, first + count) a share holds: a range of its local units (the units are dealt in order)
+static bool share_range(const ambi_batch_t* b, int k, int first, int count, int* lfirst, int* lcount) {
+    int lo = -1, hi = -1;
+    for (int u = first; u < first + count; u++)
+        if (b->where[u].first == k) { if (lo < 0) lo = b->where[u].second; hi = b->where[u].second; }
+    *lfirst = lo; *lcount = hi - lo + 1;
+    return lo >= 0;
+}
+int ambi_batch_sequence(ambi_batch_t* b, int32_t which, int32_t first_unit, int32_t n_units, int64_t max_bytes, void* hip_stream) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!(b->sharded_ready || (b->uploaded && b->ran)) || !b->hb.seq.any) return AMBI_ERR_STATE;
+    if (which < 0 || which > 1 || first_unit < 0 || n_units < 1 || (int64_t)first_unit + n_units > (int64_t)b->hb.units.size()) return AMBI_ERR_ARG;
+    b->sequenced = false; b->seq_first = first_unit; b->seq_count = n_units;
+    if (!b->sharded_ready) {
+        b->hb.seq.seal(b->hb.units);
+        const int rc = b->be->sequence(which, first_unit, n_units, max_bytes, hip_stream);
+        return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc;
+    }
+    int64_t total = 0;
+    for (size_t k = 0; k < b->shards.size(); k++) {   // every share on its own stream (the backend selects its device for the call)
+        Shard& s = *b->shards[k];
+        s.be->sequence_reset();
+        int lf, lc;
+        if (!share_range(b, (int)k, first_unit, n_units, &lf, &lc)) continue;
+        s.hb.seq.seal(s.hb.units);
+        s.hb.seq.any = true;   // (the batch has bases; a share whose units have none holds sealed units of length 0, as an unsharded batch does)
+        const int rc = s.be->sequence(which, lf, lc, max_bytes, s.be->own_stream());
+        if (rc && rc != kSeqTooLarge) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc;
+        for (int l = lf; l < lf + lc; l++) { int64_t len = 0; if (s.be->sequence_len(l, &len) == 0) total += len; }
+        if (rc == kSeqTooLarge) total = max_bytes + 1;
+    }
+    if (max_bytes > 0 && total > max_bytes) {   // the shares' lengths stay readable; what some of them assembled is not
+        for (auto& s : b->shards) s->be->sequence_drop();
+        return AMBI_ERR_TOO_LARGE;
+    }
+    return 0;
+}
+int ambi_batch_sequence_wait(ambi_batch_t* b) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
+    if (!b->sharded_ready) { if (int rc = b->be->sequence_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
+    else {
+        bool some = false;
+        for (size_t k = 0; k < b->shards.size(); k++) {
+            int lf, lc;
+            if (b->seq_count < 1 || !share_range(b, (int)k, b->seq_first, b->seq_count, &lf, &lc)) continue;
+            if (int rc = b->shards[k]->be->sequence_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc;
+            some = true;
+        }
+        if (!some) return AMBI_ERR_STATE;
+    }
+    b->sequenced = true;
+    return 0;
+}
+int ambi_batch_unit_sequence_len(const ambi_batch_t* b, int32_t unit, int64_t* bases) {
+    if (!b || !bases || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    if (!be->sequence_known()) return AMBI_ERR_STATE;
+    return be->sequence_len(local, bases) ? AMBI_ERR_ARG : 0;   // (a unit outside the request)
+}
+int ambi_batch_unit_sequence(ambi_batch_t* b, int32_t unit, int64_t first, int64_t count, uint8_t* out) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size() || first < 0 || count < 0) return AMBI_ERR_ARG;
+    if (!b->sequenced) return AMBI_ERR_STATE;
+    int local = unit;
+    Backend* be = b->owner(unit, &local);
+    const int rc = be->sequence_copy(local, first, count, out);
+    return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_ARG : rc;
+}
+int ambi_batch_sequence_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!b->sequenced || b->sharded_ready) return AMBI_ERR_STATE;
+    if (unit_off && cap < (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    return b->be->sequence_device(dev_ptr, bytes, unit_off, cap) ? AMBI_ERR_STATE : 0;
 }
 int ambi_batch_unit_bkp(const ambi_batch_t* b, int32_t unit, int32_t* out, int32_t cap) {
     const UnitOut* h = header(b, unit);

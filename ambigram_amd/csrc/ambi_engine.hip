@@ -593,6 +593,30 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_path_profile_kernel(Batc
         __syncthreads();
     }
 }
+// ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
+// Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
+// reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
+__global__ __launch_bounds__(kSeqTileLanes) void ambi_seq_extents_kernel(BatchArgs A, SeqArgs S, SeqPlan Q, int which, int pass) {
+    __shared__ __align__(16) int scratch[40];   // (exscan_i64: 16 wave totals of 8 bytes)
+    BlockGroup g(scratch);
+    for (int r = (int)blockIdx.x; r < Q.count; r += (int)gridDim.x) {
+        seq_extents_unit(g, A.units, A.results, S, Q, r, which, pass);
+        __syncthreads();
+    }
+}
+// Fill: workgroups of 256 threads, each over a CONTIGUOUS span of tiles of 4 KB of output (the cursor of ambi_sequence.hpp finds a
+// tile's unit and runs from the tile before); 256 bytes of group memory for the complement table.
+// Store-bound by design: one 16-byte store per lane, the source mostly an L2 hit (a unit's store is read once per crossing).
+__global__ __launch_bounds__(kSeqTileLanes) void ambi_seq_fill_kernel(SeqArgs S, SeqPlan Q, int64_t n_tiles) {
+    __shared__ __align__(16) uint8_t table[256];
+    BlockGroup g(nullptr);   // (no exchange between the threads behind the table)
+    seq_build_table(g, table);
+    __syncthreads();
+    const int64_t per = (n_tiles + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x, t0 = (int64_t)blockIdx.x * per;
+    const int64_t t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+    SeqCursor cur;
+    for (int64_t t = t0; t < t1; t++) seq_fill_tile(g, S, Q, table, t, cur);
+}
 // one wavefront per run
 __global__ __launch_bounds__(256) void ambi_expand_runs_kernel(const int32_t* run_start, const int32_t* run_len, const int64_t* cell_off, int64_t n_runs,
                                                                int32_t* cells, int64_t cap) {
@@ -700,12 +724,20 @@ struct Lease {
     uint8_t* d_prof = nullptr; int64_t d_prof_bytes = 0;
     uint8_t* h_prof = nullptr; int64_t h_prof_bytes = 0;
     hipEvent_t ev_prof_src = nullptr, ev_prof_packed = nullptr, ev_prof_done = nullptr;
+    // path sequences (HipBackend::sequence): the batch's sequence image [bases][seg_pos][store_off][pos_off], the working block of a
+    // request [totals][ext_off, out_off, tile_off][ext_src][ext_out] and the output block; the pinned twin carries the image up, the
+    // totals down and the three offset tables up.  Events: the run's stream reached / all queued work done / timing pairs
+    uint8_t* d_seq_img = nullptr; int64_t d_seq_img_bytes = 0;
+    uint8_t* d_seq_work = nullptr; int64_t d_seq_work_bytes = 0;
+    uint8_t* d_seq_out = nullptr; int64_t d_seq_out_bytes = 0;
+    uint8_t* h_seq = nullptr; int64_t h_seq_bytes = 0;
+    hipEvent_t ev_seq_src = nullptr, ev_seq_done = nullptr, ev_seq_t[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pass 0: [0, 1]; pass 1: [2, 3]; fill: [3, 4]
     std::vector<TimingEvents> evs;
     long uses = 0;
     int32_t seq = 0;   // run sequence numbers (the kernels report completion by storing the run's number into a pinned word)
 };
 // what stays cached in a lease between batches (larger blocks go back to the device when the batch is destroyed)
-constexpr int64_t kKeepBlock = 64ll << 20, kKeepArena = 256ll << 20, kKeepCells = 64ll << 20, kKeepStage = 16ll << 20, kKeepMail = 8ll << 20, kKeepRuns = 16ll << 20, kKeepProfile = 16ll << 20;
+constexpr int64_t kKeepBlock = 64ll << 20, kKeepArena = 256ll << 20, kKeepCells = 64ll << 20, kKeepStage = 16ll << 20, kKeepMail = 8ll << 20, kKeepRuns = 16ll << 20, kKeepProfile = 16ll << 20, kKeepSeq = 64ll << 20;
 
 class DevicePool {
     std::mutex mu_;                       // the free list and the contexts' table: never held during a probe
@@ -998,6 +1030,8 @@ class HipBackend : public Backend {
         if (inflight_) { (void)hipStreamSynchronize(stream_); inflight_ = false; }
         for (hipStream_t s : {side_.lean, side_.full, side_.scan, lease_->copy_stream, lease_->run_stream}) if (s) (void)hipStreamSynchronize(s);
         if (prof_queued_ && prof_stream_ != stream_) (void)hipStreamSynchronize(prof_stream_);   // (a profile queued on another stream than the run's)
+        if (seq_busy_ && seq_stream_ != stream_) (void)hipStreamSynchronize(seq_stream_);          // (and a sequence request)
+        seq_busy_ = false;
         prof_queued_ = false;
         (void)hipGetLastError();
     }
@@ -1042,12 +1076,16 @@ class HipBackend : public Backend {
             }
             if (L->d_prof_bytes > kKeepProfile) { (void)hipFree(L->d_prof); L->d_prof = nullptr; L->d_prof_bytes = 0; }
             if (L->h_prof_bytes > kKeepProfile) { (void)hipHostFree(L->h_prof); L->h_prof = nullptr; L->h_prof_bytes = 0; }
+            for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
+                if (*pb.second > kKeepSeq) { (void)hipFree(*pb.first); *pb.first = nullptr; *pb.second = 0; }
+            if (L->h_seq_bytes > kKeepSeq) { (void)hipHostFree(L->h_seq); L->h_seq = nullptr; L->h_seq_bytes = 0; }
             lease_ = nullptr;
             DevicePool::get().release(L);
         }
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
         prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
+        sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
 
@@ -1113,6 +1151,7 @@ class HipBackend : public Backend {
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
         prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
+        sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
         hbp_ = &hb_in; cfg_ = cfg;
@@ -2134,6 +2173,137 @@ class HipBackend : public Backend {
         if (ptr) *ptr = lease_->d_prof;
         if (bytes) *bytes = prof_bytes_;
         return 0;
+    }
+    // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----
+    // sequence() works on `stream` behind everything that writes the result blob in the last run, as profile_queue does: the
+    // sequence image if the device does not hold this version of it (pinned twin, one copy), pass 0 of the extents kernel, the
+    // totals to the pinned twin and ONE stream synchronisation -- the small device-to-host trip that sizes the extent arrays and the
+    // output block (an on-request call: the run it follows is complete by then) -- the three offset tables up, pass 1 and the fill
+    // kernel.  sequence_wait() makes the results final (wait()) and, if that moved their epoch, does all of it once more.
+    bool seq_busy_ = false, seq_timed_ = false;
+    int64_t seq_img_version_ = -1, seq_epoch_ = -1, seq_max_ = 0;
+    int seq_which_ = 1; hipStream_t seq_stream_ = nullptr;
+    SeqArgs seq_args_{};
+    int sequence_image(hipStream_t s) {
+        Lease* L = lease_;
+        const SeqImage& I = hb().seq;
+        const int64_t U = (int64_t)hb().units.size();
+        if ((int64_t)I.store_off.size() != U || (int64_t)I.pos_off.size() != U) return ST_ERR_BAD_INPUT;   // (not sealed)
+        const int64_t b0 = pad16((int64_t)I.bases.size()), b1 = b0 + 8 * (int64_t)I.seg_pos.size(), b2 = b1 + 8 * U, total = b2 + 8 * U;
+        if (seq_img_version_ != I.version || !L->d_seq_img) {
+            if (int rc = lease_device_block(&L->d_seq_img, &L->d_seq_img_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&L->h_seq, nullptr, &L->h_seq_bytes, std::max<int64_t>(total, 40 * U + 64))) return rc;
+            if (!I.bases.empty()) memcpy(L->h_seq, I.bases.data(), I.bases.size());
+            memcpy(L->h_seq + b0, I.seg_pos.data(), 8 * I.seg_pos.size());
+            memcpy(L->h_seq + b1, I.store_off.data(), (size_t)(8 * U));
+            memcpy(L->h_seq + b2, I.pos_off.data(), (size_t)(8 * U));
+            HIP_CK(hipMemcpyAsync(L->d_seq_img, L->h_seq, (size_t)total, hipMemcpyHostToDevice, s));
+            seq_img_version_ = I.version;
+        }
+        seq_args_ = SeqArgs{L->d_seq_img, reinterpret_cast<const int64_t*>(L->d_seq_img + b0), reinterpret_cast<const int64_t*>(L->d_seq_img + b1),
+                            reinterpret_cast<const int64_t*>(L->d_seq_img + b2)};
+        return 0;
+    }
+    int sequence_queue(int which, int first, int count, int64_t max_bytes, hipStream_t s) {
+        Lease* L = lease_;
+        for (hipEvent_t* e : {&L->ev_seq_src, &L->ev_seq_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        // an earlier request nobody waited for still uses the blocks, and its table upload reads the pinned twin the host writes below
+        if (seq_busy_) { HIP_CK(hipEventSynchronize(L->ev_seq_done)); seq_busy_ = false; }
+        seq_state_ = 0; seq_queued_ = false;
+        seq_which_ = which; seq_first_ = first; seq_count_ = count; seq_max_ = max_bytes; seq_stream_ = s; seq_epoch_ = epoch_;
+        if (int rc = sequence_image(s)) return rc;
+        if (s != stream_) { HIP_CK(hipEventRecord(L->ev_seq_src, stream_)); HIP_CK(hipStreamWaitEvent(s, L->ev_seq_src, 0)); }
+        if (overlap_back_) {
+            HIP_CK(hipStreamWaitEvent(s, ev_back_, 0));
+            if (direct_n_ > 0) HIP_CK(hipStreamWaitEvent(s, ev_full_, 0));
+        }
+        if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
+        // working block: [totals: 2 count] [ext_off: count + 1] [out_off: count] [tile_off: count + 1] | [ext_src: slots] [ext_out: slots]
+        const int64_t c = count, tab = 16 * c, head = pad16(tab + 8 * (3 * c + 2));
+        if (int rc = lease_device_block(&L->d_seq_work, &L->d_seq_work_bytes, head)) return rc;
+        SeqPlan Q{};
+        Q.first = first; Q.count = count; Q.totals = reinterpret_cast<int64_t*>(L->d_seq_work);
+        const int ugrid = (int)(c < 16384 ? c : 16384);
+        seq_timed_ = timing_;
+        if (seq_timed_) { for (int k = 0; k < 5; k++) if (!L->ev_seq_t[k]) HIP_CK(hipEventCreate(&L->ev_seq_t[k])); HIP_CK(hipEventRecord(L->ev_seq_t[0], s)); }
+        hipLaunchKernelGGL(ambi_seq_extents_kernel, dim3(ugrid), dim3(kSeqTileLanes), 0, s, A_, seq_args_, Q, which, 0);
+        HIP_CK(hipGetLastError());
+        if (seq_timed_) HIP_CK(hipEventRecord(L->ev_seq_t[1], s));
+        seq_busy_ = true;
+        HIP_CK(hipMemcpyAsync(L->h_seq, L->d_seq_work, (size_t)tab, hipMemcpyDeviceToHost, s));
+        HIP_CK(hipStreamSynchronize(s));
+        seq_busy_ = false;
+        seq_layout(reinterpret_cast<const int64_t*>(L->h_seq), count, seq_lay_);
+        seq_state_ = 1;
+        if (max_bytes > 0 && seq_lay_.seq_bytes > max_bytes) return kSeqTooLarge;
+        // (s is idle and nothing of an earlier request is in flight: the blocks may move)
+        if (int rc = lease_device_block(&L->d_seq_work, &L->d_seq_work_bytes, head + 16 * seq_lay_.slots)) return rc;
+        if (int rc = lease_device_block(&L->d_seq_out, &L->d_seq_out_bytes, seq_lay_.out_bytes + 16)) return rc;
+        int64_t* ht = reinterpret_cast<int64_t*>(L->h_seq + tab);
+        memcpy(ht, seq_lay_.ext_off.data(), (size_t)(8 * (c + 1)));
+        memcpy(ht + c + 1, seq_lay_.out_off.data(), (size_t)(8 * c));
+        memcpy(ht + 2 * c + 1, seq_lay_.tile_off.data(), (size_t)(8 * (c + 1)));
+        // (the totals travel back with the tables: growing the working block above has dropped the device's copy)
+        HIP_CK(hipMemcpyAsync(L->d_seq_work, L->h_seq, (size_t)(tab + 8 * (3 * c + 2)), hipMemcpyHostToDevice, s));
+        int64_t* dt = reinterpret_cast<int64_t*>(L->d_seq_work + tab);
+        Q.totals = reinterpret_cast<int64_t*>(L->d_seq_work);
+        Q.ext_off = dt; Q.out_off = dt + c + 1; Q.tile_off = dt + 2 * c + 1;
+        Q.ext_src = reinterpret_cast<int64_t*>(L->d_seq_work + head); Q.ext_out = Q.ext_src + seq_lay_.slots;
+        Q.out = L->d_seq_out; Q.out_bytes = seq_lay_.out_bytes;
+        if (seq_timed_) HIP_CK(hipEventRecord(L->ev_seq_t[2], s));
+        hipLaunchKernelGGL(ambi_seq_extents_kernel, dim3(ugrid), dim3(kSeqTileLanes), 0, s, A_, seq_args_, Q, which, 1);
+        HIP_CK(hipGetLastError());
+        if (seq_timed_) HIP_CK(hipEventRecord(L->ev_seq_t[3], s));
+        if (seq_lay_.tiles > 0) {
+            const int64_t fgrid = seq_lay_.tiles < 4096 ? seq_lay_.tiles : 4096;   // (16 workgroups per CU; a workgroup builds its table once)
+            hipLaunchKernelGGL(ambi_seq_fill_kernel, dim3((unsigned)fgrid), dim3(kSeqTileLanes), 0, s, seq_args_, Q, seq_lay_.tiles);
+            HIP_CK(hipGetLastError());
+        }
+        if (seq_timed_) HIP_CK(hipEventRecord(L->ev_seq_t[4], s));
+        HIP_CK(hipEventRecord(L->ev_seq_done, s));
+        seq_busy_ = true; seq_queued_ = true;
+        return 0;
+    }
+    int sequence(int which, int first, int count, int64_t max_bytes, void* stream) override {
+        DeviceGuard dg_(device_);
+        seq_state_ = 0; seq_queued_ = false;
+        if (!ran_ || !lease_ || !hb().seq.any || which < 0 || which > 1 || first < 0 || count < 1 || (size_t)first + (size_t)count > hb().units.size()) return ST_ERR_BAD_INPUT;
+        prof_hb_ = hbp_;
+        return sequence_queue(which, first, count, max_bytes, (hipStream_t)stream);
+    }
+    int sequence_wait() override {
+        DeviceGuard dg_(device_);
+        if (seq_state_ < 1 || !seq_queued_) return ST_ERR_BAD_INPUT;
+        if (int rc = wait()) return rc;
+        if (epoch_ != seq_epoch_) { if (int rc = sequence_queue(seq_which_, seq_first_, seq_count_, seq_max_, seq_stream_)) return rc; }
+        HIP_CK(hipEventSynchronize(lease_->ev_seq_done));
+        seq_busy_ = false;
+        seq_state_ = 2;
+        if (seq_timed_) {
+            // the extents kernel's figure is the SUM of its two launches (pass 0 + pass 1)
+            float p0 = -1.f, p1 = -1.f, fill = -1.f;
+            if (hipEventElapsedTime(&p0, lease_->ev_seq_t[0], lease_->ev_seq_t[1]) != hipSuccess) p0 = -1.f;
+            if (hipEventElapsedTime(&p1, lease_->ev_seq_t[2], lease_->ev_seq_t[3]) != hipSuccess) p1 = -1.f;
+            if (hipEventElapsedTime(&fill, lease_->ev_seq_t[3], lease_->ev_seq_t[4]) != hipSuccess) fill = -1.f;
+            const float ext = (p0 >= 0 && p1 >= 0) ? p0 + p1 : -1.f;
+            (void)hipGetLastError();
+            while (!times_.empty() && !strncmp(times_.back().name, "ambi_seq_", 9)) times_.pop_back();
+            times_.push_back({"ambi_seq_extents_kernel", ext});
+            times_.push_back({"ambi_seq_fill_kernel", fill});
+        }
+        return 0;
+    }
+    int sequence_copy(int unit, int64_t first, int64_t count, uint8_t* out) override {
+        DeviceGuard dg_(device_);
+        const int r = unit - seq_first_;
+        if (seq_state_ < 2 || !lease_ || r < 0 || r >= seq_count_ || first < 0 || count < 0 || first + count > seq_lay_.len[(size_t)r] || (count > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (count > 0) HIP_CK(hipMemcpy(out, lease_->d_seq_out + seq_lay_.out_off[(size_t)r] + first, (size_t)count, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int sequence_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) override {
+        if (seq_state_ < 2 || !lease_ || !prof_hb_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->d_seq_out;
+        return sequence_offsets(bytes, unit_off, cap);
     }
     int copy_orders(int unit, int64_t first, int64_t count, uint8_t* out) override {
         DeviceGuard dg_(device_);

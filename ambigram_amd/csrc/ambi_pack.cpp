@@ -116,6 +116,8 @@ int HostBatch::add_graph_chr(const LhGraph& g, int chr, const SolFile* sol, int 
     int u = add_unit(n, base, cn.data(), (int)js.size(), js.data(), jt.data(), jsd.data(), jtd.data(), jc.data(),
                      (int)el_a.size(), el_loop.data(), el_a.data(), el_b.data(), el_cn.data(), infeasible, has_comp);
     if (u >= 0) junc_global[u] = gidx;
+    // the chromosome's bases, back to back in local id order (ambi_sequence.hpp), when the graph carries them
+    if (u >= 0 && (int)g.seq_off.size() == g.n_seg() + 1) seq.set((size_t)u, n, g.seq_bases.data(), g.seq_off.data() + base);
     return u;
 }
 
@@ -134,6 +136,7 @@ int HostBatch::add_unit_from(const HostBatch& src, int u) {
     U.ideal_cap = ideal_cap;
     units.push_back(U);
     junc_global.push_back(src.junc_global[u]);
+    seq.copy_unit(units.size() - 1, U.n_seg, src.seq, (size_t)u);
     if ((size_t)u < src.inject_unit.size() && !src.inject_unit[u].empty()) { inject_unit.resize(units.size()); inject_unit.back() = src.inject_unit[u]; }
     for (int j = 0; j < S.n_junc; j++) {   // (any_sv as add_unit derives it)
         const Junction& J = src.juncs[S.junc_off + j];

@@ -13,8 +13,44 @@ constexpr int kPathCapLimit = 1 << 22;   // cells per unit in the result blob (t
                                          // which edits the path in LDS, is limited to kPathLdsCells)
 constexpr int kDefaultIdealCap = 4096; // slots per unit (holds up to 2048 order ideals)
 
+// Sequence image of a batch (ambi_sequence.hpp): the bases of every unit's segments back to back in local id order, and per
+// unit the int64 prefix seg_pos[0..n] of the segment lengths.  Host memory; a backend takes it to the device at the first
+// sequence request.  A unit without attached bases has an empty store and a prefix of zeros.
+struct SeqImage {
+    std::vector<uint8_t> bases;
+    std::vector<int64_t> seg_pos;      // all units' prefixes one after the other
+    std::vector<int64_t> store_off;    // [U] byte offset of a unit's store in bases
+    std::vector<int64_t> pos_off;      // [U] index of a unit's seg_pos[0]
+    bool any = false;                  // some unit has bases
+    int64_t version = 0;               // moves with every change (a backend re-sends an image it has already taken to the device)
+    // the bases of unit `unit`: local segment i + 1 = src[seg_off[i] .. seg_off[i + 1]) (seg_off ascending); a second call replaces the first
+    void set(size_t unit, int n_seg, const uint8_t* src, const int64_t* seg_off) {
+        if (store_off.size() <= unit) { store_off.resize(unit + 1, 0); pos_off.resize(unit + 1, -1); }
+        store_off[unit] = (int64_t)bases.size();
+        pos_off[unit] = (int64_t)seg_pos.size();
+        for (int i = 0; i <= n_seg; i++) seg_pos.push_back(seg_off[i] - seg_off[0]);
+        if (seg_off[n_seg] > seg_off[0]) bases.insert(bases.end(), src + seg_off[0], src + seg_off[n_seg]);
+        any = true; version++;
+    }
+    // every unit has a prefix afterwards (zeros where nothing was attached); idempotent
+    void seal(const std::vector<UnitIn>& units) {
+        if (store_off.size() < units.size()) { store_off.resize(units.size(), 0); pos_off.resize(units.size(), -1); }
+        for (size_t u = 0; u < units.size(); u++)
+            if (pos_off[u] < 0) { pos_off[u] = (int64_t)seg_pos.size(); seg_pos.insert(seg_pos.end(), (size_t)units[u].n_seg + 1, 0); version++; }
+    }
+    // unit u of another image (ambi_batch_run_sharded deals units to shares)
+    void copy_unit(size_t unit, int n_seg, const SeqImage& from, size_t u) {
+        if (u >= from.pos_off.size() || from.pos_off[u] < 0) return;
+        const int64_t* p = from.seg_pos.data() + from.pos_off[u];
+        std::vector<int64_t> off(p, p + n_seg + 1);
+        for (auto& o : off) o += from.store_off[u];
+        set(unit, n_seg, from.bases.data(), off.data());
+    }
+};
+
 struct HostBatch {
     std::vector<UnitIn> units;
+    SeqImage seq;                      // bases of the units' segments (empty unless sequences were attached)
     std::vector<double> seg_cn;
     std::vector<Junction> juncs;
     std::vector<JuncEnds> junc_ends;   // junc_ends(juncs[i]) of every record

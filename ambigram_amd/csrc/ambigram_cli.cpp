@@ -249,6 +249,13 @@ int run_sc_bfb(Args& A) {
 // --cn_profile <file> (what the reference's commented-out CN.txt writer meant to report, localhap.cpp:318-351): after the run, one
 // tab-separated row per segment -- sample, chromosome name, segment id, start, end, input CN, target CN, forward count, reverse
 // count, count - target -- from the device's copy-number profile of the final paths (ambi_batch_profile); stdout is unchanged.
+// --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
+// chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
+// reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
+// and `>BFBPATH_<chromosome name>` otherwise, the sequence on ONE line.  Every line ends in "\n": the reference's script omits
+// the newline behind the last line (main.py:579-588), a deviation on purpose (a text file ends in a newline; `cat` of two outputs
+// stays a FASTA file).  The units are assembled in chunks of at most --fasta_chunk_bytes (default 256 MiB; a single unit beyond
+// it goes alone); stdout is unchanged.
 struct Sample {
     std::string lh;
     ambi_graph_t* g = nullptr;
@@ -269,6 +276,9 @@ int run_bfb(Args& A) {
     const bool junc_info = truthy(A.kv["junc_info"]), reversed = truthy(A.kv["reversed"]), all = truthy(A.kv["all"]);
     const double solver_timeout = A.kv.count("solver_timeout") ? atof(A.kv["solver_timeout"].c_str()) : 0;   // extension: seconds, 0 = none
     const std::string cn_profile = A.kv.count("cn_profile") ? A.kv["cn_profile"] : "";
+    const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
+    if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
+    const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
     int n_devices = 0;                   // 0: one device, the classic path; > 0: that many; -1: all visible
     std::vector<int32_t> device_list;    // or an explicit list of ordinals "0,1,1" (an ordinal may repeat: several shares on one device)
     if (A.kv.count("devices")) {
@@ -307,6 +317,14 @@ int run_bfb(Args& A) {
                 std::cerr << "--cn_profile: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
                 return 2;
             }
+        }
+        if (!out_fasta.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << "--out_fasta: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device sequence" << std::endl;
+                return 2;
+            }
+            if ((rc = ambi_graph_read_fasta(g, ref_fasta.c_str())) != 0) return die("--ref_fasta " + ref_fasta + ": " + ambi_error_string(rc));
         }
         // PROP I1 / C1 (TRX-BFB, localhap.cpp:79-88): the graph has been rebuilt while loading; the reference leaves it in ./new.lh
         S.trx_before = ambi_graph_trx_before(g, nullptr, 0) > 0;
@@ -403,6 +421,57 @@ int run_bfb(Args& A) {
                 }
             }
         fclose(pf);
+    }
+    if (!out_fasta.empty()) {
+        FILE* ff = fopen(out_fasta.c_str(), "w");
+        if (!ff) return die("Cannot open file " + out_fasta);
+        auto fail = [&](int code) { fclose(ff); return die(std::string("engine: ") + ambi_error_string(code)); };
+        std::vector<std::string> name((size_t)n_units);   // unit -> record name
+        for (Sample& S : samples)
+            for (int c = 0; c < S.n_chr; c++) {
+                int32_t s, e;
+                ambi_graph_chromosome(S.g, c, &s, &e);
+                char nm[256]; ambi_graph_chrom_name(S.g, s, nm, sizeof(nm));
+                name[(size_t)S.unit[c]] = S.n_chr == 1 ? "BFBPATH" : std::string("BFBPATH_") + nm;
+            }
+        std::vector<uint8_t> buf((size_t)(1 << 22));
+        // one request for everything; if that exceeds the budget it assembles nothing and leaves EVERY unit's length readable: the
+        // chunks are planned from them once, each the longest range that fits (a single unit beyond the budget goes alone)
+        std::vector<int64_t> ulen;
+        rc = ambi_batch_sequence(b, 1, 0, n_units, fasta_chunk, nullptr);
+        const bool whole = rc == 0;
+        if (rc == AMBI_ERR_TOO_LARGE) {
+            ulen.resize((size_t)n_units);
+            for (int u = 0; u < n_units; u++) if ((rc = ambi_batch_unit_sequence_len(b, u, &ulen[(size_t)u])) != 0) return fail(rc);
+        } else if (rc != 0) return fail(rc);
+        for (int first = 0; first < n_units;) {
+            int count = n_units - first;
+            if (!whole) {
+                int64_t sum = 0; int fit = 0;
+                for (; fit < count; fit++) {
+                    if (fit > 0 && sum + ulen[(size_t)(first + fit)] > fasta_chunk) break;
+                    sum += ulen[(size_t)(first + fit)];
+                }
+                count = fit;
+                rc = ambi_batch_sequence(b, 1, first, count, 0, nullptr);
+            }
+            if (rc != 0 || (rc = ambi_batch_sequence_wait(b)) != 0) return fail(rc);
+            for (int u = first; u < first + count; u++) {
+                ambi_unit_result_t r; ambi_batch_unit_result(b, u, &r);
+                int64_t len = 0;
+                if ((rc = ambi_batch_unit_sequence_len(b, u, &len)) != 0) return fail(rc);
+                if (r.status < 0 || r.path_indel_len <= 0) continue;   // no path: no record
+                fprintf(ff, ">%s\n", name[(size_t)u].c_str());
+                for (int64_t at = 0; at < len; at += (int64_t)buf.size()) {
+                    const int64_t k = len - at < (int64_t)buf.size() ? len - at : (int64_t)buf.size();
+                    if ((rc = ambi_batch_unit_sequence(b, u, at, k, buf.data())) != 0) return fail(rc);
+                    fwrite(buf.data(), 1, (size_t)k, ff);
+                }
+                fputc('\n', ff);
+            }
+            first += count;
+        }
+        fclose(ff);
     }
     int refused_total = 0;
     for (Sample& S : samples) {
@@ -539,14 +608,22 @@ int main(int argc, char** argv) {
     Args A = parse(argc, argv);
     if (A.help) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
-                     "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>]\n"
+                     "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
+                     "[--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
-                     "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n";
+                     "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
+                     "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
+                     "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";
         return 0;
     }
     const std::string op = A.kv.count("op") ? A.kv["op"] : "";
     std::cout << op << std::endl;   // localhap.cpp:47
+    if (op == "sc_bfb" && (A.kv.count("out_fasta") || A.kv.count("ref_fasta"))) {
+        std::cerr << "--ref_fasta / --out_fasta: --op bfb only" << std::endl;
+        return 2;
+    }
     if (op == "sc_bfb") return run_sc_bfb(A);
     if (op != "bfb") return 0;   // the reference does nothing for any other op (localhap.cpp:49, :390)
     return run_bfb(A);

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -24,6 +25,10 @@ const char* lh_error_string(int code) {
         case LH_ERR_SOL_OPEN: return "ILP error: cannot open file";
         case LH_ERR_LINE_TOO_LONG: return "line longer than 8191 bytes";
         case LH_ERR_UNSUPPORTED: return "TRX-BFB (PROP I1/C1): the reference reads what nothing has set on this input (no junction between the listed chromosomes, a one-vertex path, or a .juncs file with these modes)";
+        case LH_ERR_FASTA_OPEN: return "cannot open the FASTA file";
+        case LH_ERR_FASTA_CHROM: return "a segment's chromosome is not a record of the FASTA file";
+        case LH_ERR_FASTA_RANGE: return "a segment ends beyond its FASTA record";
+        case LH_ERR_FASTA_ORDER: return "a segment's end lies before its start";
         default: return "unknown error";
     }
 }
@@ -680,6 +685,83 @@ void translocation_bfb(const LhGraph& g, std::vector<std::vector<int32_t>>& path
             start_pos = first_of(res, 0, ins.back());
         }
     }
+}
+
+// ---- bases of the segments (script/main.py:709-740 seg2fasta, through our own FASTA reader) ----
+bool set_sequences(LhGraph& g, const uint8_t* bases, const int64_t* seg_off) {
+    const int n = g.n_seg();
+    if (!seg_off || seg_off[0] < 0) return false;
+    for (int i = 0; i < n; i++) if (seg_off[i + 1] < seg_off[i]) return false;
+    if (!bases && seg_off[n] > seg_off[0]) return false;
+    g.seq_off.assign((size_t)n + 1, 0);
+    for (int i = 0; i <= n; i++) g.seq_off[i] = seg_off[i] - seg_off[0];
+    if (seg_off[n] > seg_off[0]) g.seq_bases.assign(bases + seg_off[0], bases + seg_off[n]); else g.seq_bases.clear();
+    return true;
+}
+
+int read_fasta(LhGraph& g, const std::string& path) {
+    const int n = g.n_seg();
+    for (int i = 0; i < n; i++) if (g.seg_end[i] < g.seg_start[i]) return LH_ERR_FASTA_ORDER;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return LH_ERR_FASTA_OPEN;
+    // the records some segment names, one at a time: only their bases are kept while the file is read
+    std::unordered_map<std::string, std::vector<int>> want;
+    for (int i = 0; i < n; i++) want[g.seg_chrom[i]].push_back(i);
+    std::vector<std::vector<uint8_t>> got((size_t)n);
+    std::vector<char> seen((size_t)n, 0);
+    int rc = LH_OK;
+    std::vector<uint8_t> rec;
+    const std::vector<int>* segs = nullptr;   // segments of the record being read (nullptr: nobody wants it)
+    auto close_record = [&]() {
+        if (!segs) return;
+        for (int i : *segs) {
+            if (seen[i]) continue;   // (a name that occurs twice: the first record counts)
+            seen[i] = 1;
+            if (g.seg_start[i] < 0 || (int64_t)g.seg_end[i] > (int64_t)rec.size()) { if (rc == LH_OK) rc = LH_ERR_FASTA_RANGE; continue; }
+            got[i].assign(rec.begin() + g.seg_start[i], rec.begin() + g.seg_end[i]);
+        }
+        segs = nullptr;
+    };
+    std::vector<char> buf(1 << 16);
+    std::string name;
+    bool in_header = false, name_done = false, line_start = true;
+    for (;;) {
+        const size_t k = fread(buf.data(), 1, buf.size(), f);
+        if (k == 0) break;
+        for (size_t j = 0; j < k; j++) {
+            const char c = buf[j];
+            if (in_header) {
+                if (c == '\n') {
+                    in_header = false; line_start = true;
+                    auto it = want.find(name);
+                    segs = it == want.end() ? nullptr : &it->second;
+                    rec.clear();
+                } else if (!name_done) {
+                    if (c == ' ' || c == '\t' || c == '\r') name_done = true; else name += c;
+                }
+                continue;
+            }
+            if (line_start && c == '>') { close_record(); in_header = true; name_done = false; name.clear(); continue; }
+            line_start = c == '\n';
+            if (c == '\n' || c == '\r') continue;
+            if (segs) rec.push_back((uint8_t)c);
+        }
+    }
+    if (in_header) {   // a header without a newline behind it: an empty record
+        auto it = want.find(name);
+        segs = it == want.end() ? nullptr : &it->second;
+        rec.clear();
+    }
+    close_record();
+    fclose(f);
+    if (rc != LH_OK) return rc;
+    for (int i = 0; i < n; i++) if (!seen[i]) return LH_ERR_FASTA_CHROM;
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    for (int i = 0; i < n; i++) off[i + 1] = off[i] + (int64_t)got[i].size();
+    g.seq_bases.clear(); g.seq_bases.reserve((size_t)off[n]);
+    for (int i = 0; i < n; i++) g.seq_bases.insert(g.seq_bases.end(), got[i].begin(), got[i].end());
+    g.seq_off = off;
+    return LH_OK;
 }
 
 }  // namespace ambi

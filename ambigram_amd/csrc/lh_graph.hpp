@@ -45,6 +45,9 @@ struct LhGraph {
     std::vector<std::vector<int32_t>> components;
     // lines the reference prints to stdout while loading (progress, SEG echoes, WARNs, .juncs breakpoints)
     std::vector<std::string> log;
+    // bases of the segments (set_sequences / read_fasta; empty: none): segment id i + 1 = seq_bases[seq_off[i] .. seq_off[i + 1])
+    std::vector<uint8_t> seq_bases;
+    std::vector<int64_t> seq_off;
 
     int n_seg() const { return (int)seg_id.size(); }
     int n_junc() const { return (int)j_src.size(); }
@@ -71,6 +74,11 @@ enum LhError {
     LH_ERR_LINE_TOO_LONG = -8, // > 8191 bytes: the reference's getline(line, 8192) never terminates
     LH_ERR_UNSUPPORTED = -9,   // TRX-BFB (PROP I1 / C1) where the reference reads what nothing has set: no junction between the listed
                                // chromosomes, a one-vertex path, a .juncs file together with these modes
+    // read_fasta (the reference's scripts leave these to bedtools)
+    LH_ERR_FASTA_OPEN = -40,   // cannot open the FASTA file
+    LH_ERR_FASTA_CHROM = -41,  // a segment's chromosome is not a record of the file
+    LH_ERR_FASTA_RANGE = -42,  // a segment ends beyond its record (or starts below 0)
+    LH_ERR_FASTA_ORDER = -43,  // a segment with end < start
 };
 const char* lh_error_string(int code);
 
@@ -80,6 +88,14 @@ void copy_num(LhGraph& g);                                        // Graph.cpp:3
 int read_juncs(LhGraph& g, const std::string& path);
 int write_lh(LhGraph& g, const std::string& path);               // Graph.cpp:239-266 Graph::writeGraph              // LGM.cpp:5096-5156 (needs partitions set)
 void set_partitions(LhGraph& g);                                   // localhap.cpp:94-98
+// Bases of the segments (what script/main.py:709-740 seg2fasta asks bedtools for).  Segment i = chrom[start .. end) of the record
+// whose name (first word behind '>') is the segment's chromosome: 0-based, half-open, end - start bytes, exactly as seg2fasta
+// writes `chr start end` of the .lh into a BED line.  Plain text, no index: any and irregular line widths, "\n" and "\r\n", a
+// last line without a newline, several records; bytes are kept as they are (lower case included).  On an error the graph keeps
+// the sequences it had.
+int read_fasta(LhGraph& g, const std::string& path);
+// the same store from memory: segment id i + 1 = bases[seg_off[i] .. seg_off[i + 1]), any byte values; false: offsets not ascending from 0
+bool set_sequences(LhGraph& g, const uint8_t* bases, const int64_t* seg_off);
 
 // ---- TRX-BFB, PROP I1 / C1 (localhap.cpp:79-88, :263): a translocation that happened BEFORE the BFB cycles -----------------------
 // insertBeforeBFB / concatBeforeBFB (LGM.cpp:4195-4395) rebuild the graph -- the inserted segments spliced into the main

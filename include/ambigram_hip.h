@@ -60,6 +60,12 @@ extern "C" {
 #define AMBI_ERR_HIP (-31)
 #define AMBI_ERR_STATE (-32)      /* call order violated (e.g. run before upload) */
 #define AMBI_ERR_ARG (-33)
+#define AMBI_ERR_TOO_LARGE (-34)  /* ambi_batch_sequence: the unit range's sequences exceed max_bytes */
+/* ambi_graph_read_fasta */
+#define AMBI_ERR_FASTA_OPEN (-40)   /* cannot open the FASTA file */
+#define AMBI_ERR_FASTA_CHROM (-41)  /* a segment's chromosome is not a record of the file */
+#define AMBI_ERR_FASTA_RANGE (-42)  /* a segment ends beyond its record */
+#define AMBI_ERR_FASTA_ORDER (-43)  /* a segment with end < start */
 
 const char* ambi_error_string(int code);
 int ambi_abi_version(void);
@@ -126,6 +132,20 @@ int ambi_graph_trx_restore(const ambi_graph_t* g, int32_t* path, int32_t len, in
 int ambi_graph_write_lh(ambi_graph_t* g, const char* lh_path);
 
 int ambi_graph_components(const ambi_graph_t* g, int32_t* ids, int32_t ids_cap, int32_t* offsets, int32_t off_cap);
+/* Bases of the segments, for ambi_batch_sequence.  Replaces what the reference's scripts ask bedtools for (script/main.py:709-740
+ * seg2fasta, script/bfb_scripts.py:31-49 getFasta).
+ * ambi_graph_set_sequences: segment id i + 1 = bases[seg_off[i] .. seg_off[i + 1]), seg_off[0 .. n_seg] ascending; any byte values.
+ * ambi_graph_read_fasta: segment i = chrom[start .. end) of the record whose name (the first word behind '>') is the segment's
+ *   chromosome in the .lh: 0-BASED, HALF-OPEN, end - start bytes -- seg2fasta writes `chr start end` of the .lh unchanged into a BED
+ *   line, and BED is half-open.  The reader is plain text and needs no index: any and irregular line widths, "\n" and "\r\n", a
+ *   last line without a newline, several records; bytes are kept as they are (lower case included).  AMBI_ERR_FASTA_OPEN / _CHROM /
+ *   _RANGE / _ORDER; after an error the graph keeps the sequences it had.
+ * ambi_graph_sequences: the store back (seg_off: n_seg + 1 entries from 0; at most cap bytes to bases); returns its bytes,
+ *   AMBI_ERR_STATE without sequences.
+ * Attach them before the graph's chromosomes are added to a batch: ambi_batch_add_chromosome* copies a unit's bases. */
+int ambi_graph_set_sequences(ambi_graph_t* g, const uint8_t* bases, const int64_t* seg_off);
+int ambi_graph_read_fasta(ambi_graph_t* g, const char* fasta_path);
+int64_t ambi_graph_sequences(const ambi_graph_t* g, uint8_t* bases, int64_t cap, int64_t* seg_off);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch of units.  A unit = one chromosome of one sample = one iteration of the loop localhap.cpp:111-265:
@@ -298,6 +318,39 @@ int ambi_batch_unit_path_cn(const ambi_batch_t* b, int32_t unit, int32_t* fwd, i
  * [ambi_unit_profile_t[n_units]] padded to 16 bytes, then per unit fwd int32[n + 1] and rev int32[n + 1], each array padded to 16
  * bytes.  Valid after ambi_batch_profile_wait until the next ambi_batch_profile; not available for a sharded batch. */
 int ambi_batch_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+
+/* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
+ * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
+ * through `bedtools getfasta -s`, all records joined).
+ *   sequence of a path = the concatenation over its cells c of seq(|c|) for c > 0 and of the reverse complement of seq(|c|) for
+ *     c < 0; `which` selects the cells ambi_batch_unit_path(unit, which) returns; a unit with a negative status or without a path
+ *     has length 0.
+ *   complement = one byte-to-byte table: ACGTUMRWSYKVHDBN -> TGCAAKYWSRMBDHVN and the same in lower case; every other byte value
+ *     (0-255) maps to itself; case is preserved.
+ * The bases come from the graph (ambi_graph_set_sequences / ambi_graph_read_fasta, copied by ambi_batch_add_chromosome*) or from
+ * ambi_batch_set_unit_sequences (local segment i + 1 = bases[seg_off[i] .. seg_off[i + 1]); not after ambi_batch_run_sharded).  They
+ * form a host-side image of the batch that travels to the device at the first request: ambi_batch_upload and ambi_batch_run are
+ * what they are without it.
+ * ambi_batch_sequence assembles the units [first_unit, first_unit + n_units) of the LAST run behind that run on hip_stream.  It
+ *   fetches the units' lengths (one small device-to-host trip: it blocks until the run's kernels have finished) and sizes the
+ *   output block from them; when they sum to more than max_bytes > 0 it returns AMBI_ERR_TOO_LARGE and assembles nothing -- the
+ *   lengths stay readable, so a caller can split the range.  AMBI_ERR_STATE before any run or without sequences, AMBI_ERR_ARG
+ *   for another `which` or a range outside the batch.  After ambi_batch_run_sharded the call goes to every share on its own
+ *   stream (the limit holds for the sum over the shares).
+ * ambi_batch_sequence_wait blocks until the request is done; it makes the run's results final first (ambi_batch_wait) and
+ *   assembles once more if that changed them (it can then return AMBI_ERR_TOO_LARGE itself).
+ * ambi_batch_unit_sequence_len: a unit's length in bytes, from ambi_batch_sequence on (final after the wait); AMBI_ERR_ARG for a
+ *   unit outside the request.
+ * ambi_batch_unit_sequence: bytes [first, first + count) of one unit's sequence to host memory; nothing else is downloaded.
+ * ambi_batch_sequence_device: the block in DEVICE memory and, in unit_off[0 .. n_units of the batch) (cap entries), every unit's
+ *   byte offset in it (a multiple of 16; -1 for a unit outside the request); valid until the next ambi_batch_sequence or run; not
+ *   available for a sharded batch. */
+int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off);
+int ambi_batch_sequence(ambi_batch_t* b, int32_t which, int32_t first_unit, int32_t n_units, int64_t max_bytes, void* hip_stream);
+int ambi_batch_sequence_wait(ambi_batch_t* b);
+int ambi_batch_unit_sequence_len(const ambi_batch_t* b, int32_t unit, int64_t* bases);
+int ambi_batch_unit_sequence(ambi_batch_t* b, int32_t unit, int64_t first, int64_t count, uint8_t* out);
+int ambi_batch_sequence_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap);
 
 /* Expands runs into cells: run r writes dev_cells[dev_cell_off[r] + k] = dev_run_start[r] + k, k < dev_run_len[r]
  * (dev_cell_off = exclusive prefix sum of the lengths, int64).  All pointers are device memory of the current device. */
