@@ -632,6 +632,9 @@ AMBI_HD int synth_out_juncs_runs(const G& g, const cell_t* bkp, int np, const in
         nc += tot;
     }
     g.sync();
+    // a unit has room for `cap` junction STEPS, repeats included: the rule of the cell form (synth_out_juncs lists the steps in room
+    // for that many), kept here too so that a unit ends the same way whichever stage finishes it
+    if (nc > cap) return ST_ERR_OUTJUNC_CAPACITY;
     return synth_classes(g, cand, nc, out, cap, seg_base, htab, htab ? synth_hash_size(nc, htab_ints) : 0);
 }
 

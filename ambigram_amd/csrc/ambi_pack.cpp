@@ -62,7 +62,17 @@ int HostBatch::add_unit(int n_seg, int seg_base, const double* cn_local, int n_j
     path_cap = (path_cap + 7) & ~int64_t(7);
     U.bkp_cap = (int32_t)bkp_cap;
     U.path_cap = (int32_t)path_cap;
-    U.out_cap = (int32_t)(bkp_cap + 64);
+    // output junctions = distinct junction steps of the final path.  getBFB's path has a step only between two breakpoint
+    // pairs: at most bkp_cap / 2 - 1.  indelBFB adds at most one NEW step per SV: a two-vertex group (one SV) that erases
+    // [pos1 + 1, pos2) leaves the one step pos1 -> pos2, one that duplicates [pos2, pos1] the one step path[pos1] -> path[pos2]
+    // (the steps inside the copy and the step behind it exist already and only raise their counts), and a group of k + 1
+    // chained SVs inserts k cells between pos1 and pos2: k + 1 steps (LGM.cpp:3779-3832).  So bkp_cap / 2 + n_sv records
+    // always suffice; the 64 are kept from the time before n_sv was counted.  The same number limits the junction STEPS of
+    // the final path, repeats included (the full finish stage lists them in a third of its candidate area, finish_cand_cap;
+    // the stages that work on runs apply the same rule): without a duplication there are no more steps than that bound
+    // either; duplications can repeat steps beyond any bound that is known here, and such a unit ends with
+    // ST_ERR_OUTJUNC_CAPACITY in every finish stage.
+    U.out_cap = (int32_t)(bkp_cap + 64 + n_sv);
     U.ideal_cap = ideal_cap;
     U.direct_full = may_dup ? 1 : 0;
     units.push_back(U);

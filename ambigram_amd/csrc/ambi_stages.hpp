@@ -1198,7 +1198,9 @@ struct FinishWork {
     uint8_t* has_ext;   // [m]
 };
 // (the deque of the general indelBFB path, 2m+4 ints, lives in the unit's HBM scratch: it is touched only when SVs chain)
-AMBI_HD int finish_cand_cap(int bkp_cap, int out_cap) { return out_cap + 2 * bkp_cap + 32; }
+// synth_out_juncs lists the junction steps of the path in (cand_cap - 1) / 3 ints: room for as many steps as the unit has
+// output-junction records (out_cap >= bkp_cap + 64: HostBatch::add_unit derives it)
+AMBI_HD int finish_cand_cap(int bkp_cap, int out_cap) { (void)bkp_cap; return 3 * out_cap + 1; }
 // the full finish stage holds the path cells in group memory: at most kPathLdsCells of them (longer paths are served by
 // the lean stage only; if their SVs chain or edit the path the unit ends with ST_ERR_PATH_CAPACITY)
 constexpr int kPathLdsCells = 65536;

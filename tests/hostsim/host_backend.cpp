@@ -382,10 +382,35 @@ class HostSimBackend : public Backend {
         const int64_t U = (int64_t)units_.size(), tot = hb_.run_slot.empty() ? 0 : hb_.run_slot.back();
         const int32_t* w = run_blk_.data();
         int64_t nr = 0, nc = 0;
-        for (int64_t u = 0; u < U; u++) { if (w[u] < 0) return ST_ERR_BAD_INPUT; nr += w[u]; nc += w[U + u]; }
-        *out = RunsView{nr, nc, w + U, w, w + 2 * U, w + 2 * U + tot, hb_.run_slot.data(), results_.data(), (2 * U + 2 * nr) * 4, (2 * U + 2 * tot) * 4};
+        bool over = false;
+        for (int64_t u = 0; u < U; u++) { if (w[u] < 0) over = true; else nr += w[u]; nc += w[U + u]; }
+        if (!over) {
+            *out = RunsView{nr, nc, w + U, w, w + 2 * U, w + 2 * U + tot, hb_.run_slot.data(), results_.data(), (2 * U + 2 * nr) * 4, (2 * U + 2 * tot) * 4};
+            return 0;
+        }
+        // a unit's runs did not fit its slots (the finish stages left -1 as its count): the batch through pack_runs, as
+        // HipBackend::runs_wait does it -- the layout of that route: totals | lengths[U] | run_counts[U] | run_start | run_len, and a
+        // second pass with room for all the runs when the first capacity was too small
+        int64_t cap = 64;
+        for (const UnitIn& un : units_) cap += un.bkp_cap / 2 + 8;
+        int32_t* p = nullptr;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            packed_runs_.assign((size_t)(4 + 2 * U + 2 * cap), 0);
+            p = packed_runs_.data();
+            if (int rc = pack_runs(1, p + 4, p + 4 + U, p + 4 + 2 * U, p + 4 + 2 * U + cap, cap, reinterpret_cast<int64_t*>(p), nullptr)) return rc;
+            const int64_t need = reinterpret_cast<const int64_t*>(p)[0];
+            if (need <= cap) break;
+            if (attempt == 1) return ST_ERR_BAD_INPUT;
+            cap = need;
+        }
+        const int64_t* totals = reinterpret_cast<const int64_t*>(p);
+        packed_off_.assign((size_t)U + 1, 0);
+        for (int64_t u = 0; u < U; u++) packed_off_[(size_t)u + 1] = packed_off_[(size_t)u] + p[4 + U + u];
+        *out = RunsView{totals[0], totals[1], p + 4, p + 4 + U, p + 4 + 2 * U, p + 4 + 2 * U + cap, packed_off_.data(), results_.data(),
+                        (4 + 2 * U + 2 * totals[0]) * 4, (4 + 2 * U + 2 * cap) * 4};
         return 0;
     }
+    std::vector<int32_t> packed_runs_; std::vector<int64_t> packed_off_;   // runs_wait's block when it went through pack_runs
     void set_timing(bool) override {}
     const std::vector<KernelTime>& kernel_times() override { return times_; }
     int64_t order_bytes_written() const override { return orders_needed_; }
