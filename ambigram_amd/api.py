@@ -39,6 +39,11 @@ class UnitProfile(C.Structure):     # ambi_unit_profile_t
                 ("n_uncovered", C.c_int32), ("n_off_target", C.c_int32), ("n_off_input", C.c_int32), ("l1_target", C.c_int64)]
 
 
+class UnitJuncProfile(C.Structure):     # ambi_unit_junc_profile_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "steps", "steps_matched", "steps_unmatched", "first_unmatched", "juncs", "juncs_used",
+                                         "max_count", "n_over", "n_under")]
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -107,6 +112,11 @@ def _declare(L):
         "ambi_batch_unit_profile": (C.c_int, [vp, i32, _P(UnitProfile)]),
         "ambi_batch_unit_path_cn": (C.c_int, [vp, i32, pi32, pi32, i32]),
         "ambi_batch_profile_device": (C.c_int, [vp, _P(vp), pi64]),
+        "ambi_batch_junc_profile": (C.c_int, [vp, i32, vp]),
+        "ambi_batch_junc_profile_wait": (C.c_int, [vp]),
+        "ambi_batch_unit_junc_profile": (C.c_int, [vp, i32, _P(UnitJuncProfile)]),
+        "ambi_batch_unit_junc_usage": (C.c_int, [vp, i32, pi32, pi32, i32]),
+        "ambi_batch_junc_profile_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_graph_set_sequences": (C.c_int, [vp, vp, pi64]),
         "ambi_graph_read_fasta": (C.c_int, [vp, C.c_char_p]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
@@ -545,6 +555,35 @@ class Batch:
         self._ck(self.lib.ambi_batch_profile_device(self.h, C.byref(p), C.byref(n)), "profile_device")
         return p.value or 0, n.value
 
+    def junc_profile(self, which=1, stream=None):
+        """Queues the junction usage profile of the last run's paths behind that run (ambi_batch_junc_profile): per junction of a
+        unit how many steps of the path (which: 0 getBFB's, 1 the final one) take it, and a summary per unit; `stream` is not blocked."""
+        self._ck(self.lib.ambi_batch_junc_profile(self.h, which, C.c_void_p(stream or 0)), "junc_profile")
+
+    def junc_profile_wait(self):
+        """Waits for the junction profile in host memory (the run's results are final first); unit_junc_profile / unit_junc_usage
+        answer afterwards."""
+        self._ck(self.lib.ambi_batch_junc_profile_wait(self.h), "junc_profile_wait")
+
+    def unit_junc_profile(self, u):
+        r = UnitJuncProfile()
+        self._ck(self.lib.ambi_batch_unit_junc_profile(self.h, u, C.byref(r)), "unit_junc_profile")
+        return {k: getattr(r, k) for k, _ in UnitJuncProfile._fields_}
+
+    def unit_junc_usage(self, u):
+        """(count, graph_index): int32 arrays over the unit's junctions in the unit's order -- steps credited to the junction, and
+        its index into Graph.junctions() (the junction's own index for a unit added with add_unit)."""
+        m = self._ck(self.lib.ambi_batch_unit_junc_usage(self.h, u, None, None, 1 << 30), "unit_junc_usage")
+        count = np.zeros(m, np.int32); index = np.zeros(m, np.int32)
+        self._ck(self.lib.ambi_batch_unit_junc_usage(self.h, u, count.ctypes.data_as(_P(C.c_int32)), index.ctypes.data_as(_P(C.c_int32)), m), "unit_junc_usage")
+        return count, index
+
+    def junc_profile_device(self):
+        """(address, bytes) of the junction profile block in device memory (ambi_batch_junc_profile_device), for collectives."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._ck(self.lib.ambi_batch_junc_profile_device(self.h, C.byref(p), C.byref(n)), "junc_profile_device")
+        return p.value or 0, n.value
+
     def set_unit_sequences(self, u, bases, seg_off):
         """Bases of a unit added with add_unit (ambi_batch_set_unit_sequences): local segment i + 1 = bases[seg_off[i]:seg_off[i + 1]]."""
         raw = np.frombuffer(bytes(bases), np.uint8) if not isinstance(bases, np.ndarray) else np.ascontiguousarray(bases, np.uint8)
@@ -752,11 +791,14 @@ def merge_out_juncs(acc, unit_list, increase=True):
 
 
 def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, first_budget=0, order_arena_bytes=-1,
-                       target_lanes=0, keep_orders=False, profile=False, ref_fasta=None):
+                       target_lanes=0, keep_orders=False, profile=False, ref_fasta=None, junc_profile=False):
     """Host-side mirror of `Ambigram --op bfb` (localhap.cpp:49-388) with the external `cbc` call replaced by the given
     .sol files (one per chromosome that reaches the ILP, in order).  Returns a dict shaped like the oracle's dump.
     profile=True: every chromosome's dict gains path_cn_fwd / path_cn_rev (traversal counts of the final path per local segment
     id, slot 0 unused) and profile (the unit's summary), computed on the device (Batch.profile).
+    junc_profile=True: every chromosome's dict gains junc_count (per junction of the GRAPH, in file order: steps of the final path
+    credited to it; 0 for a junction outside the chromosome), junc_graph_index (the graph indices of the chromosome's junctions,
+    in the unit's order) and junc_profile (the unit's summary), computed on the device (Batch.junc_profile).
     ref_fasta: every chromosome's dict gains sequence (bytes), the nucleotide sequence of its final path assembled on the device
     (Batch.sequence) from the segments' bases in that FASTA file (chrom[start:end], 0-based and half-open)."""
     g = Graph(lib, lh)
@@ -798,6 +840,8 @@ def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, fir
     b.runs_to_host(1, 0); b.runs_wait(0)
     if profile:
         b.profile(1); b.profile_wait()
+    if junc_profile:
+        b.junc_profile(1); b.junc_profile_wait()
     if ref_fasta:
         b.sequence(1); b.sequence_wait()
     res = dict(ok=True, err="", log=log, chr=[], paths=[], out_juncs=[], trx_run=False, trx_path=[])
@@ -823,6 +867,11 @@ def reconstruct_sample(lib, lh, sols, juncs="", reversed_=False, all_=False, fir
         if profile:
             fwd, rev = b.unit_path_cn(c, e - s + 1)
             st.update(path_cn_fwd=fwd, path_cn_rev=rev, profile=b.unit_profile(c))
+        if junc_profile:
+            cnt, idx = b.unit_junc_usage(c)
+            per_graph = np.zeros(g.n_junc, np.int32)
+            per_graph[idx] = cnt
+            st.update(junc_count=per_graph, junc_graph_index=idx, junc_profile=b.unit_junc_profile(c))
         if ref_fasta:
             st["sequence"] = b.unit_sequence(c)
         if r["status"] == ST_OK:

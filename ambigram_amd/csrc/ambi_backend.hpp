@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ambi_pack.hpp"
+#include "ambi_junc_profile.hpp"
 #include "ambi_profile.hpp"
 #include "ambi_sequence.hpp"
 
@@ -88,7 +89,7 @@ class Backend {
     // getters below then answer from that copy.  The default runs stage_path_profile on the host over the downloaded blob (the
     // host simulation); the HIP engine overrides both with ambi_path_profile_kernel and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    void profile_bind(const HostBatch* hb) { prof_hb_ = hb; prof_view_ = nullptr; }
+    void profile_bind(const HostBatch* hb) { prof_hb_ = hb; prof_view_ = nullptr; jprof_view_ = nullptr; }
     virtual int profile(int which, void* stream) {
         (void)stream;
         if (!prof_hb_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
@@ -130,6 +131,54 @@ class Backend {
         if (fwd) memcpy(fwd, p, sizeof(int32_t) * (size_t)(n + 1));
         if (rev) memcpy(rev, p + profile_rev_off(n), sizeof(int32_t) * (size_t)(n + 1));
         return n + 1;
+    }
+
+    // ---- junction usage profile of every unit's path (ambi_junc_profile.hpp; which as above) ----
+    // The junction-level twin of the profile above, with the same life cycle: junc_profile() queues it behind the last run,
+    // junc_profile_wait() waits for it in host memory, the getters answer from that copy.  The default runs stage_junc_profile on
+    // the host over the downloaded blob (the host simulation); the HIP engine overrides the virtual entries with
+    // ambi_junc_profile_kernel and never reaches it.
+    virtual int junc_profile(int which, void* stream) {
+        (void)stream;
+        if (!prof_hb_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
+        std::vector<uint8_t> blob;
+        if (int rc = download(blob)) return rc;
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        jprof_bytes_ = junc_profile_block_layout(units, jprof_off_);
+        jprof_blob_.assign((size_t)jprof_bytes_, 0);
+        int jwin, slots, swin;
+        junc_profile_windows(&jwin, &slots, &swin);
+        std::vector<int32_t> lds((size_t)(junc_profile_lds_bytes(slots, swin) / 4));
+        const JuncTable T = junc_table(lds.data(), slots, swin);
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++)
+            junc_profile_unit(g, units.data(), prof_hb_->junc_ends.data(), prof_hb_->junc_cn.data(), blob.data(), (int)u, which, jwin, T, jprof_blob_.data(), jprof_off_.data());
+        jprof_view_ = nullptr;
+        return 0;
+    }
+    virtual int junc_profile_wait() {
+        if (jprof_blob_.empty()) return ST_ERR_BAD_INPUT;
+        jprof_view_ = jprof_blob_.data();
+        return 0;
+    }
+    // the block where the collectives of the caller can read it (device memory of the HIP engine), valid after junc_profile_wait()
+    virtual int junc_profile_device(void** ptr, int64_t* bytes) {
+        if (!jprof_view_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = jprof_blob_.data();
+        if (bytes) *bytes = jprof_bytes_;
+        return 0;
+    }
+    int junc_profile_summary(int unit, UnitJuncProfile* out) const {
+        if (!jprof_view_ || unit < 0 || unit >= (int)jprof_off_.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitJuncProfile*>(jprof_view_)[unit];
+        return 0;
+    }
+    int junc_profile_counts(int unit, int32_t* count, int cap) const {   // m counts; returns m
+        if (!jprof_view_ || !prof_hb_ || unit < 0 || unit >= (int)jprof_off_.size()) return ST_ERR_BAD_INPUT;
+        const int m = prof_hb_->units[(size_t)unit].n_junc;
+        if (cap < m) return ST_ERR_BAD_INPUT;
+        if (count && m > 0) memcpy(count, jprof_view_ + jprof_off_[(size_t)unit], sizeof(int32_t) * (size_t)m);
+        return m;
     }
 
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
@@ -199,6 +248,14 @@ class Backend {
     bool sequence_known() const { return seq_state_ >= 1; }
 
   protected:
+    // junctions per pass, table slots and segments per window of the bound batch (AMBI_JPROFILE_* can only shrink the windows)
+    void junc_profile_windows(int* jwin, int* slots, int* swin) const {
+        const char* ej = ambi_env("AMBI_JPROFILE_JUNC_WINDOW");
+        const char* es = ambi_env("AMBI_JPROFILE_SEG_WINDOW");
+        *jwin = junc_window(prof_hb_->max_m, ej ? atoi(ej) : 0);
+        *slots = junc_slots(*jwin);
+        *swin = junc_seg_window(prof_hb_->max_n, es ? atoi(es) : 0);
+    }
     int sequence_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
         const int U = (int)prof_hb_->units.size();
         if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
@@ -214,8 +271,12 @@ class Backend {
     std::vector<int64_t> prof_off_;      // byte offset of every unit's fwd array in the profile block (profile_block_layout)
     int64_t prof_bytes_ = 0;             // bytes of the block
     const uint8_t* prof_view_ = nullptr; // the block in host memory once profile_wait() has returned (nullptr: no profile to read)
+    std::vector<int64_t> jprof_off_;     // byte offset of every unit's counts in the junction profile block (junc_profile_block_layout)
+    int64_t jprof_bytes_ = 0;            // bytes of that block
+    const uint8_t* jprof_view_ = nullptr;// the block in host memory once junc_profile_wait() has returned
   private:
     std::vector<uint8_t> prof_blob_;     // the default implementation's block
+    std::vector<uint8_t> jprof_blob_;    // ... and its junction profile block
     std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };
 

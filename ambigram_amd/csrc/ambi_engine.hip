@@ -19,6 +19,8 @@
 //                                                  run) turns runs back into cells on the receiving rank (ambi_exchange.hpp)
 //   ambi_path_profile_kernel      1 block / unit   on request: per-segment traversal counts of the path + summary
 //                                                  (ambi_profile.hpp)                              <- read-bound, 2 bytes / cell
+//   ambi_junc_profile_kernel      1 block / unit   on request: per-junction traversal counts of the path + summary
+//                                                  (ambi_junc_profile.hpp)                         <- the same cells + a hash table in LDS
 // Every kernel but the two plan kernels is a wrapper around the stage functions of ambi_stages.hpp (ambi_exchange.hpp,
 // ambi_profile.hpp for the pack / expand and profile kernels), which the host simulation runs as well, the four table kernels
 // (blocks_build, enumerate_blocks, enumerate, enumerate_wide; their logic is under stage_enumerate's banner) included.  The
@@ -593,6 +595,17 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_path_profile_kernel(Batc
         __syncthreads();
     }
 }
+// ---- junction usage profile of the paths (ambi_junc_profile.hpp; launched by HipBackend::junc_profile only) ----
+// One workgroup of 256 threads per unit, grid-stride over the units.  Group memory: 256 bytes for the group's reductions, then
+// the hash table of `slots` slots (key, lowest index, count: 12 bytes each) and the difference array of `swin` segments.
+__global__ __launch_bounds__(kProfileThreads) void ambi_junc_profile_kernel(BatchArgs A, int which, int jwin, int slots, int swin, uint8_t* block, const int64_t* off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    const JuncTable T = junc_table(ambi_lds + kProfileScratchBytes, slots, swin);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        junc_profile_unit(g, A.units, A.junc_ends, A.junc_cn, A.results, u, which, jwin, T, block, off);
+        __syncthreads();
+    }
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -724,6 +737,10 @@ struct Lease {
     uint8_t* d_prof = nullptr; int64_t d_prof_bytes = 0;
     uint8_t* h_prof = nullptr; int64_t h_prof_bytes = 0;
     hipEvent_t ev_prof_src = nullptr, ev_prof_packed = nullptr, ev_prof_done = nullptr;
+    // junction usage profile (HipBackend::junc_profile): the same for the block [UnitJuncProfile[U]][per unit count]
+    uint8_t* d_jprof = nullptr; int64_t d_jprof_bytes = 0;
+    uint8_t* h_jprof = nullptr; int64_t h_jprof_bytes = 0;
+    hipEvent_t ev_jprof_src = nullptr, ev_jprof_packed = nullptr, ev_jprof_done = nullptr;
     // path sequences (HipBackend::sequence): the batch's sequence image [bases][seg_pos][store_off][pos_off], the working block of a
     // request [totals][ext_off, out_off, tile_off][ext_src][ext_out] and the output block; the pinned twin carries the image up, the
     // totals down and the three offset tables up.  Events: the run's stream reached / all queued work done / timing pairs
@@ -1030,6 +1047,8 @@ class HipBackend : public Backend {
         if (inflight_) { (void)hipStreamSynchronize(stream_); inflight_ = false; }
         for (hipStream_t s : {side_.lean, side_.full, side_.scan, lease_->copy_stream, lease_->run_stream}) if (s) (void)hipStreamSynchronize(s);
         if (prof_queued_ && prof_stream_ != stream_) (void)hipStreamSynchronize(prof_stream_);   // (a profile queued on another stream than the run's)
+        if (jprof_queued_ && jprof_stream_ != stream_) (void)hipStreamSynchronize(jprof_stream_);
+        jprof_queued_ = false;
         if (seq_busy_ && seq_stream_ != stream_) (void)hipStreamSynchronize(seq_stream_);          // (and a sequence request)
         seq_busy_ = false;
         prof_queued_ = false;
@@ -1076,6 +1095,8 @@ class HipBackend : public Backend {
             }
             if (L->d_prof_bytes > kKeepProfile) { (void)hipFree(L->d_prof); L->d_prof = nullptr; L->d_prof_bytes = 0; }
             if (L->h_prof_bytes > kKeepProfile) { (void)hipHostFree(L->h_prof); L->h_prof = nullptr; L->h_prof_bytes = 0; }
+            if (L->d_jprof_bytes > kKeepProfile) { (void)hipFree(L->d_jprof); L->d_jprof = nullptr; L->d_jprof_bytes = 0; }
+            if (L->h_jprof_bytes > kKeepProfile) { (void)hipHostFree(L->h_jprof); L->h_jprof = nullptr; L->h_jprof_bytes = 0; }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
                 if (*pb.second > kKeepSeq) { (void)hipFree(*pb.first); *pb.first = nullptr; *pb.second = 0; }
             if (L->h_seq_bytes > kKeepSeq) { (void)hipHostFree(L->h_seq); L->h_seq = nullptr; L->h_seq_bytes = 0; }
@@ -1085,6 +1106,7 @@ class HipBackend : public Backend {
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
         prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
+        jprof_view_ = nullptr; jprof_queued_ = false; jprof_laid_out_ = false;
         sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
@@ -1151,6 +1173,7 @@ class HipBackend : public Backend {
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
         prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
+        jprof_view_ = nullptr; jprof_queued_ = false; jprof_laid_out_ = false;
         sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
@@ -2172,6 +2195,71 @@ class HipBackend : public Backend {
         if (!prof_view_ || !lease_) return ST_ERR_BAD_INPUT;
         if (ptr) *ptr = lease_->d_prof;
         if (bytes) *bytes = prof_bytes_;
+        return 0;
+    }
+    // ---- junction usage profile of the paths (ambi_junc_profile.hpp) ----
+    // The profile's twin: junc_profile() queues ambi_junc_profile_kernel on `stream` behind everything that writes the result blob
+    // in the last run, then ONE device-to-host copy of the block on the lease's copy stream; junc_profile_wait() makes the results
+    // final (wait()) and, if that moved the results' epoch after the kernel was queued, queues kernel and copy once more.
+    bool jprof_queued_ = false, jprof_laid_out_ = false;
+    int jprof_which_ = 1; int64_t jprof_epoch_ = -1; hipStream_t jprof_stream_ = nullptr;
+    int64_t* d_jprof_off_ = nullptr;
+    int junc_profile_queue(int which, hipStream_t s) {
+        Lease* L = lease_;
+        const int64_t U = (int64_t)hb().units.size();
+        if (!jprof_laid_out_) {
+            jprof_bytes_ = junc_profile_block_layout(hb().units, jprof_off_);
+            const int64_t total = jprof_bytes_ + U * (int64_t)sizeof(int64_t);   // (jprof_bytes_ is a multiple of 16)
+            if (int rc = lease_device_block(&L->d_jprof, &L->d_jprof_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&L->h_jprof, nullptr, &L->h_jprof_bytes, total)) return rc;
+            if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
+            for (hipEvent_t* e : {&L->ev_jprof_src, &L->ev_jprof_packed, &L->ev_jprof_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
+            memcpy(L->h_jprof + jprof_bytes_, jprof_off_.data(), (size_t)U * sizeof(int64_t));
+            d_jprof_off_ = reinterpret_cast<int64_t*>(L->d_jprof + jprof_bytes_);
+            HIP_CK(hipMemcpyAsync(d_jprof_off_, L->h_jprof + jprof_bytes_, (size_t)U * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            jprof_laid_out_ = true;
+        }
+        if (s != stream_) { HIP_CK(hipEventRecord(L->ev_jprof_src, stream_)); HIP_CK(hipStreamWaitEvent(s, L->ev_jprof_src, 0)); }
+        if (overlap_back_) {
+            HIP_CK(hipStreamWaitEvent(s, ev_back_, 0));
+            if (direct_n_ > 0) HIP_CK(hipStreamWaitEvent(s, ev_full_, 0));
+        }
+        if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
+        int jwin, slots, swin;
+        junc_profile_windows(&jwin, &slots, &swin);
+        const int lds = kProfileScratchBytes + (int)junc_profile_lds_bytes(slots, swin);
+        if (jprof_queued_) HIP_CK(hipStreamWaitEvent(s, L->ev_jprof_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
+        const int grid = (int)(U < 16384 ? U : 16384);
+        hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, L->d_jprof, (const int64_t*)d_jprof_off_);
+        HIP_CK(hipGetLastError());
+        HIP_CK(hipEventRecord(L->ev_jprof_packed, s));
+        HIP_CK(hipStreamWaitEvent(L->copy_stream, L->ev_jprof_packed, 0));
+        HIP_CK(hipMemcpyAsync(L->h_jprof, L->d_jprof, (size_t)jprof_bytes_, hipMemcpyDeviceToHost, L->copy_stream));
+        HIP_CK(hipEventRecord(L->ev_jprof_done, L->copy_stream));
+        jprof_which_ = which; jprof_stream_ = s; jprof_epoch_ = epoch_; jprof_queued_ = true;
+        jprof_view_ = nullptr;
+        return 0;
+    }
+    int junc_profile(int which, void* stream) override {
+        DeviceGuard dg_(device_);
+        if (!ran_ || !lease_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
+        prof_hb_ = hbp_;
+        return junc_profile_queue(which, (hipStream_t)stream);
+    }
+    int junc_profile_wait() override {
+        DeviceGuard dg_(device_);
+        if (!jprof_queued_) return ST_ERR_BAD_INPUT;
+        if (int rc = wait()) return rc;
+        if (epoch_ != jprof_epoch_) { if (int rc = junc_profile_queue(jprof_which_, jprof_stream_)) return rc; }
+        HIP_CK(hipEventSynchronize(lease_->ev_jprof_done));
+        jprof_view_ = lease_->h_jprof;
+        return 0;
+    }
+    int junc_profile_device(void** ptr, int64_t* bytes) override {
+        if (!jprof_view_ || !lease_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->d_jprof;
+        if (bytes) *bytes = jprof_bytes_;
         return 0;
     }
     // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----

@@ -5,6 +5,7 @@
 // The per-chromosome stages run on the GPU through libambigram_hip.so; the ILP model is built on the host
 // (ambi_ilp_build) and solved by whatever `cbc` is on PATH, exactly as the reference shells out (localhap.cpp:179-181).
 #include <chrono>
+#include <cstdint>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -249,6 +250,11 @@ int run_sc_bfb(Args& A) {
 // --cn_profile <file> (what the reference's commented-out CN.txt writer meant to report, localhap.cpp:318-351): after the run, one
 // tab-separated row per segment -- sample, chromosome name, segment id, start, end, input CN, target CN, forward count, reverse
 // count, count - target -- from the device's copy-number profile of the final paths (ambi_batch_profile); stdout is unchanged.
+// --junc_profile <file> (the join the reference leaves to the reader of simulation_sv.txt, localhap.cpp:267-289 and :326-337): after
+// the run, one tab-separated row per junction of the graph in file order -- sample, chromosome index (-1 for a junction between
+// chromosomes, which belongs to no unit: count 0), source chromosome name, source segment id, source strand, target chromosome
+// name, target segment id, target strand, input CN, count in the final path, count - CN -- from the device's junction usage
+// profile of the final paths (ambi_batch_junc_profile); stdout and the side files are unchanged.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -276,6 +282,7 @@ int run_bfb(Args& A) {
     const bool junc_info = truthy(A.kv["junc_info"]), reversed = truthy(A.kv["reversed"]), all = truthy(A.kv["all"]);
     const double solver_timeout = A.kv.count("solver_timeout") ? atof(A.kv["solver_timeout"].c_str()) : 0;   // extension: seconds, 0 = none
     const std::string cn_profile = A.kv.count("cn_profile") ? A.kv["cn_profile"] : "";
+    const std::string junc_profile = A.kv.count("junc_profile") ? A.kv["junc_profile"] : "";
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
     const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
@@ -315,6 +322,13 @@ int run_bfb(Args& A) {
             ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
             if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
                 std::cerr << "--cn_profile: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
+                return 2;
+            }
+        }
+        if (!junc_profile.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << "--junc_profile: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
                 return 2;
             }
         }
@@ -420,6 +434,32 @@ int run_bfb(Args& A) {
                             target[i], fwd[i], rev[i], fwd[i] + rev[i] - target[i]);
                 }
             }
+        fclose(pf);
+    }
+    if (!junc_profile.empty()) {
+        if ((rc = ambi_batch_junc_profile(b, 1, nullptr)) != 0 || (rc = ambi_batch_junc_profile_wait(b)) != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+        FILE* pf = fopen(junc_profile.c_str(), "w");
+        if (!pf) return die("Cannot open file " + junc_profile);
+        for (Sample& S : samples) {
+            const int m = S.n_junc;
+            std::vector<int32_t> src(m), tgt(m), count(m, 0), chr_of(m, -1);
+            std::vector<int8_t> sdir(m), tdir(m);
+            std::vector<double> cn(m);
+            ambi_graph_junctions(S.g, src.data(), sdir.data(), tgt.data(), tdir.data(), nullptr, cn.data(), nullptr, nullptr);
+            for (int c = 0; c < S.n_chr; c++) {
+                const int mu = ambi_batch_unit_junc_usage(b, S.unit[c], nullptr, nullptr, INT32_MAX);
+                if (mu < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(mu)); }
+                std::vector<int32_t> cnt(mu), idx(mu);
+                if ((rc = ambi_batch_unit_junc_usage(b, S.unit[c], cnt.data(), idx.data(), mu)) < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                for (int j = 0; j < mu; j++) if (idx[j] >= 0 && idx[j] < m) { count[idx[j]] = cnt[j]; chr_of[idx[j]] = c; }
+            }
+            for (int j = 0; j < m; j++) {
+                char ns[256], nt[256];
+                ambi_graph_chrom_name(S.g, src[j], ns, sizeof(ns)); ambi_graph_chrom_name(S.g, tgt[j], nt, sizeof(nt));
+                fprintf(pf, "%s\t%d\t%s\t%d\t%c\t%s\t%d\t%c\t%g\t%d\t%g\n", S.lh.c_str(), chr_of[j], ns, src[j], sdir[j] > 0 ? '+' : '-', nt, tgt[j],
+                        tdir[j] > 0 ? '+' : '-', cn[j], count[j], (double)count[j] - cn[j]);
+            }
+        }
         fclose(pf);
     }
     if (!out_fasta.empty()) {
@@ -609,10 +649,13 @@ int main(int argc, char** argv) {
     if (A.help) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
-                     "[--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--junc_profile <file>] [--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --junc_profile <file> (--op bfb): one tab-separated row per junction after the run, in file order: sample, chromosome index (-1 between "
+                     "chromosomes), source chromosome, source segment id, source strand, target chromosome, target segment id, target strand, input CN, count in "
+                     "the final path, count - CN (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
                      "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
                      "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
                      "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";

@@ -319,6 +319,49 @@ int ambi_batch_unit_path_cn(const ambi_batch_t* b, int32_t unit, int32_t* fwd, i
  * bytes.  Valid after ambi_batch_profile_wait until the next ambi_batch_profile; not available for a sharded batch. */
 int ambi_batch_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
 
+/* The junction usage profile of every unit's path, computed ON THE DEVICE (ambi_junc_profile_kernel): which of the unit's input
+ * junctions (SVs, fold-backs, adjacencies) the path takes, how often, and how that compares with their input copy numbers.  The
+ * reference leaves the raw material in simulation_sv.txt (localhap.cpp:326-337: every input junction with its copy number as an
+ * `input` row, every non-adjacent step of the paths with its count as an `output` row) and the join to the user; the join test is
+ * its own (localhap.cpp:277-278): a step u -> v belongs to a junction when it equals the junction's edge A or its complement edge
+ * B (Junction.cpp:27-39).  With the path cells c[0..P) that ambi_batch_unit_path(unit, which) returns (as local ids) and the
+ * unit's junctions j = 0..m-1 in the unit's order (the graph's order restricted to junctions with both ends inside the unit):
+ *   step i = (c[i], c[i+1]), i = 0..P-2; junction j with strand-signed ends (s, t) matches a step (x, y) when (x, y) == (s, t) or
+ *   (x, y) == (-t, -s); a fold-back (s, -s) has equal edges and is credited once per step; when several junctions match (raw units
+ *   only: lh_graph.cpp:81 drops a second copy) the LOWEST index is credited and the others get nothing.
+ * All fields are exact integers.  Per unit m int32 travel to the host instead of the path's cells. */
+typedef struct {
+    int32_t status;           /* the unit's status (ambi_unit_result_t::status) */
+    int32_t steps;            /* P - 1; a unit with a negative status or without a path has every field but status zero */
+    int32_t steps_matched;    /* steps credited to a junction = sum of the counts */
+    int32_t steps_unmatched;  /* steps that match no junction of the unit (localhap.cpp:277-289 finds no input row for them) */
+    int32_t first_unmatched;  /* smallest i whose step matches nothing, -1 if none */
+    int32_t juncs;            /* m */
+    int32_t juncs_used;       /* junctions with count > 0 */
+    int32_t max_count;        /* max over the junctions of count */
+    int32_t n_over;           /* junctions with count - cn >= 0.5 (cn: the junction's input copy number as uploaded) */
+    int32_t n_under;          /* junctions with cn - count >= 0.5 */
+} ambi_unit_junc_profile_t;
+/* Queues the junction profile of the LAST run's results behind that run on hip_stream (which as for ambi_batch_profile;
+ * localhap.cpp:267-289 walks the printed paths), then one device-to-host copy of the block on the engine's copy stream: hip_stream
+ * is not blocked.  AMBI_ERR_STATE before any run, AMBI_ERR_ARG for another `which`.  After ambi_batch_run_sharded the call goes to
+ * every share, on the share's own stream. */
+int ambi_batch_junc_profile(ambi_batch_t* b, int32_t which, void* hip_stream);
+/* Blocks until the junction profile is in host memory.  Makes the run's results final first (ambi_batch_wait) and profiles once
+ * more if that changed them after the request was queued (localhap.cpp:267-289 runs after the last path is final). */
+int ambi_batch_junc_profile_wait(ambi_batch_t* b);
+/* A unit's summary (localhap.cpp:326-337: input rows against output rows); AMBI_ERR_STATE without a waited-for junction profile
+ * of the last run. */
+int ambi_batch_unit_junc_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_junc_profile_t* out);
+/* A unit's counts per junction (localhap.cpp:277-278 joined with :326-337): count[j] = steps credited to the unit's junction j,
+ * graph_index[j] = its index into the arrays of ambi_graph_junctions (j itself for a raw unit).  Either pointer may be NULL.
+ * Returns m; AMBI_ERR_ARG when cap < m. */
+int ambi_batch_unit_junc_usage(const ambi_batch_t* b, int32_t unit, int32_t* count, int32_t* graph_index, int32_t cap);
+/* The junction profile block in DEVICE memory, for collectives (localhap.cpp:326-337 for a whole cohort without a host round
+ * trip): [ambi_unit_junc_profile_t[n_units]] padded to 16 bytes, then per unit count int32[m] padded to 16 bytes.  Valid after
+ * ambi_batch_junc_profile_wait until the next ambi_batch_junc_profile; not available for a sharded batch. */
+int ambi_batch_junc_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
  * through `bedtools getfasta -s`, all records joined).
