@@ -200,8 +200,9 @@ __global__ __launch_bounds__(64) void ambi_lattice_own_kernel(BatchArgs A) {
     // (then every prefix fits, whatever subset the plan kernel ends up placing)
     if (threadIdx.x == 0 && A.lat_seq) {
         const bool ok = A.lat_status[u] == ST_OK || A.lat_status[u] == ST_ERR_NO_ELEMENTS;   // (no elements: the express stage reports that itself)
-        const int64_t bytes = A.lat_status[u] == ST_OK ? order_bytes((int64_t)A.lat_R[u], A.units[u].n_elem, A.order_align) : 0;
-        if (!ok) *A.lat_unsure = 1;
+        const bool toobig = A.lat_status[u] == ST_OK && order_table_too_big((int64_t)A.lat_R[u], A.units[u].n_elem);   // (the plan kernel will refuse it)
+        const int64_t bytes = A.lat_status[u] == ST_OK && !toobig ? order_bytes((int64_t)A.lat_R[u], A.units[u].n_elem, A.order_align) : 0;
+        if (!ok || toobig) *A.lat_unsure = 1;
         __threadfence_system();
         const unsigned long long total = atomicAdd(reinterpret_cast<unsigned long long*>(A.lat_sum), (unsigned long long)bytes) + (unsigned long long)bytes;
         (void)total;
@@ -260,7 +261,7 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
     for (int base = 0; base < A.n_units; base += chunk) {
         load_chunk(base);
 #pragma unroll
-        for (int k = 0; k < kPlanPer; k++) if (wanted_[k] && R_[k] < (int64_t)kCountSat) my_rows += R_[k];
+        for (int k = 0; k < kPlanPer; k++) if (wanted_[k] && !order_table_too_big(R_[k], K_[k])) my_rows += R_[k];
     }
     int64_t total_rows;
     (void)g.exscan_i64(my_rows, &total_rows);
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
         for (int k = 0; k < kPlanPer; k++) {
             bytes[k] = 0; blocks[k] = 0; live[k] = false; toobig[k] = false;
             if (wanted_[k]) {
-                if (R_[k] >= (int64_t)kCountSat) toobig[k] = true;
+                if (order_table_too_big(R_[k], K_[k])) toobig[k] = true;   // (the rule and its bound: ambi_stages.hpp, next to order_bytes)
                 else {
                     live[k] = true;
                     bytes[k] = order_bytes(R_[k], K_[k], A.order_align);
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(1024) void ambi_plan_kernel(BatchArgs A) {
             }
             blk += fits[k] ? blocks[k] : 0;
         }
-        off_carry += tot_b;
+        off_carry = order_bytes_add(off_carry, tot_b);
         blk_carry += tot_k;
     }
     __syncthreads();

@@ -392,13 +392,27 @@ AMBI_HD int rows_per_lane_for(int64_t total_rows, int target_lanes) {
 }
 // bytes a unit's table takes of the arena: its rows, rounded up to `align` (a power of two >= 16) so that the next table starts aligned
 AMBI_HD int64_t order_bytes(int64_t R, int K, int64_t align = 16) { return (R * row_stride(K) + align - 1) & ~(align - 1); }
+// The one rule for tables no arena can hold (plan_serial and ambi_plan_kernel both ask here, before order_bytes): counts are kept
+// below kCountSat = 2^62 and a row has up to 256 bytes, so R * row_stride(K) can pass 2^63 and wrap.  A table of more than
+// kOrderTableMaxBytes = 2^48 bytes -- beyond the address space of the host and of the device, let alone their memory -- is never
+// placed: the unit ends with ORDERS_CAPACITY (order_off = kOrderOffNoRoom, no work blocks), its num_orders stays the exact
+// count, and it is left out of the offsets and of orders_needed, so the units behind it are placed as if it were not there.
+// The test itself stays in range without a division: a row has at least 4 bytes, so R > 2^46 is too big whatever the stride
+// (counts saturated at kCountSat among them), and below that R * row_stride(K) <= 2^46 * 256 = 2^54.
+constexpr int64_t kOrderTableMaxBytes = int64_t(1) << 48;
+AMBI_HD bool order_table_too_big(int64_t R, int K) { return R < 0 || R > (kOrderTableMaxBytes >> 2) || R * row_stride(K) > kOrderTableMaxBytes; }
+// orders_needed is a sum of tables of less than 2^49 bytes each; it stops at kOrderBytesSat, so that neither it nor what the
+// hosts derive from it (need + need / 16 + a page, rounded up) leaves int64.  Adding in any grouping gives the same value as
+// long as no partial sum passes 2^63: ambi_plan_kernel adds at most 4096 tables (2^61) to a saturated carry.
+constexpr int64_t kOrderBytesSat = int64_t(1) << 62;
+AMBI_HD int64_t order_bytes_add(int64_t sum, int64_t more) { return sum + more < kOrderBytesSat ? sum + more : kOrderBytesSat; }
 
 // serial reference form of the plan kernel (host simulation)
 AMBI_HD void plan_serial(const BatchArgs& A) {
     int64_t total_rows = 0;
     for (int i = 0; i < A.n_units; i++) {
         const UnitOut* out = unit_out(A.results, A.unit_base + i);
-        if (out->order_off == kOrderOffWanted && out->num_orders < (int64_t)kCountSat) total_rows += out->num_orders;
+        if (out->order_off == kOrderOffWanted && !order_table_too_big(out->num_orders, out->K)) total_rows += out->num_orders;   // (rows that are written: below 2^46 per unit)
     }
     const int T = rows_per_lane_for(total_rows, A.target_lanes);
     int64_t off = 0, blk = 0;   // off: relative to the launch's arena region
@@ -410,12 +424,12 @@ AMBI_HD void plan_serial(const BatchArgs& A) {
         if (out->order_off != kOrderOffWanted) continue;
         const int K = out->K;
         const int64_t R = out->num_orders;
-        if (R >= (int64_t)kCountSat) { out->order_off = kOrderOffNoRoom; continue; }
+        if (order_table_too_big(R, K)) { out->order_off = kOrderOffNoRoom; continue; }
         const int64_t bytes = order_bytes(R, K, A.order_align);
-        // plain prefix sum: a unit that does not fit still advances the offset (so orders_needed is the true total)
-        if (off + bytes > A.order_arena_bytes) { out->order_off = kOrderOffNoRoom; off += bytes; continue; }
+        // plain prefix sum: a unit that does not fit still advances the offset (so orders_needed is the total, up to kOrderBytesSat)
+        if (off + bytes > A.order_arena_bytes) { out->order_off = kOrderOffNoRoom; off = order_bytes_add(off, bytes); continue; }
         out->order_off = A.arena_base + off;
-        off += bytes;
+        off = order_bytes_add(off, bytes);
         blk += (R + 256ll * T - 1) / (256ll * T);   // one work block = 256*T rows = one workgroup (4 waves x 64*T)
     }
     A.blk_off[A.n_units] = blk;

@@ -5,9 +5,13 @@
 // sanitizers run over the kernel code on the CPU.  It is built into tests/hostsim/libambigram_hostsim.so only;
 // the product library libambigram_hip.so does not contain it and nothing in ambigram_amd/ loads it by default.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <vector>
+
+#include <unistd.h>
 
 #include "../../ambigram_amd/csrc/ambi_backend.hpp"
 #include "../../ambigram_amd/csrc/ambi_exchange.hpp"
@@ -172,6 +176,10 @@ class HostSimBackend : public Backend {
         }
     }
 
+    static int64_t host_memory_bytes() {
+        const long pages = sysconf(_SC_PHYS_PAGES), page = sysconf(_SC_PAGE_SIZE);
+        return pages > 0 && page > 0 ? (int64_t)pages * page : INT64_MAX;
+    }
     int run(uint32_t flags, void*) override {
         HostGroup g;
         bind(flags);
@@ -204,7 +212,24 @@ class HostSimBackend : public Backend {
             int64_t want = orders_needed_;
             { const char* cap = ambi_env("AMBI_ARENA_MAX_BYTES"); if (cap && atoll(cap) > 0 && want > atoll(cap)) want = atoll(cap); }   // as HipBackend::run
             if (want <= (int64_t)arena_.size()) break;   // cannot grow further: the units beyond it end with ORDERS_CAPACITY
-            arena_.assign((size_t)want, 0);              // grow the arena and redo (first run only)
+            // grow the arena and redo (first run only).  The new arena first, the old one goes only when that worked: a failed
+            // growth keeps the arena and redoes nothing, and the units whose tables do not fit it end with ORDERS_CAPACITY, one
+            // by one (as HipBackend::grow_arena; orders_needed is at most kOrderBytesSat, so `want` is in range).  hipMalloc fails
+            // when the device lacks the memory; operator new on a host that overcommits would not, and the zero fill would get the
+            // process killed instead -- so a request beyond the machine's physical memory counts as failed without being made
+            bool grown = false;
+            if (want <= host_memory_bytes()) {
+                try {
+                    std::vector<uint8_t> fresh((size_t)want, 0);
+                    arena_.swap(fresh);
+                    grown = true;
+                } catch (const std::exception&) {}
+            }
+            if (!grown) {
+                fprintf(stderr, "ambigram_hostsim: order-table arena of %lld bytes not available; keeping %lld bytes (units beyond it report ORDERS_CAPACITY)\n",
+                        (long long)want, (long long)arena_.size());
+                break;
+            }
             bind(flags);
             if (express)   // the lattice stage does not rewrite the header: take back what the plan pass decided against the small arena
                 for (int u = 0; u < Un; u++) {
@@ -360,8 +385,8 @@ class HostSimBackend : public Backend {
         const UnitOut* h = unit_out(results_.data(), unit);
         if (h->order_off < 0 || first < 0 || first + count > h->num_orders) return ST_ERR_BAD_INPUT;
         const int stride = row_stride(h->K);
-        for (int64_t r = 0; r < count; r++)
-            for (int d = 0; d < h->K; d++) out[r * h->K + d] = (uint8_t)row_node(arena_.data() + h->order_off + (first + r) * stride, h->K, d);
+        // one pass per row (as HipBackend::copy_orders; row_node per node is quadratic in K, seconds for the tables of the order fuzz)
+        for (int64_t r = 0; r < count; r++) row_unpack(arena_.data() + h->order_off + (first + r) * stride, h->K, out + r * h->K);
         return 0;
     }
     int copy_debug_order(int unit, uint8_t* out) override {
