@@ -323,14 +323,17 @@ ELEMENT_SHARE = (0.0, 0.3, 0.7, 1.0)
 ELEMENT_CROSS = (0, 10, 100, 1000)       # the unit's absolute ids straddle this power of ten (0: the chromosome starts at 1)
 
 
-def element_case(workdir, seed):
+def element_case(workdir, seed, ns=None, ks=None, prefix="pe"):
     """cases.random_decomposition's .lh (fold-backs everywhere) with a random element set of K in ELEMENT_K elements, a loop share
     in ELEMENT_SHARE, the ends drawn from few shared points (a dense DAG); in multi-chromosome files the unit is the LAST
     chromosome, behind short chromosomes without fold-backs, so that its absolute ids -- the reference's map keys are their
-    decimal strings -- straddle 9/10, 99/100 or 999/1000."""
+    decimal strings -- straddle 9/10, 99/100 or 999/1000.  Other families give segment counts `ns` (four of them), element
+    counts `ks` (twelve) and a name prefix of their own (wide_checks: K = 64..255)."""
     rng = random.Random(0x85EBCA6B * (seed + 1) & 0xFFFFFFFF)
-    n = ELEMENT_N[seed % 4]
-    K = ELEMENT_K[(seed // 4) % 12]
+    ns, ks = ns or ELEMENT_N, ks or ELEMENT_K
+    assert len(ns) == 4 and len(ks) == 12
+    n = ns[seed % 4]
+    K = ks[(seed // 4) % 12]
     share = ELEMENT_SHARE[(seed // 48) % 4]
     cross = ELEMENT_CROSS[(seed // 192) % 4] if seed >= 192 else rng.choice(ELEMENT_CROSS)
     start = 1 if cross == 0 else max(1, cross - rng.randint(1, n - 1))
@@ -369,7 +372,7 @@ def element_case(workdir, seed):
         els.add((rng.random() < share, a, b))
     num_pat = n * (n + 1) // 2
     rows = sorted((synth.rank_ab(a, b, 1, n) + (num_pat if is_loop else 0), 1 if not is_loop else rng.randint(1, 2)) for (is_loop, a, b) in els)
-    name = "pe%d" % seed
+    name = "%s%d" % (prefix, seed)
     lh = _write(os.path.join(workdir, name + ".lh"), lh_text(name, ranges, seg_cn, juncs))
     sol = _write(os.path.join(workdir, name + ".sol"),
                  "Optimal - objective value 0.00000000\n" + "".join("%7d x%-7d %15d %15d\n" % (c, c, v, 0) for c, v in rows))
