@@ -84,100 +84,69 @@ class Backend {
     virtual int all_finish() = 0;
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
 
-    // ---- copy-number profile of every unit's path (ambi_profile.hpp; which: 0 getBFB, 1 after indelBFB) ----
-    // profile() queues the profile of the last run's results behind that run, profile_wait() waits for it in host memory; the
-    // getters below then answer from that copy.  The default runs stage_path_profile on the host over the downloaded blob (the
-    // host simulation); the HIP engine overrides both with ambi_path_profile_kernel and never reaches it.
+    // ---- on-request profiles of every unit's path (which: 0 getBFB, 1 after indelBFB) ----
+    // Two kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand) and the
+    // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts), each a block [summary[U]][per unit counts].
+    // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
+    // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
+    // simulation); the HIP engine overrides the three virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    void profile_bind(const HostBatch* hb) { prof_hb_ = hb; prof_view_ = nullptr; jprof_view_ = nullptr; }
-    virtual int profile(int which, void* stream) {
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1 };
+    void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
+    virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
         if (!prof_hb_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
         std::vector<uint8_t> blob;
         if (int rc = download(blob)) return rc;
-        const std::vector<UnitIn>& units = prof_hb_->units;
-        prof_bytes_ = profile_block_layout(units, prof_off_);
-        prof_blob_.assign((size_t)prof_bytes_, 0);
-        const char* e = ambi_env("AMBI_PROFILE_WINDOW");
-        const int window = profile_window(prof_hb_->max_n, e ? atoi(e) : 0);
-        std::vector<int32_t> bins((size_t)(2 * window));
-        HostGroup g;
-        for (size_t u = 0; u < units.size(); u++) profile_unit(g, units.data(), blob.data(), (int)u, which, window, bins.data(), prof_blob_.data(), prof_off_.data());
-        prof_view_ = nullptr;
+        ProfileState& P = prof_[kind];
+        profile_layout(kind);
+        P.blob.assign((size_t)P.bytes, 0);
+        if (kind == kJunction) host_junc_profile(blob.data(), which, P); else host_profile(blob.data(), which, P);
+        P.view = nullptr;
         return 0;
     }
-    virtual int profile_wait() {
-        if (prof_blob_.empty()) return ST_ERR_BAD_INPUT;
-        prof_view_ = prof_blob_.data();
+    virtual int profile_wait(ProfileKind kind) {
+        ProfileState& P = prof_[kind];
+        if (P.blob.empty()) return ST_ERR_BAD_INPUT;
+        P.view = P.blob.data();
         return 0;
     }
-    // the profile block where the collectives of the caller can read it (device memory of the HIP engine), valid after profile_wait()
-    virtual int profile_device(void** ptr, int64_t* bytes) {
-        if (!prof_view_) return ST_ERR_BAD_INPUT;
-        if (ptr) *ptr = prof_blob_.data();
-        if (bytes) *bytes = prof_bytes_;
+    // the block where the collectives of the caller can read it (device memory of the HIP engine), valid after profile_wait()
+    virtual int profile_device(ProfileKind kind, void** ptr, int64_t* bytes) {
+        ProfileState& P = prof_[kind];
+        if (!P.view) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = P.blob.data();
+        if (bytes) *bytes = P.bytes;
         return 0;
     }
     int profile_summary(int unit, UnitProfile* out) const {
-        if (!prof_view_ || unit < 0 || unit >= (int)prof_off_.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitProfile*>(prof_view_)[unit];
+        const ProfileState& P = prof_[kCopyNumber];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitProfile*>(P.view)[unit];
         return 0;
     }
     int profile_counts(int unit, int32_t* fwd, int32_t* rev, int cap) const {   // n + 1 counts each; returns n + 1
-        if (!prof_view_ || !prof_hb_ || unit < 0 || unit >= (int)prof_off_.size()) return ST_ERR_BAD_INPUT;
+        const ProfileState& P = prof_[kCopyNumber];
+        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
         const int n = prof_hb_->units[(size_t)unit].n_seg;
         if (cap < n + 1) return ST_ERR_BAD_INPUT;
-        const uint8_t* p = prof_view_ + prof_off_[(size_t)unit];
+        const uint8_t* p = P.view + P.off[(size_t)unit];
         if (fwd) memcpy(fwd, p, sizeof(int32_t) * (size_t)(n + 1));
         if (rev) memcpy(rev, p + profile_rev_off(n), sizeof(int32_t) * (size_t)(n + 1));
         return n + 1;
     }
-
-    // ---- junction usage profile of every unit's path (ambi_junc_profile.hpp; which as above) ----
-    // The junction-level twin of the profile above, with the same life cycle: junc_profile() queues it behind the last run,
-    // junc_profile_wait() waits for it in host memory, the getters answer from that copy.  The default runs stage_junc_profile on
-    // the host over the downloaded blob (the host simulation); the HIP engine overrides the virtual entries with
-    // ambi_junc_profile_kernel and never reaches it.
-    virtual int junc_profile(int which, void* stream) {
-        (void)stream;
-        if (!prof_hb_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
-        std::vector<uint8_t> blob;
-        if (int rc = download(blob)) return rc;
-        const std::vector<UnitIn>& units = prof_hb_->units;
-        jprof_bytes_ = junc_profile_block_layout(units, jprof_off_);
-        jprof_blob_.assign((size_t)jprof_bytes_, 0);
-        int jwin, slots, swin;
-        junc_profile_windows(&jwin, &slots, &swin);
-        std::vector<int32_t> lds((size_t)(junc_profile_lds_bytes(slots, swin) / 4));
-        const JuncTable T = junc_table(lds.data(), slots, swin);
-        HostGroup g;
-        for (size_t u = 0; u < units.size(); u++)
-            junc_profile_unit(g, units.data(), prof_hb_->junc_ends.data(), prof_hb_->junc_cn.data(), blob.data(), (int)u, which, jwin, T, jprof_blob_.data(), jprof_off_.data());
-        jprof_view_ = nullptr;
-        return 0;
-    }
-    virtual int junc_profile_wait() {
-        if (jprof_blob_.empty()) return ST_ERR_BAD_INPUT;
-        jprof_view_ = jprof_blob_.data();
-        return 0;
-    }
-    // the block where the collectives of the caller can read it (device memory of the HIP engine), valid after junc_profile_wait()
-    virtual int junc_profile_device(void** ptr, int64_t* bytes) {
-        if (!jprof_view_) return ST_ERR_BAD_INPUT;
-        if (ptr) *ptr = jprof_blob_.data();
-        if (bytes) *bytes = jprof_bytes_;
-        return 0;
-    }
     int junc_profile_summary(int unit, UnitJuncProfile* out) const {
-        if (!jprof_view_ || unit < 0 || unit >= (int)jprof_off_.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitJuncProfile*>(jprof_view_)[unit];
+        const ProfileState& P = prof_[kJunction];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitJuncProfile*>(P.view)[unit];
         return 0;
     }
     int junc_profile_counts(int unit, int32_t* count, int cap) const {   // m counts; returns m
-        if (!jprof_view_ || !prof_hb_ || unit < 0 || unit >= (int)jprof_off_.size()) return ST_ERR_BAD_INPUT;
+        const ProfileState& P = prof_[kJunction];
+        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
         const int m = prof_hb_->units[(size_t)unit].n_junc;
         if (cap < m) return ST_ERR_BAD_INPUT;
-        if (count && m > 0) memcpy(count, jprof_view_ + jprof_off_[(size_t)unit], sizeof(int32_t) * (size_t)m);
+        if (count && m > 0) memcpy(count, P.view + P.off[(size_t)unit], sizeof(int32_t) * (size_t)m);
         return m;
     }
 
@@ -248,6 +217,23 @@ class Backend {
     bool sequence_known() const { return seq_state_ >= 1; }
 
   protected:
+    // one on-request profile block on the host side: where every unit's counts start in it, its size, the block in host memory once
+    // profile_wait() has returned (nullptr: nothing to read), and the default implementation's own block
+    struct ProfileState {
+        std::vector<int64_t> off;
+        int64_t bytes = 0;
+        const uint8_t* view = nullptr;
+        std::vector<uint8_t> blob;
+    };
+    ProfileState prof_[2];               // [ProfileKind]
+    void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
+        ProfileState& P = prof_[kind];
+        P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
+    }
+    int profile_window_of() const {      // segments per window of the bound batch (AMBI_PROFILE_WINDOW can only shrink it)
+        const char* e = ambi_env("AMBI_PROFILE_WINDOW");
+        return profile_window(prof_hb_->max_n, e ? atoi(e) : 0);
+    }
     // junctions per pass, table slots and segments per window of the bound batch (AMBI_JPROFILE_* can only shrink the windows)
     void junc_profile_windows(int* jwin, int* slots, int* swin) const {
         const char* ej = ambi_env("AMBI_JPROFILE_JUNC_WINDOW");
@@ -268,15 +254,24 @@ class Backend {
     int seq_state_ = 0;                  // 0: no request; 1: lengths known; 2: sequence_wait() has returned, the getters answer
     bool seq_queued_ = false;            // the stages of the last request have been queued (false behind kSeqTooLarge)
     const HostBatch* prof_hb_ = nullptr;
-    std::vector<int64_t> prof_off_;      // byte offset of every unit's fwd array in the profile block (profile_block_layout)
-    int64_t prof_bytes_ = 0;             // bytes of the block
-    const uint8_t* prof_view_ = nullptr; // the block in host memory once profile_wait() has returned (nullptr: no profile to read)
-    std::vector<int64_t> jprof_off_;     // byte offset of every unit's counts in the junction profile block (junc_profile_block_layout)
-    int64_t jprof_bytes_ = 0;            // bytes of that block
-    const uint8_t* jprof_view_ = nullptr;// the block in host memory once junc_profile_wait() has returned
   private:
-    std::vector<uint8_t> prof_blob_;     // the default implementation's block
-    std::vector<uint8_t> jprof_blob_;    // ... and its junction profile block
+    void host_profile(const uint8_t* blob, int which, ProfileState& P) {
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        const int window = profile_window_of();
+        std::vector<int32_t> bins((size_t)(2 * window));
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++) profile_unit(g, units.data(), blob, (int)u, which, window, bins.data(), P.blob.data(), P.off.data());
+    }
+    void host_junc_profile(const uint8_t* blob, int which, ProfileState& P) {
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        int jwin, slots, swin;
+        junc_profile_windows(&jwin, &slots, &swin);
+        std::vector<int32_t> lds((size_t)(junc_profile_lds_bytes(slots, swin) / 4));
+        const JuncTable T = junc_table(lds.data(), slots, swin);
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++)
+            junc_profile_unit(g, units.data(), prof_hb_->junc_ends.data(), prof_hb_->junc_cn.data(), blob, (int)u, which, jwin, T, P.blob.data(), P.off.data());
+    }
     std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };
 

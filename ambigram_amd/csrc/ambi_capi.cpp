@@ -115,8 +115,7 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled = false;    // ambi_batch_profile_wait has returned for the last run: the profile getters answer
-    bool jprofiled = false;   // ambi_batch_junc_profile_wait has returned for the last run: the junction profile getters answer
+    bool profiled[2] = {false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
@@ -430,14 +429,14 @@ int ambi_batch_upload(ambi_batch_t* b) {
     b->be->profile_bind(&b->hb);
     int rc = b->be->upload(b->hb, b->cfg);
     if (rc == 0) b->uploaded = true;
-    b->ran = false; b->profiled = false; b->jprofiled = false; b->sequenced = false;
+    b->ran = false; b->profiled[0] = b->profiled[1] = false; b->sequenced = false;
     b->be->sequence_reset();
     return rc;
 }
 int ambi_batch_run(ambi_batch_t* b, uint32_t flags, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!b->uploaded) return AMBI_ERR_STATE;
-    b->downloaded = false; b->mail_view = false; b->profiled = false; b->jprofiled = false; b->sequenced = false;
+    b->downloaded = false; b->mail_view = false; b->profiled[0] = b->profiled[1] = false; b->sequenced = false;
     b->be->sequence_reset();
     const int rc = b->be->run(flags, hip_stream);
     if (rc == 0) b->ran = true;
@@ -501,7 +500,7 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
         for (auto& s : b->shards) s->hb.finalize();
     }
     b->hb.finalize();
-    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled = false; b->jprofiled = false; b->sequenced = false;
+    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled[0] = b->profiled[1] = false; b->sequenced = false;
     for (auto& s : b->shards) s->be->sequence_reset();
     // every share on its own (resident) thread, the first one too: set_device changes the current device of the thread that calls it,
     // and the caller's thread keeps the device it had.  Nothing is merged: the getters read a unit where its share left it.
@@ -647,28 +646,38 @@ int ambi_batch_unit_path(const ambi_batch_t* b, int32_t unit, int32_t which, int
     return len;
 }
 // ---- copy-number profile of the paths (ambi_profile.hpp; localhap.cpp:318-351) ----
-int ambi_batch_profile(ambi_batch_t* b, int32_t which, void* hip_stream) {
+// Both kinds (Backend::ProfileKind) go to the batch's backend or, after run_sharded, to every share that holds units: a request on
+// the share's own stream (the backend selects its device for the call)
+static int profile_start(ambi_batch_t* b, Backend::ProfileKind kind, int32_t which, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
     if (which < 0 || which > 1) return AMBI_ERR_ARG;
-    b->profiled = false;
-    if (!b->sharded_ready) return b->be->profile(which, hip_stream);
-    for (auto& s : b->shards)   // every share on its own stream (the backend selects its device for the call)
-        if (!s->units.empty()) { if (int rc = s->be->profile(which, s->be->own_stream())) return rc; }
+    b->profiled[kind] = false;
+    if (!b->sharded_ready) return b->be->profile(kind, which, hip_stream);
+    for (auto& s : b->shards)
+        if (!s->units.empty()) { if (int rc = s->be->profile(kind, which, s->be->own_stream())) return rc; }
     return 0;
 }
-int ambi_batch_profile_wait(ambi_batch_t* b) {
+static int profile_wait(ambi_batch_t* b, Backend::ProfileKind kind) {
     if (!b) return AMBI_ERR_ARG;
     if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
-    if (!b->sharded_ready) { if (int rc = b->be->profile_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
+    if (!b->sharded_ready) { if (int rc = b->be->profile_wait(kind)) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
     else for (auto& s : b->shards)
-        if (!s->units.empty()) { if (int rc = s->be->profile_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
-    b->profiled = true;
+        if (!s->units.empty()) { if (int rc = s->be->profile_wait(kind)) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
+    b->profiled[kind] = true;
     return 0;
 }
+static int profile_device(ambi_batch_t* b, Backend::ProfileKind kind, void** dev_ptr, int64_t* bytes) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!b->profiled[kind] || b->sharded_ready) return AMBI_ERR_STATE;   // (one block per share: no single device view)
+    return b->be->profile_device(kind, dev_ptr, bytes) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_profile(ambi_batch_t* b, int32_t which, void* hip_stream) { return profile_start(b, Backend::kCopyNumber, which, hip_stream); }
+int ambi_batch_profile_wait(ambi_batch_t* b) { return profile_wait(b, Backend::kCopyNumber); }
+int ambi_batch_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) { return profile_device(b, Backend::kCopyNumber, dev_ptr, bytes); }
 int ambi_batch_unit_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_profile_t* out) {
     if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
-    if (!b->profiled) return AMBI_ERR_STATE;
+    if (!b->profiled[Backend::kCopyNumber]) return AMBI_ERR_STATE;
     int local = unit;
     const Backend* be = b->owner(unit, &local);
     static_assert(sizeof(ambi_unit_profile_t) == sizeof(UnitProfile), "ambi_unit_profile_t is ambi::UnitProfile");
@@ -676,41 +685,20 @@ int ambi_batch_unit_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_profi
 }
 int ambi_batch_unit_path_cn(const ambi_batch_t* b, int32_t unit, int32_t* fwd, int32_t* rev, int32_t cap) {
     if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
-    if (!b->profiled) return AMBI_ERR_STATE;
+    if (!b->profiled[Backend::kCopyNumber]) return AMBI_ERR_STATE;
     if (cap < b->hb.units[unit].n_seg + 1) return AMBI_ERR_ARG;
     int local = unit;
     const Backend* be = b->owner(unit, &local);
     const int rc = be->profile_counts(local, fwd, rev, cap);
     return rc < 0 ? AMBI_ERR_STATE : rc;
 }
-int ambi_batch_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) {
-    if (!b) return AMBI_ERR_ARG;
-    if (!b->profiled || b->sharded_ready) return AMBI_ERR_STATE;
-    return b->be->profile_device(dev_ptr, bytes) ? AMBI_ERR_STATE : 0;
-}
 // ---- junction usage profile of the paths (ambi_junc_profile.hpp; localhap.cpp:267-289, :326-337) ----
-int ambi_batch_junc_profile(ambi_batch_t* b, int32_t which, void* hip_stream) {
-    if (!b) return AMBI_ERR_ARG;
-    if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
-    if (which < 0 || which > 1) return AMBI_ERR_ARG;
-    b->jprofiled = false;
-    if (!b->sharded_ready) return b->be->junc_profile(which, hip_stream);
-    for (auto& s : b->shards)   // every share on its own stream (the backend selects its device for the call)
-        if (!s->units.empty()) { if (int rc = s->be->junc_profile(which, s->be->own_stream())) return rc; }
-    return 0;
-}
-int ambi_batch_junc_profile_wait(ambi_batch_t* b) {
-    if (!b) return AMBI_ERR_ARG;
-    if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
-    if (!b->sharded_ready) { if (int rc = b->be->junc_profile_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
-    else for (auto& s : b->shards)
-        if (!s->units.empty()) { if (int rc = s->be->junc_profile_wait()) return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc; }
-    b->jprofiled = true;
-    return 0;
-}
+int ambi_batch_junc_profile(ambi_batch_t* b, int32_t which, void* hip_stream) { return profile_start(b, Backend::kJunction, which, hip_stream); }
+int ambi_batch_junc_profile_wait(ambi_batch_t* b) { return profile_wait(b, Backend::kJunction); }
+int ambi_batch_junc_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) { return profile_device(b, Backend::kJunction, dev_ptr, bytes); }
 int ambi_batch_unit_junc_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_junc_profile_t* out) {
     if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
-    if (!b->jprofiled) return AMBI_ERR_STATE;
+    if (!b->profiled[Backend::kJunction]) return AMBI_ERR_STATE;
     int local = unit;
     const Backend* be = b->owner(unit, &local);
     static_assert(sizeof(ambi_unit_junc_profile_t) == sizeof(UnitJuncProfile), "ambi_unit_junc_profile_t is ambi::UnitJuncProfile");
@@ -718,7 +706,7 @@ int ambi_batch_unit_junc_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_
 }
 int ambi_batch_unit_junc_usage(const ambi_batch_t* b, int32_t unit, int32_t* count, int32_t* graph_index, int32_t cap) {
     if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
-    if (!b->jprofiled) return AMBI_ERR_STATE;
+    if (!b->profiled[Backend::kJunction]) return AMBI_ERR_STATE;
     const int m = b->hb.units[unit].n_junc;
     if (cap < m) return AMBI_ERR_ARG;
     int local = unit;
@@ -730,11 +718,6 @@ int ambi_batch_unit_junc_usage(const ambi_batch_t* b, int32_t unit, int32_t* cou
         for (int j = 0; j < m; j++) graph_index[j] = j < (int)map.size() ? map[j] : j;
     }
     return rc;
-}
-int ambi_batch_junc_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) {
-    if (!b) return AMBI_ERR_ARG;
-    if (!b->jprofiled || b->sharded_ready) return AMBI_ERR_STATE;
-    return b->be->junc_profile_device(dev_ptr, bytes) ? AMBI_ERR_STATE : 0;
 }
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
 int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {

@@ -717,6 +717,17 @@ struct PinnedWords {                    // what kernels write into host memory (
     uint32_t guard_hi[16];
 };
 struct TimingEvents { const char* name; hipEvent_t a, b; };
+// The lease's part of one on-request profile (HipBackend::profile_queue): the block [summary[U]][per unit counts] with the units'
+// offsets behind it, its pinned twin, and three events (the run's stream reached / kernel done / block arrived)
+struct RequestBlock {
+    uint8_t* d = nullptr; int64_t d_bytes = 0;
+    uint8_t* h = nullptr; int64_t h_bytes = 0;
+    hipEvent_t ev_src = nullptr, ev_packed = nullptr, ev_done = nullptr;
+    void trim(int64_t keep) {   // a block larger than `keep` goes back to the device when the batch is destroyed
+        if (d_bytes > keep) { (void)hipFree(d); d = nullptr; d_bytes = 0; }
+        if (h_bytes > keep) { (void)hipHostFree(h); h = nullptr; h_bytes = 0; }
+    }
+};
 struct Lease {
     int device = 0;
     DeviceContext* ctx = nullptr;   // the device's
@@ -733,15 +744,8 @@ struct Lease {
     uint8_t* h_runs[2] = {nullptr, nullptr}; int64_t h_runs_bytes[2] = {0, 0};
     hipStream_t run_stream = nullptr;   // own_stream(): for callers without a stream (ambi_batch_run_sharded's shares)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
-    // copy-number profile (HipBackend::profile): the profile block [UnitProfile[U]][per unit fwd, rev] with the units' offsets behind it,
-    // its pinned twin, and three events (the run's stream reached / kernel done / block arrived)
-    uint8_t* d_prof = nullptr; int64_t d_prof_bytes = 0;
-    uint8_t* h_prof = nullptr; int64_t h_prof_bytes = 0;
-    hipEvent_t ev_prof_src = nullptr, ev_prof_packed = nullptr, ev_prof_done = nullptr;
-    // junction usage profile (HipBackend::junc_profile): the same for the block [UnitJuncProfile[U]][per unit count]
-    uint8_t* d_jprof = nullptr; int64_t d_jprof_bytes = 0;
-    uint8_t* h_jprof = nullptr; int64_t h_jprof_bytes = 0;
-    hipEvent_t ev_jprof_src = nullptr, ev_jprof_packed = nullptr, ev_jprof_done = nullptr;
+    // [Backend::ProfileKind] copy-number profile [UnitProfile[U]][per unit fwd, rev], junction usage profile [UnitJuncProfile[U]][per unit count]
+    RequestBlock prof[2];
     // path sequences (HipBackend::sequence): the batch's sequence image [bases][seg_pos][store_off][pos_off], the working block of a
     // request [totals][ext_off, out_off, tile_off][ext_src][ext_out] and the output block; the pinned twin carries the image up, the
     // totals down and the three offset tables up.  Events: the run's stream reached / all queued work done / timing pairs
@@ -1040,6 +1044,16 @@ class HipBackend : public Backend {
     std::chrono::steady_clock::time_point t_run_; double t_launched_ = 0;   // env AMBI_DEBUG_LATENCY
     bool debug_ = false;      // env AMBI_DEBUG: budgets and grids chosen; guard words of the direct path areas checked at wait()
 
+    // per-batch state of one on-request profile (profile_queue): a request is in flight or waited for, the block is laid out and its
+    // offsets are on the device (d_off), and what profile_wait() needs to queue it again
+    struct Request {
+        bool queued = false, laid_out = false;
+        int which = 1; int64_t epoch = -1; hipStream_t stream = nullptr;
+        int64_t* d_off = nullptr;
+    };
+    Request req_[2];   // [ProfileKind]
+    void requests_reset() { for (int k = 0; k < 2; k++) { req_[k] = Request{}; prof_[k].view = nullptr; } }
+
     // Everything this batch queued is complete when this returns: the caller's stream (only if a run is still in flight -- the
     // stream must outlive its work), the side streams this batch used and the lease's copy and run streams, each synchronised
     // EXPLICITLY (round 2 relied on hipFree's implicit device synchronisation and destroyed streams it had never synchronised).
@@ -1047,12 +1061,10 @@ class HipBackend : public Backend {
         if (!lease_) return;
         if (inflight_) { (void)hipStreamSynchronize(stream_); inflight_ = false; }
         for (hipStream_t s : {side_.lean, side_.full, side_.scan, lease_->copy_stream, lease_->run_stream}) if (s) (void)hipStreamSynchronize(s);
-        if (prof_queued_ && prof_stream_ != stream_) (void)hipStreamSynchronize(prof_stream_);   // (a profile queued on another stream than the run's)
-        if (jprof_queued_ && jprof_stream_ != stream_) (void)hipStreamSynchronize(jprof_stream_);
-        jprof_queued_ = false;
+        for (const Request& R : req_) if (R.queued && R.stream != stream_) (void)hipStreamSynchronize(R.stream);   // (a profile queued on another stream than the run's)
         if (seq_busy_ && seq_stream_ != stream_) (void)hipStreamSynchronize(seq_stream_);          // (and a sequence request)
         seq_busy_ = false;
-        prof_queued_ = false;
+        requests_reset();
         (void)hipGetLastError();
     }
     // guard words around the pinned words the kernels write through (always) and around the path areas of the direct
@@ -1094,10 +1106,7 @@ class HipBackend : public Backend {
                 if (L->d_runs_bytes[k] > kKeepRuns) { (void)hipFree(L->d_runs[k]); L->d_runs[k] = nullptr; L->d_runs_bytes[k] = 0; }
                 if (L->h_runs_bytes[k] > kKeepRuns) { (void)hipHostFree(L->h_runs[k]); L->h_runs[k] = nullptr; L->h_runs_bytes[k] = 0; }
             }
-            if (L->d_prof_bytes > kKeepProfile) { (void)hipFree(L->d_prof); L->d_prof = nullptr; L->d_prof_bytes = 0; }
-            if (L->h_prof_bytes > kKeepProfile) { (void)hipHostFree(L->h_prof); L->h_prof = nullptr; L->h_prof_bytes = 0; }
-            if (L->d_jprof_bytes > kKeepProfile) { (void)hipFree(L->d_jprof); L->d_jprof = nullptr; L->d_jprof_bytes = 0; }
-            if (L->h_jprof_bytes > kKeepProfile) { (void)hipHostFree(L->h_jprof); L->h_jprof = nullptr; L->h_jprof_bytes = 0; }
+            for (RequestBlock& B : L->prof) B.trim(kKeepProfile);
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
                 if (*pb.second > kKeepSeq) { (void)hipFree(*pb.first); *pb.first = nullptr; *pb.second = 0; }
             if (L->h_seq_bytes > kKeepSeq) { (void)hipHostFree(L->h_seq); L->h_seq = nullptr; L->h_seq_bytes = 0; }
@@ -1106,8 +1115,7 @@ class HipBackend : public Backend {
         }
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
-        prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
-        jprof_view_ = nullptr; jprof_queued_ = false; jprof_laid_out_ = false;
+        requests_reset();
         sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
@@ -1173,8 +1181,7 @@ class HipBackend : public Backend {
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -30;   // AMBI_ERR_NO_DEVICE: no CPU fallback
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
-        prof_view_ = nullptr; prof_queued_ = false; prof_laid_out_ = false;
-        jprof_view_ = nullptr; jprof_queued_ = false; jprof_laid_out_ = false;
+        requests_reset();
         sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
@@ -2128,143 +2135,83 @@ class HipBackend : public Backend {
         out->copied_bytes = words * 4 + (runs_hdr_[slot] ? U * (int64_t)sizeof(UnitOut) : 0);
         return 0;
     }
-    // ---- copy-number profile of the paths (ambi_profile.hpp) ----
-    // profile() queues ambi_path_profile_kernel on `stream` behind everything that writes the result blob in the last run -- the
-    // caller's stream of that run, and explicitly the events "results complete" of the side streams (lean / list finish kernels,
-    // direct edit + full launch) and of the express kernel -- then ONE device-to-host copy of the profile block on the lease's copy
-    // stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes the results final (wait():
-    // the first run done again with a larger arena, units finished by the parallel search) and, if that moved the results' epoch
-    // after the kernel was queued, queues kernel and copy once more.
-    bool prof_queued_ = false, prof_laid_out_ = false;
-    int prof_which_ = 1; int64_t prof_epoch_ = -1; hipStream_t prof_stream_ = nullptr;
-    int64_t* d_prof_off_ = nullptr;
-    int profile_queue(int which, hipStream_t s) {
-        Lease* L = lease_;
-        const int64_t U = (int64_t)hb().units.size();
-        if (!prof_laid_out_) {
-            prof_bytes_ = profile_block_layout(hb().units, prof_off_);
-            const int64_t total = prof_bytes_ + U * (int64_t)sizeof(int64_t);   // (prof_bytes_ is a multiple of 16)
-            if (int rc = lease_device_block(&L->d_prof, &L->d_prof_bytes, total)) return rc;
-            if (int rc = lease_pinned_block(&L->h_prof, nullptr, &L->h_prof_bytes, total)) return rc;
-            if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&L->ev_prof_src, &L->ev_prof_packed, &L->ev_prof_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-            // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
-            memcpy(L->h_prof + prof_bytes_, prof_off_.data(), (size_t)U * sizeof(int64_t));
-            d_prof_off_ = reinterpret_cast<int64_t*>(L->d_prof + prof_bytes_);
-            HIP_CK(hipMemcpyAsync(d_prof_off_, L->h_prof + prof_bytes_, (size_t)U * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            prof_laid_out_ = true;
-        }
-        // behind the run: its caller's stream has waited for every side stream at the end of run(); the events themselves once more for
-        // a caller that profiles on another stream
-        if (s != stream_) { HIP_CK(hipEventRecord(L->ev_prof_src, stream_)); HIP_CK(hipStreamWaitEvent(s, L->ev_prof_src, 0)); }
+    // ---- on-request results: both profiles (ambi_profile.hpp, ambi_junc_profile.hpp) and the sequences below ----
+    // A request works on `stream` behind everything that writes the result blob in the last run: the caller's stream of that run,
+    // which has waited for every side stream at the end of run(), and -- for a caller that asks on another stream -- explicitly the
+    // events "results complete" of the side streams (lean / list finish kernels, direct edit + full launch) and of the express
+    // kernel.  behind_results() holds these waits for all three requests; src: the request's own event for the run's stream.
+    int behind_results(hipStream_t s, hipEvent_t src) {
+        if (s != stream_) { HIP_CK(hipEventRecord(src, stream_)); HIP_CK(hipStreamWaitEvent(s, src, 0)); }
         if (overlap_back_) {
             HIP_CK(hipStreamWaitEvent(s, ev_back_, 0));
             if (direct_n_ > 0) HIP_CK(hipStreamWaitEvent(s, ev_full_, 0));
         }
         if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
-        const char* e = ambi_env("AMBI_PROFILE_WINDOW");
-        const int window = profile_window(hb().max_n, e ? atoi(e) : 0);
-        const int lds = kProfileScratchBytes + (int)profile_bins_bytes(window);
-        if (prof_queued_) HIP_CK(hipStreamWaitEvent(s, L->ev_prof_done, 0));   // (an earlier profile nobody waited for: its copy still reads the block)
+        return 0;
+    }
+    // The two profiles are instances of one on-request block (Lease::prof, req_, Backend::prof_); a kind has its own layout, its own
+    // kernel with its LDS size, and nothing else.  profile() queues the kind's kernel behind the run, then ONE device-to-host copy of
+    // the block on the lease's copy stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes
+    // the results final (wait(): the first run done again with a larger arena, units finished by the parallel search) and, if that
+    // moved the results' epoch after the kernel was queued, queues kernel and copy once more.
+    int profile_queue(ProfileKind kind, int which, hipStream_t s) {
+        Lease* L = lease_;
+        RequestBlock& B = L->prof[kind]; Request& R = req_[kind]; ProfileState& P = prof_[kind];
+        const int64_t U = (int64_t)hb().units.size();
+        if (!R.laid_out) {
+            profile_layout(kind);
+            const int64_t total = P.bytes + U * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
+            if (int rc = lease_device_block(&B.d, &B.d_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&B.h, nullptr, &B.h_bytes, total)) return rc;
+            if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
+            for (hipEvent_t* e : {&B.ev_src, &B.ev_packed, &B.ev_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
+            memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
+            R.d_off = reinterpret_cast<int64_t*>(B.d + P.bytes);
+            HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)U * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            R.laid_out = true;
+        }
+        if (int rc = behind_results(s, B.ev_src)) return rc;
+        int window = 0, jwin = 0, slots = 0, swin = 0, lds = kProfileScratchBytes;
+        if (kind == kJunction) { junc_profile_windows(&jwin, &slots, &swin); lds += (int)junc_profile_lds_bytes(slots, swin); }
+        else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
+        if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
         const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        hipLaunchKernelGGL(ambi_path_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, window, L->d_prof, (const int64_t*)d_prof_off_);
+        if (kind == kJunction) hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, B.d, (const int64_t*)R.d_off);
+        else hipLaunchKernelGGL(ambi_path_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, window, B.d, (const int64_t*)R.d_off);
         HIP_CK(hipGetLastError());
-        HIP_CK(hipEventRecord(L->ev_prof_packed, s));
-        HIP_CK(hipStreamWaitEvent(L->copy_stream, L->ev_prof_packed, 0));
-        HIP_CK(hipMemcpyAsync(L->h_prof, L->d_prof, (size_t)prof_bytes_, hipMemcpyDeviceToHost, L->copy_stream));
-        HIP_CK(hipEventRecord(L->ev_prof_done, L->copy_stream));
-        prof_which_ = which; prof_stream_ = s; prof_epoch_ = epoch_; prof_queued_ = true;
-        prof_view_ = nullptr;
+        HIP_CK(hipEventRecord(B.ev_packed, s));
+        HIP_CK(hipStreamWaitEvent(L->copy_stream, B.ev_packed, 0));
+        HIP_CK(hipMemcpyAsync(B.h, B.d, (size_t)P.bytes, hipMemcpyDeviceToHost, L->copy_stream));
+        HIP_CK(hipEventRecord(B.ev_done, L->copy_stream));
+        R.which = which; R.stream = s; R.epoch = epoch_; R.queued = true;
+        P.view = nullptr;
         return 0;
     }
-    int profile(int which, void* stream) override {
+    int profile(ProfileKind kind, int which, void* stream) override {
         DeviceGuard dg_(device_);
         if (!ran_ || !lease_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
         prof_hb_ = hbp_;
-        return profile_queue(which, (hipStream_t)stream);
+        return profile_queue(kind, which, (hipStream_t)stream);
     }
-    int profile_wait() override {
+    int profile_wait(ProfileKind kind) override {
         DeviceGuard dg_(device_);
-        if (!prof_queued_) return ST_ERR_BAD_INPUT;
+        const Request& R = req_[kind];
+        if (!R.queued) return ST_ERR_BAD_INPUT;
         if (int rc = wait()) return rc;
-        if (epoch_ != prof_epoch_) { if (int rc = profile_queue(prof_which_, prof_stream_)) return rc; }
-        HIP_CK(hipEventSynchronize(lease_->ev_prof_done));
-        prof_view_ = lease_->h_prof;
+        if (epoch_ != R.epoch) { if (int rc = profile_queue(kind, R.which, R.stream)) return rc; }
+        HIP_CK(hipEventSynchronize(lease_->prof[kind].ev_done));
+        prof_[kind].view = lease_->prof[kind].h;
         return 0;
     }
-    int profile_device(void** ptr, int64_t* bytes) override {
-        if (!prof_view_ || !lease_) return ST_ERR_BAD_INPUT;
-        if (ptr) *ptr = lease_->d_prof;
-        if (bytes) *bytes = prof_bytes_;
-        return 0;
-    }
-    // ---- junction usage profile of the paths (ambi_junc_profile.hpp) ----
-    // The profile's twin: junc_profile() queues ambi_junc_profile_kernel on `stream` behind everything that writes the result blob
-    // in the last run, then ONE device-to-host copy of the block on the lease's copy stream; junc_profile_wait() makes the results
-    // final (wait()) and, if that moved the results' epoch after the kernel was queued, queues kernel and copy once more.
-    bool jprof_queued_ = false, jprof_laid_out_ = false;
-    int jprof_which_ = 1; int64_t jprof_epoch_ = -1; hipStream_t jprof_stream_ = nullptr;
-    int64_t* d_jprof_off_ = nullptr;
-    int junc_profile_queue(int which, hipStream_t s) {
-        Lease* L = lease_;
-        const int64_t U = (int64_t)hb().units.size();
-        if (!jprof_laid_out_) {
-            jprof_bytes_ = junc_profile_block_layout(hb().units, jprof_off_);
-            const int64_t total = jprof_bytes_ + U * (int64_t)sizeof(int64_t);   // (jprof_bytes_ is a multiple of 16)
-            if (int rc = lease_device_block(&L->d_jprof, &L->d_jprof_bytes, total)) return rc;
-            if (int rc = lease_pinned_block(&L->h_jprof, nullptr, &L->h_jprof_bytes, total)) return rc;
-            if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&L->ev_jprof_src, &L->ev_jprof_packed, &L->ev_jprof_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-            // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
-            memcpy(L->h_jprof + jprof_bytes_, jprof_off_.data(), (size_t)U * sizeof(int64_t));
-            d_jprof_off_ = reinterpret_cast<int64_t*>(L->d_jprof + jprof_bytes_);
-            HIP_CK(hipMemcpyAsync(d_jprof_off_, L->h_jprof + jprof_bytes_, (size_t)U * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            jprof_laid_out_ = true;
-        }
-        if (s != stream_) { HIP_CK(hipEventRecord(L->ev_jprof_src, stream_)); HIP_CK(hipStreamWaitEvent(s, L->ev_jprof_src, 0)); }
-        if (overlap_back_) {
-            HIP_CK(hipStreamWaitEvent(s, ev_back_, 0));
-            if (direct_n_ > 0) HIP_CK(hipStreamWaitEvent(s, ev_full_, 0));
-        }
-        if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
-        int jwin, slots, swin;
-        junc_profile_windows(&jwin, &slots, &swin);
-        const int lds = kProfileScratchBytes + (int)junc_profile_lds_bytes(slots, swin);
-        if (jprof_queued_) HIP_CK(hipStreamWaitEvent(s, L->ev_jprof_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
-        const int grid = (int)(U < 16384 ? U : 16384);
-        hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, L->d_jprof, (const int64_t*)d_jprof_off_);
-        HIP_CK(hipGetLastError());
-        HIP_CK(hipEventRecord(L->ev_jprof_packed, s));
-        HIP_CK(hipStreamWaitEvent(L->copy_stream, L->ev_jprof_packed, 0));
-        HIP_CK(hipMemcpyAsync(L->h_jprof, L->d_jprof, (size_t)jprof_bytes_, hipMemcpyDeviceToHost, L->copy_stream));
-        HIP_CK(hipEventRecord(L->ev_jprof_done, L->copy_stream));
-        jprof_which_ = which; jprof_stream_ = s; jprof_epoch_ = epoch_; jprof_queued_ = true;
-        jprof_view_ = nullptr;
-        return 0;
-    }
-    int junc_profile(int which, void* stream) override {
-        DeviceGuard dg_(device_);
-        if (!ran_ || !lease_ || which < 0 || which > 1) return ST_ERR_BAD_INPUT;
-        prof_hb_ = hbp_;
-        return junc_profile_queue(which, (hipStream_t)stream);
-    }
-    int junc_profile_wait() override {
-        DeviceGuard dg_(device_);
-        if (!jprof_queued_) return ST_ERR_BAD_INPUT;
-        if (int rc = wait()) return rc;
-        if (epoch_ != jprof_epoch_) { if (int rc = junc_profile_queue(jprof_which_, jprof_stream_)) return rc; }
-        HIP_CK(hipEventSynchronize(lease_->ev_jprof_done));
-        jprof_view_ = lease_->h_jprof;
-        return 0;
-    }
-    int junc_profile_device(void** ptr, int64_t* bytes) override {
-        if (!jprof_view_ || !lease_) return ST_ERR_BAD_INPUT;
-        if (ptr) *ptr = lease_->d_jprof;
-        if (bytes) *bytes = jprof_bytes_;
+    int profile_device(ProfileKind kind, void** ptr, int64_t* bytes) override {
+        if (!prof_[kind].view || !lease_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->prof[kind].d;
+        if (bytes) *bytes = prof_[kind].bytes;
         return 0;
     }
     // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----
-    // sequence() works on `stream` behind everything that writes the result blob in the last run, as profile_queue does: the
+    // sequence() works on `stream` behind everything that writes the result blob in the last run (behind_results): the
     // sequence image if the device does not hold this version of it (pinned twin, one copy), pass 0 of the extents kernel, the
     // totals to the pinned twin and ONE stream synchronisation -- the small device-to-host trip that sizes the extent arrays and the
     // output block (an on-request call: the run it follows is complete by then) -- the three offset tables up, pass 1 and the fill
@@ -2301,12 +2248,7 @@ class HipBackend : public Backend {
         seq_state_ = 0; seq_queued_ = false;
         seq_which_ = which; seq_first_ = first; seq_count_ = count; seq_max_ = max_bytes; seq_stream_ = s; seq_epoch_ = epoch_;
         if (int rc = sequence_image(s)) return rc;
-        if (s != stream_) { HIP_CK(hipEventRecord(L->ev_seq_src, stream_)); HIP_CK(hipStreamWaitEvent(s, L->ev_seq_src, 0)); }
-        if (overlap_back_) {
-            HIP_CK(hipStreamWaitEvent(s, ev_back_, 0));
-            if (direct_n_ > 0) HIP_CK(hipStreamWaitEvent(s, ev_full_, 0));
-        }
-        if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
+        if (int rc = behind_results(s, L->ev_seq_src)) return rc;
         // working block: [totals: 2 count] [ext_off: count + 1] [out_off: count] [tile_off: count + 1] | [ext_src: slots] [ext_out: slots]
         const int64_t c = count, tab = 16 * c, head = pad16(tab + 8 * (3 * c + 2));
         if (int rc = lease_device_block(&L->d_seq_work, &L->d_seq_work_bytes, head)) return rc;

@@ -403,6 +403,43 @@ def check_big_unit_finished_at_wait(lib, oracle, workdir):
     pc.close_all(graphs, b)
 
 
+# ---- case 8b: the queueing path's other branches ---------------------------------------------------------------------
+def check_request_paths(lib, oracle, workdir, run_stream=None, req_stream=None):
+    """As profile_checks.check_request_paths: a request on another stream than the run's (None on the host simulation), a request
+    nobody waited for followed by another, and a batch closed with a request in flight whose lease the next batch takes over."""
+    graphs, b, items = many_items(lib, oracle, workdir)
+    b.upload()
+
+    def compare(which, tag):
+        for u, (lh, g, oc) in enumerate(items):
+            idx, count, summary, _ = unit_expectation(lh, g, oc, which)
+            compare_unit(b, u, idx, count, summary, (tag, which, u))
+    # (1) run on one stream, request on another, nothing waited for in between
+    for which in (0, 1):
+        b.run(0, run_stream)
+        b.junc_profile(which, req_stream); b.junc_profile_wait()
+        compare(which, "other stream")
+    # the two paths give different counts somewhere: (2) can tell which request the getters answer for
+    assert any(unit_expectation(lh, g, oc, 0)[1] != unit_expectation(lh, g, oc, 1)[1] for lh, g, oc in items)
+    # (2) a request nobody waited for, then another: the second one answers; again after another run; then a single request
+    for k in range(2):
+        b.run(0, run_stream)
+        b.junc_profile(0, req_stream); b.junc_profile(1, req_stream); b.junc_profile_wait()
+        compare(1, ("unwaited", k))
+    b.run(0, run_stream)
+    b.junc_profile(0, req_stream); b.junc_profile_wait()
+    compare(0, "single after unwaited")
+    # (3) closed with a request in flight; the next batch (other units, other offsets) gets the lease back
+    b.run(0, run_stream)
+    b.junc_profile(1, req_stream)
+    pc.close_all(graphs, b)
+    sub = pc.many_units(oracle, workdir)[3:20]
+    graphs, b = pc.many_batch(lib, sub)
+    b.upload(); b.run(0, run_stream)
+    check_batch(b, [(lh, g, oc) for (lh, _, oc), g in zip(sub, graphs)], "after a close in flight")
+    pc.close_all(graphs, b)
+
+
 # ---- case 9: sharded -------------------------------------------------------------------------------------------------
 def check_sharded(lib, oracle, workdir, devices):
     import pytest

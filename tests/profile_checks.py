@@ -257,6 +257,49 @@ def check_big_unit_finished_at_wait(lib, oracle, workdir):
     close_all(graphs, b)
 
 
+# ---- case 6b: the queueing path's other branches ---------------------------------------------------------------------
+def check_request_paths(lib, oracle, workdir, run_stream=None, req_stream=None):
+    """A request on another stream than the run's (run_stream / req_stream: raw stream handles; None on the host simulation, where
+    the same calls go through the default path), a request nobody waited for followed by another, and a batch closed with a
+    request in flight whose lease the next batch takes over."""
+    items = many_units(oracle, workdir)
+    records = [oc for _, _, oc in items]
+    graphs, b = many_batch(lib, items)
+    b.upload()
+
+    def compare(which, tag):
+        for u, oc in enumerate(records):
+            n, want = unit_expectation(b, u, oc, which)
+            compare_unit(b, u, n, want, (tag, which, u))
+    # (1) run on one stream, request on another, nothing waited for in between
+    for which in (0, 1):
+        b.run(0, run_stream)
+        b.profile(which, req_stream); b.profile_wait()
+        b.download()
+        compare(which, "other stream")
+    # the two paths give different profiles somewhere: (2) can tell which request the getters answer for
+    assert any(unit_expectation(b, u, oc, 0)[1][0].tolist() != unit_expectation(b, u, oc, 1)[1][0].tolist() for u, oc in enumerate(records))
+    # (2) a request nobody waited for, then another: the second one answers; again after another run; then a single request
+    for k in range(2):
+        b.run(0, run_stream)
+        b.profile(0, req_stream); b.profile(1, req_stream); b.profile_wait()
+        b.download()
+        compare(1, ("unwaited", k))
+    b.run(0, run_stream)
+    b.profile(0, req_stream); b.profile_wait()
+    b.download()
+    compare(0, "single after unwaited")
+    # (3) closed with a request in flight; the next batch (other units, other offsets) gets the lease back
+    b.run(0, run_stream)
+    b.profile(1, req_stream)
+    close_all(graphs, b)
+    sub = items[3:20]
+    graphs, b = many_batch(lib, sub)
+    b.upload(); b.run(0, run_stream); b.download()
+    check_batch(b, [oc for _, _, oc in sub], "after a close in flight")
+    close_all(graphs, b)
+
+
 # ---- case 7: argument and state errors ------------------------------------------------------------------------------
 def check_errors(lib):
     import pytest

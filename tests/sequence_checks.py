@@ -376,6 +376,62 @@ def check_big_unit_finished_at_wait(lib, oracle, workdir):
     pc.close_all(graphs, b)
 
 
+# ---- case 5b: the queueing path's other branches ---------------------------------------------------------------------------
+def check_request_paths(lib, oracle, workdir, run_stream=None, req_stream=None):
+    """A request on another stream than the run's (run_stream / req_stream: raw stream handles; None on the host simulation), two
+    requests over different unit ranges with one wait, and a batch closed with a request in flight whose lease the next batch
+    takes over."""
+    items, records, seg_lists, _ = many_sequences(oracle, workdir)
+    U = len(items)
+    full = {which: [want_of(oc, which, segs) for oc, segs in zip(records, seg_lists)] for which in (0, 1)}
+    graphs, b = many_batch(lib, items, seg_lists)
+    b.upload()
+    # (1) run on one stream, request on another, nothing waited for in between
+    for which in (0, 1):
+        b.run(0, run_stream)
+        b.sequence(which, stream=req_stream); b.sequence_wait()
+        compare_units(b, full[which], ("other stream", which))
+    # (2) a request nobody waited for, then another over other units: the second range answers; the same after another run
+    for k in range(2):
+        b.run(0, run_stream)
+        b.sequence(1, 0, 9, stream=req_stream); b.sequence(1, 5, 17, stream=req_stream); b.sequence_wait()
+        compare_units(b, full[1][5:22], ("unwaited", k), 5)
+        for u in (0, 4, 22, U - 1):
+            with pytest.raises(api.AmbiError) as e:
+                b.unit_sequence_len(u)                         # outside the second request (0 and 4 were inside the first)
+            assert e.value.code == ERR_ARG, u
+    # (3) closed with a request in flight; the next batch (other units, another image) gets the lease back
+    b.run(0, run_stream)
+    b.sequence(1, stream=req_stream)
+    pc.close_all(graphs, b)
+    graphs, b = many_batch(lib, items[3:20], seg_lists[3:20])
+    b.upload(); b.run(0, run_stream)
+    for which in (0, 1):
+        b.sequence(which); b.sequence_wait()
+        compare_units(b, full[which][3:20], ("after a close in flight", which))
+    pc.close_all(graphs, b)
+
+
+def check_three_requests_in_flight(lib, oracle, workdir, run_stream=None, req_stream=None):
+    """Both profiles and a sequence request queued back to back, waited for in the opposite order: each answers for itself."""
+    import junc_profile_checks as jc
+    items, records, seg_lists, _ = many_sequences(oracle, workdir)
+    graphs, b = many_batch(lib, items, seg_lists)
+    b.upload()
+    for which in (1, 0):
+        b.run(0, run_stream)
+        b.profile(which, req_stream); b.junc_profile(which, req_stream); b.sequence(which, 5, 17, stream=req_stream)
+        b.sequence_wait(); b.junc_profile_wait(); b.profile_wait()
+        b.download()
+        for u, ((lh, _, oc), g) in enumerate(zip(items, graphs)):
+            n, want = pc.unit_expectation(b, u, oc, which)
+            pc.compare_unit(b, u, n, want, ("three", which, u))
+            idx, count, summary, _ = jc.unit_expectation(lh, g, oc, which)
+            jc.compare_unit(b, u, idx, count, summary, ("three", which, u))
+        compare_units(b, [want_of(oc, which, segs) for oc, segs in zip(records[5:22], seg_lists[5:22])], ("three", which), 5)
+    pc.close_all(graphs, b)
+
+
 # ---- case 6: sharded ------------------------------------------------------------------------------------------------------
 def check_sharded(lib, oracle, workdir, devices):
     items, records, seg_lists, _ = many_sequences(oracle, workdir)

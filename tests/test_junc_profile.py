@@ -70,6 +70,10 @@ def test_cli_junc_profile(hostsim_lib, oracle, workdir, tmp_path):
     jc.check_cli(hostsim_lib, exe, str(tmp_path), oracle, workdir)
 
 
+def test_request_paths(hostsim_lib, oracle, workdir):
+    jc.check_request_paths(hostsim_lib, oracle, workdir)
+
+
 def test_errors(hostsim_lib):
     jc.check_errors(hostsim_lib)
 
@@ -175,6 +179,14 @@ def test_gpu_cli_junc_profile(hip_lib, oracle, workdir, tmp_path):
     exe = os.path.join(ROOT, "ambigram_amd", "bin", "Ambigram")
     assert os.path.exists(exe), "build the CLI first (__graft_entry__.build)"
     jc.check_cli(hip_lib, exe, str(tmp_path), oracle, workdir)
+
+
+@pytest.mark.gpu
+def test_gpu_request_paths(hip_lib, oracle, workdir):
+    """The run on one stream, every request on another."""
+    import torch
+    run_s, req_s = torch.cuda.Stream(), torch.cuda.Stream()
+    jc.check_request_paths(hip_lib, oracle, workdir, run_s.cuda_stream, req_s.cuda_stream)
 
 
 @pytest.mark.gpu

@@ -41,6 +41,10 @@ def test_big_unit_finished_at_wait(hostsim_lib, oracle, workdir):
     pc.check_big_unit_finished_at_wait(hostsim_lib, oracle, workdir)
 
 
+def test_request_paths(hostsim_lib, oracle, workdir):
+    pc.check_request_paths(hostsim_lib, oracle, workdir)
+
+
 def test_errors(hostsim_lib):
     pc.check_errors(hostsim_lib)
 
@@ -130,6 +134,14 @@ def test_gpu_three_chromosomes(hip_lib, oracle, workdir):
 @pytest.mark.gpu
 def test_gpu_big_unit_finished_at_wait(hip_lib, oracle, workdir):
     pc.check_big_unit_finished_at_wait(hip_lib, oracle, workdir)
+
+
+@pytest.mark.gpu
+def test_gpu_request_paths(hip_lib, oracle, workdir):
+    """The run on one stream, every request on another."""
+    import torch
+    run_s, req_s = torch.cuda.Stream(), torch.cuda.Stream()
+    pc.check_request_paths(hip_lib, oracle, workdir, run_s.cuda_stream, req_s.cuda_stream)
 
 
 @pytest.mark.gpu

@@ -43,6 +43,14 @@ def test_big_unit_finished_at_wait(hostsim_lib, oracle, workdir):
     sc.check_big_unit_finished_at_wait(hostsim_lib, oracle, workdir)
 
 
+def test_request_paths(hostsim_lib, oracle, workdir):
+    sc.check_request_paths(hostsim_lib, oracle, workdir)
+
+
+def test_three_requests_in_flight(hostsim_lib, oracle, workdir):
+    sc.check_three_requests_in_flight(hostsim_lib, oracle, workdir)
+
+
 def test_sharded_sequence(hostsim_lib, oracle, workdir):
     sc.check_sharded(hostsim_lib, oracle, workdir, [0, 0, 0])
 
@@ -122,6 +130,21 @@ def test_gpu_two_runs(hip_lib, oracle, workdir):
 @pytest.mark.gpu
 def test_gpu_big_unit_finished_at_wait(hip_lib, oracle, workdir):
     sc.check_big_unit_finished_at_wait(hip_lib, oracle, workdir)
+
+
+@pytest.mark.gpu
+def test_gpu_request_paths(hip_lib, oracle, workdir):
+    """The run on one stream, every request on another."""
+    import torch
+    run_s, req_s = torch.cuda.Stream(), torch.cuda.Stream()
+    sc.check_request_paths(hip_lib, oracle, workdir, run_s.cuda_stream, req_s.cuda_stream)
+
+
+@pytest.mark.gpu
+def test_gpu_three_requests_in_flight(hip_lib, oracle, workdir):
+    import torch
+    run_s, req_s = torch.cuda.Stream(), torch.cuda.Stream()
+    sc.check_three_requests_in_flight(hip_lib, oracle, workdir, run_s.cuda_stream, req_s.cuda_stream)
 
 
 @pytest.mark.gpu
