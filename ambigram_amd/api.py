@@ -44,6 +44,11 @@ class UnitJuncProfile(C.Structure):     # ambi_unit_junc_profile_t
                                          "max_count", "n_over", "n_under")]
 
 
+class UnitFragProfile(C.Structure):     # ambi_unit_frag_profile_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "cells", "frags", "frags_supported", "first_unsupported", "max_count", "longest_supported",
+                                         "reserved")] + [("occurrences", C.c_int64)]
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -119,6 +124,15 @@ def _declare(L):
         "ambi_batch_junc_profile_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_graph_set_sequences": (C.c_int, [vp, vp, pi64]),
         "ambi_graph_read_fasta": (C.c_int, [vp, C.c_char_p]),
+        "ambi_graph_read_fragments": (C.c_int, [vp, C.c_char_p]),
+        "ambi_graph_set_fragments": (C.c_int, [vp, pi32, pi64, i32]),
+        "ambi_graph_fragments": (i32, [vp, pi32, i64, pi64, i32, pi32]),
+        "ambi_batch_set_unit_fragments": (C.c_int, [vp, i32, pi32, pi64, i32]),
+        "ambi_batch_frag_profile": (C.c_int, [vp, i32, vp]),
+        "ambi_batch_frag_profile_wait": (C.c_int, [vp]),
+        "ambi_batch_unit_frag_profile": (C.c_int, [vp, i32, _P(UnitFragProfile)]),
+        "ambi_batch_unit_frag_support": (C.c_int, [vp, i32, pi32, pi32, pi32, pi32, i32]),
+        "ambi_batch_frag_profile_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
         "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
         "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
@@ -248,6 +262,33 @@ class Graph:
         if rc != 0:
             raise AmbiError(self.lib, rc, "read_juncs")
         self._refresh()
+
+    def read_fragments(self, path):
+        """Every non-empty line of a .juncs file as one signed chain of segment ids (ambi_graph_read_fragments), the evidence
+        Batch.frag_profile checks the paths against; the graph itself stays as it is.  Before the chromosomes are added to a batch."""
+        rc = self.lib.ambi_graph_read_fragments(self.h, path.encode())
+        if rc != 0:
+            raise AmbiError(self.lib, rc, "read_fragments")
+
+    def set_fragments(self, fragments):
+        """The same from memory (ambi_graph_set_fragments): a list of chains of signed segment ids."""
+        cells, pc = _arr([v for f in fragments for v in f], np.int32)
+        off, po = _arr(np.concatenate([[0], np.cumsum([len(f) for f in fragments])]), np.int64)
+        rc = self.lib.ambi_graph_set_fragments(self.h, pc, po, len(fragments))
+        if rc != 0:
+            raise AmbiError(self.lib, rc, "set_fragments")
+
+    def fragments(self):
+        """(fragments, unit_chr): the attached chains as lists of signed segment ids, and per fragment the chromosome index it
+        belongs to (-1: fewer than two cells or spanning chromosomes)."""
+        n = self.lib.ambi_graph_fragments(self.h, None, 0, None, 0, None)
+        if n < 0:
+            raise AmbiError(self.lib, int(n), "fragments")
+        off = np.zeros(n + 1, np.int64); chr_ = np.zeros(max(n, 1), np.int32)
+        self.lib.ambi_graph_fragments(self.h, None, 0, off.ctypes.data_as(_P(C.c_int64)), n + 1, chr_.ctypes.data_as(_P(C.c_int32)))
+        cells = np.zeros(max(int(off[n]), 1), np.int32)
+        self.lib.ambi_graph_fragments(self.h, cells.ctypes.data_as(_P(C.c_int32)), int(off[n]), None, 0, None)
+        return [cells[off[f]:off[f + 1]].tolist() for f in range(n)], chr_[:n].tolist()
 
     def set_sequences(self, bases, seg_off):
         """Attaches the segments' bases (ambi_graph_set_sequences): segment id i + 1 = bases[seg_off[i]:seg_off[i + 1]], any byte
@@ -582,6 +623,44 @@ class Batch:
         """(address, bytes) of the junction profile block in device memory (ambi_batch_junc_profile_device), for collectives."""
         p, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.ambi_batch_junc_profile_device(self.h, C.byref(p), C.byref(n)), "junc_profile_device")
+        return p.value or 0, n.value
+
+    def set_unit_fragments(self, u, fragments):
+        """Fragments of a unit added with add_unit (ambi_batch_set_unit_fragments): a list of chains of LOCAL signed ids, two cells
+        each at least."""
+        cells, pc = _arr([v for f in fragments for v in f], np.int32)
+        off, po = _arr(np.concatenate([[0], np.cumsum([len(f) for f in fragments])]), np.int64)
+        self._ck(self.lib.ambi_batch_set_unit_fragments(self.h, u, pc, po, len(fragments)), "set_unit_fragments")
+
+    def frag_profile(self, which=1, stream=None):
+        """Queues the fragment support profile of the last run's paths behind that run (ambi_batch_frag_profile): per fragment of a
+        unit how often the path (which: 0 getBFB's, 1 the final one) contains it, forward and reverse-complemented, and where first;
+        `stream` is not blocked."""
+        self._ck(self.lib.ambi_batch_frag_profile(self.h, which, C.c_void_p(stream or 0)), "frag_profile")
+
+    def frag_profile_wait(self):
+        """Waits for the fragment profile in host memory (the run's results are final first); unit_frag_profile / unit_frag_support
+        answer afterwards."""
+        self._ck(self.lib.ambi_batch_frag_profile_wait(self.h), "frag_profile_wait")
+
+    def unit_frag_profile(self, u):
+        r = UnitFragProfile()
+        self._ck(self.lib.ambi_batch_unit_frag_profile(self.h, u, C.byref(r)), "unit_frag_profile")
+        return {k: getattr(r, k) for k, _ in UnitFragProfile._fields_}
+
+    def unit_frag_support(self, u):
+        """(fwd, rev, first, graph_index): int32 arrays over the unit's fragments -- occurrences of the fragment, of its reverse
+        complement, the smallest position of either (-1: none), and the fragment's index in Graph.fragments() (its own for a unit
+        added with add_unit)."""
+        F = self._ck(self.lib.ambi_batch_unit_frag_support(self.h, u, None, None, None, None, 1 << 30), "unit_frag_support")
+        out = [np.zeros(F, np.int32) for _ in range(4)]
+        self._ck(self.lib.ambi_batch_unit_frag_support(self.h, u, *[a.ctypes.data_as(_P(C.c_int32)) for a in out], F), "unit_frag_support")
+        return tuple(out)
+
+    def frag_profile_device(self):
+        """(address, bytes) of the fragment profile block in device memory (ambi_batch_frag_profile_device), for collectives."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._ck(self.lib.ambi_batch_frag_profile_device(self.h, C.byref(p), C.byref(n)), "frag_profile_device")
         return p.value or 0, n.value
 
     def set_unit_sequences(self, u, bases, seg_off):

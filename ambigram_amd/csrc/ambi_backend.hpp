@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ambi_pack.hpp"
+#include "ambi_frag_profile.hpp"
 #include "ambi_junc_profile.hpp"
 #include "ambi_profile.hpp"
 #include "ambi_sequence.hpp"
@@ -85,13 +86,15 @@ class Backend {
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
 
     // ---- on-request profiles of every unit's path (which: 0 getBFB, 1 after indelBFB) ----
-    // Two kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand) and the
-    // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts), each a block [summary[U]][per unit counts].
+    // Three kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand), the
+    // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts) and the fragment support profile
+    // (ambi_frag_profile.hpp: occurrences of every .juncs fragment in either direction), each a block [summary[U]][per unit counts].
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
     // simulation); the HIP engine overrides the three virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    enum ProfileKind { kCopyNumber = 0, kJunction = 1 };
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2 };
+    static constexpr int kProfileKinds = 3;
     void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
     virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
@@ -101,7 +104,9 @@ class Backend {
         ProfileState& P = prof_[kind];
         profile_layout(kind);
         P.blob.assign((size_t)P.bytes, 0);
-        if (kind == kJunction) host_junc_profile(blob.data(), which, P); else host_profile(blob.data(), which, P);
+        if (kind == kFragment) host_frag_profile(blob.data(), which, P);
+        else if (kind == kJunction) host_junc_profile(blob.data(), which, P);
+        else host_profile(blob.data(), which, P);
         P.view = nullptr;
         return 0;
     }
@@ -148,6 +153,25 @@ class Backend {
         if (cap < m) return ST_ERR_BAD_INPUT;
         if (count && m > 0) memcpy(count, P.view + P.off[(size_t)unit], sizeof(int32_t) * (size_t)m);
         return m;
+    }
+
+    int frag_profile_summary(int unit, UnitFragProfile* out) const {
+        const ProfileState& P = prof_[kFragment];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitFragProfile*>(P.view)[unit];
+        return 0;
+    }
+    int frag_profile_counts(int unit, int32_t* fwd, int32_t* rev, int32_t* first, int cap) const {   // F values each; returns F
+        const ProfileState& P = prof_[kFragment];
+        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size() || (size_t)unit >= prof_hb_->frag.n_frag.size()) return ST_ERR_BAD_INPUT;
+        const int F = prof_hb_->frag.n_frag[(size_t)unit];
+        if (cap < F) return ST_ERR_BAD_INPUT;
+        const uint8_t* p = P.view + P.off[(size_t)unit];
+        const int64_t arr = frag_profile_arr_bytes(F);
+        if (fwd && F > 0) memcpy(fwd, p, sizeof(int32_t) * (size_t)F);
+        if (rev && F > 0) memcpy(rev, p + arr, sizeof(int32_t) * (size_t)F);
+        if (first && F > 0) memcpy(first, p + 2 * arr, sizeof(int32_t) * (size_t)F);
+        return F;
     }
 
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
@@ -225,10 +249,17 @@ class Backend {
         const uint8_t* view = nullptr;
         std::vector<uint8_t> blob;
     };
-    ProfileState prof_[2];               // [ProfileKind]
+    ProfileState prof_[kProfileKinds];   // [ProfileKind]
     void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
         ProfileState& P = prof_[kind];
-        P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
+        if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
+        else P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
+    }
+    // patterns per window and table slots of the bound batch (AMBI_FPROFILE_FRAG_WINDOW can only shrink the window)
+    void frag_profile_windows(int* pwin, int* slots) const {
+        const char* e = ambi_env("AMBI_FPROFILE_FRAG_WINDOW");
+        *pwin = frag_window(prof_hb_->frag.max_f, e ? atoi(e) : 0);
+        *slots = frag_slots(*pwin);
     }
     int profile_window_of() const {      // segments per window of the bound batch (AMBI_PROFILE_WINDOW can only shrink it)
         const char* e = ambi_env("AMBI_PROFILE_WINDOW");
@@ -271,6 +302,17 @@ class Backend {
         HostGroup g;
         for (size_t u = 0; u < units.size(); u++)
             junc_profile_unit(g, units.data(), prof_hb_->junc_ends.data(), prof_hb_->junc_cn.data(), blob, (int)u, which, jwin, T, P.blob.data(), P.off.data());
+    }
+    void host_frag_profile(const uint8_t* blob, int which, ProfileState& P) {
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        const FragImage& I = prof_hb_->frag;
+        int pwin, slots;
+        frag_profile_windows(&pwin, &slots);
+        std::vector<int32_t> lds((size_t)(frag_profile_lds_bytes(slots, pwin) / 4));
+        const FragTable T = frag_table(lds.data(), slots, pwin);
+        const FragArgs A{I.cells.data(), I.frag_off.data(), I.cell_off.data(), I.pref_off.data(), I.n_frag.data()};
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++) frag_profile_unit(g, units.data(), A, blob, (int)u, which, T, P.blob.data(), P.off.data());
     }
     std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };

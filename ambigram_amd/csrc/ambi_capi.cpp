@@ -115,7 +115,7 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled[2] = {false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    bool profiled[Backend::kProfileKinds] = {false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
@@ -227,6 +227,23 @@ int ambi_graph_chromosome(const ambi_graph_t* g, int32_t chr, int32_t* source_id
 int ambi_graph_read_juncs(ambi_graph_t* g, const char* juncs_path) {
     if (!g) return AMBI_ERR_ARG;
     return read_juncs(g->g, juncs_path ? juncs_path : "");
+}
+int ambi_graph_read_fragments(ambi_graph_t* g, const char* juncs_path) {
+    if (!g) return AMBI_ERR_ARG;
+    return read_fragments(g->g, juncs_path ? juncs_path : "");
+}
+int ambi_graph_set_fragments(ambi_graph_t* g, const int32_t* cells, const int64_t* frag_off, int32_t n) {
+    if (!g || n < 0 || (n > 0 && (!cells || !frag_off))) return AMBI_ERR_ARG;
+    return set_fragments(g->g, cells, frag_off, n);
+}
+int32_t ambi_graph_fragments(const ambi_graph_t* g, int32_t* cells, int64_t cap, int64_t* frag_off, int32_t off_cap, int32_t* unit_chr) {
+    if (!g) return AMBI_ERR_ARG;
+    const LhGraph& G = g->g;
+    const int n = G.n_frag();
+    if (cells) for (int64_t i = 0; i < (int64_t)G.frag_cells.size() && i < cap; i++) cells[i] = G.frag_cells[(size_t)i];
+    if (frag_off) for (int f = 0; f <= n && f < off_cap; f++) frag_off[f] = n > 0 ? G.frag_off[(size_t)f] : 0;
+    if (unit_chr && off_cap > n) for (int f = 0; f < n; f++) unit_chr[f] = fragment_chr(G, f);
+    return n;
 }
 int ambi_graph_set_sequences(ambi_graph_t* g, const uint8_t* bases, const int64_t* seg_off) {
     if (!g || !seg_off) return AMBI_ERR_ARG;
@@ -429,14 +446,14 @@ int ambi_batch_upload(ambi_batch_t* b) {
     b->be->profile_bind(&b->hb);
     int rc = b->be->upload(b->hb, b->cfg);
     if (rc == 0) b->uploaded = true;
-    b->ran = false; b->profiled[0] = b->profiled[1] = false; b->sequenced = false;
+    b->ran = false; b->profiled[0] = b->profiled[1] = b->profiled[2] = false; b->sequenced = false;
     b->be->sequence_reset();
     return rc;
 }
 int ambi_batch_run(ambi_batch_t* b, uint32_t flags, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!b->uploaded) return AMBI_ERR_STATE;
-    b->downloaded = false; b->mail_view = false; b->profiled[0] = b->profiled[1] = false; b->sequenced = false;
+    b->downloaded = false; b->mail_view = false; b->profiled[0] = b->profiled[1] = b->profiled[2] = false; b->sequenced = false;
     b->be->sequence_reset();
     const int rc = b->be->run(flags, hip_stream);
     if (rc == 0) b->ran = true;
@@ -500,7 +517,7 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
         for (auto& s : b->shards) s->hb.finalize();
     }
     b->hb.finalize();
-    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled[0] = b->profiled[1] = false; b->sequenced = false;
+    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled[0] = b->profiled[1] = b->profiled[2] = false; b->sequenced = false;
     for (auto& s : b->shards) s->be->sequence_reset();
     // every share on its own (resident) thread, the first one too: set_device changes the current device of the thread that calls it,
     // and the caller's thread keeps the device it had.  Nothing is merged: the getters read a unit where its share left it.
@@ -653,6 +670,10 @@ static int profile_start(ambi_batch_t* b, Backend::ProfileKind kind, int32_t whi
     if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
     if (which < 0 || which > 1) return AMBI_ERR_ARG;
     b->profiled[kind] = false;
+    if (kind == Backend::kFragment) {   // every unit has a prefix in the image from here on (F = 0 where nothing was attached)
+        b->hb.frag.seal(b->hb.units);
+        for (auto& s : b->shards) s->hb.frag.seal(s->hb.units);
+    }
     if (!b->sharded_ready) return b->be->profile(kind, which, hip_stream);
     for (auto& s : b->shards)
         if (!s->units.empty()) { if (int rc = s->be->profile(kind, which, s->be->own_stream())) return rc; }
@@ -716,6 +737,52 @@ int ambi_batch_unit_junc_usage(const ambi_batch_t* b, int32_t unit, int32_t* cou
     if (graph_index) {
         const std::vector<int32_t>& map = b->hb.junc_global[unit];   // (empty for a raw unit)
         for (int j = 0; j < m; j++) graph_index[j] = j < (int)map.size() ? map[j] : j;
+    }
+    return rc;
+}
+// ---- fragment support profile of the paths (ambi_frag_profile.hpp; the .juncs lines as chains) ----
+int ambi_batch_set_unit_fragments(ambi_batch_t* b, int32_t unit, const int32_t* cells, const int64_t* frag_off, int32_t n) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size() || n < 0 || n > kMaxUnitFrags || (n > 0 && (!cells || !frag_off || frag_off[0] != 0))) return AMBI_ERR_ARG;
+    if (!b->shards.empty()) return AMBI_ERR_STATE;   // (the shares hold copies of their units' fragments)
+    const int n_seg = b->hb.units[unit].n_seg;
+    for (int f = 0; f < n; f++) if (frag_off[f + 1] - frag_off[f] < 2) return AMBI_ERR_ARG;
+    const int64_t total = n > 0 ? frag_off[n] : 0;
+    if (total >= (int64_t(1) << 31)) return AMBI_ERR_ARG;
+    std::vector<rcell_t> local((size_t)total);
+    for (int64_t i = 0; i < total; i++) {
+        const int64_t id = cells[i] < 0 ? -(int64_t)cells[i] : cells[i];
+        if (id < 1 || id > n_seg) return AMBI_ERR_ARG;
+        local[(size_t)i] = (rcell_t)cells[i];
+    }
+    const int64_t zero = 0;
+    b->hb.frag.set((size_t)unit, local.data(), n > 0 ? frag_off : &zero, n, nullptr);
+    b->profiled[Backend::kFragment] = false;
+    return 0;
+}
+int ambi_batch_frag_profile(ambi_batch_t* b, int32_t which, void* hip_stream) { return profile_start(b, Backend::kFragment, which, hip_stream); }
+int ambi_batch_frag_profile_wait(ambi_batch_t* b) { return profile_wait(b, Backend::kFragment); }
+int ambi_batch_frag_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) { return profile_device(b, Backend::kFragment, dev_ptr, bytes); }
+int ambi_batch_unit_frag_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_frag_profile_t* out) {
+    if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kFragment]) return AMBI_ERR_STATE;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    static_assert(sizeof(ambi_unit_frag_profile_t) == sizeof(UnitFragProfile), "ambi_unit_frag_profile_t is ambi::UnitFragProfile");
+    return be->frag_profile_summary(local, reinterpret_cast<UnitFragProfile*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_unit_frag_support(const ambi_batch_t* b, int32_t unit, int32_t* fwd, int32_t* rev, int32_t* first, int32_t* graph_index, int32_t cap) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kFragment]) return AMBI_ERR_STATE;
+    const FragImage& I = b->hb.frag;
+    const int F = (size_t)unit < I.n_frag.size() ? I.n_frag[(size_t)unit] : 0;
+    if (cap < F) return AMBI_ERR_ARG;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    const int rc = be->frag_profile_counts(local, fwd, rev, first, cap);
+    if (rc < 0) return AMBI_ERR_STATE;
+    if (graph_index) {
+        const std::vector<int32_t>& map = I.graph_index[(size_t)unit];   // (empty for a raw unit)
+        for (int f = 0; f < F; f++) graph_index[f] = f < (int)map.size() ? map[f] : f;
     }
     return rc;
 }

@@ -21,6 +21,8 @@
 //                                                  (ambi_profile.hpp)                              <- read-bound, 2 bytes / cell
 //   ambi_junc_profile_kernel      1 block / unit   on request: per-junction traversal counts of the path + summary
 //                                                  (ambi_junc_profile.hpp)                         <- the same cells + a hash table in LDS
+//   ambi_frag_profile_kernel      1 block / unit   on request: occurrences of every .juncs fragment in the path, both directions,
+//                                                  + summary (ambi_frag_profile.hpp)               <- the same cells + chained patterns in LDS
 // Every kernel but the two plan kernels is a wrapper around the stage functions of ambi_stages.hpp (ambi_exchange.hpp,
 // ambi_profile.hpp for the pack / expand and profile kernels), which the host simulation runs as well, the four table kernels
 // (blocks_build, enumerate_blocks, enumerate, enumerate_wide; their logic is under stage_enumerate's banner) included.  The
@@ -607,6 +609,17 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_junc_profile_kernel(Batc
         __syncthreads();
     }
 }
+// ---- fragment support profile of the paths (ambi_frag_profile.hpp; launched by HipBackend::profile_queue only) ----
+// One workgroup of 256 threads per unit, grid-stride over the units.  Group memory: 256 bytes for the group's reductions, then
+// the hash table of `slots` first steps (key, chain head: 8 bytes each) and the window's `pwin` patterns (next, count, first: 12 bytes).
+__global__ __launch_bounds__(kProfileThreads) void ambi_frag_profile_kernel(BatchArgs A, FragArgs I, int which, int pwin, int slots, uint8_t* block, const int64_t* off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    const FragTable T = frag_table(ambi_lds + kProfileScratchBytes, slots, pwin);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        frag_profile_unit(g, A.units, I, A.results, u, which, T, block, off);
+        __syncthreads();
+    }
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -744,8 +757,14 @@ struct Lease {
     uint8_t* h_runs[2] = {nullptr, nullptr}; int64_t h_runs_bytes[2] = {0, 0};
     hipStream_t run_stream = nullptr;   // own_stream(): for callers without a stream (ambi_batch_run_sharded's shares)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
-    // [Backend::ProfileKind] copy-number profile [UnitProfile[U]][per unit fwd, rev], junction usage profile [UnitJuncProfile[U]][per unit count]
-    RequestBlock prof[2];
+    // [Backend::ProfileKind] copy-number profile [UnitProfile[U]][per unit fwd, rev], junction usage profile [UnitJuncProfile[U]][per unit count],
+    // fragment support profile [UnitFragProfile[U]][per unit fwd, rev, first]
+    RequestBlock prof[Backend::kProfileKinds];
+    // the batch's fragment image (HipBackend::fragment_image) [cells][frag_off][cell_off][pref_off][n_frag], its pinned twin and the
+    // event behind its last upload (the host writes the twin again only behind it)
+    uint8_t* d_frag_img = nullptr; int64_t d_frag_img_bytes = 0;
+    uint8_t* h_frag = nullptr; int64_t h_frag_bytes = 0;
+    hipEvent_t ev_frag_up = nullptr;
     // path sequences (HipBackend::sequence): the batch's sequence image [bases][seg_pos][store_off][pos_off], the working block of a
     // request [totals][ext_off, out_off, tile_off][ext_src][ext_out] and the output block; the pinned twin carries the image up, the
     // totals down and the three offset tables up.  Events: the run's stream reached / all queued work done / timing pairs
@@ -1051,8 +1070,8 @@ class HipBackend : public Backend {
         int which = 1; int64_t epoch = -1; hipStream_t stream = nullptr;
         int64_t* d_off = nullptr;
     };
-    Request req_[2];   // [ProfileKind]
-    void requests_reset() { for (int k = 0; k < 2; k++) { req_[k] = Request{}; prof_[k].view = nullptr; } }
+    Request req_[kProfileKinds];   // [ProfileKind]
+    void requests_reset() { for (int k = 0; k < kProfileKinds; k++) { req_[k] = Request{}; prof_[k].view = nullptr; } }
 
     // Everything this batch queued is complete when this returns: the caller's stream (only if a run is still in flight -- the
     // stream must outlive its work), the side streams this batch used and the lease's copy and run streams, each synchronised
@@ -1107,6 +1126,8 @@ class HipBackend : public Backend {
                 if (L->h_runs_bytes[k] > kKeepRuns) { (void)hipHostFree(L->h_runs[k]); L->h_runs[k] = nullptr; L->h_runs_bytes[k] = 0; }
             }
             for (RequestBlock& B : L->prof) B.trim(kKeepProfile);
+            if (L->d_frag_img_bytes > kKeepProfile) { (void)hipFree(L->d_frag_img); L->d_frag_img = nullptr; L->d_frag_img_bytes = 0; }
+            if (L->h_frag_bytes > kKeepProfile) { (void)hipHostFree(L->h_frag); L->h_frag = nullptr; L->h_frag_bytes = 0; }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
                 if (*pb.second > kKeepSeq) { (void)hipFree(*pb.first); *pb.first = nullptr; *pb.second = 0; }
             if (L->h_seq_bytes > kKeepSeq) { (void)hipHostFree(L->h_seq); L->h_seq = nullptr; L->h_seq_bytes = 0; }
@@ -1116,7 +1137,7 @@ class HipBackend : public Backend {
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
 
@@ -1182,7 +1203,7 @@ class HipBackend : public Backend {
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
         hbp_ = &hb_in; cfg_ = cfg;
@@ -2135,7 +2156,7 @@ class HipBackend : public Backend {
         out->copied_bytes = words * 4 + (runs_hdr_[slot] ? U * (int64_t)sizeof(UnitOut) : 0);
         return 0;
     }
-    // ---- on-request results: both profiles (ambi_profile.hpp, ambi_junc_profile.hpp) and the sequences below ----
+    // ---- on-request results: the profiles (ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp) and the sequences below ----
     // A request works on `stream` behind everything that writes the result blob in the last run: the caller's stream of that run,
     // which has waited for every side stream at the end of run(), and -- for a caller that asks on another stream -- explicitly the
     // events "results complete" of the side streams (lean / list finish kernels, direct edit + full launch) and of the express
@@ -2149,15 +2170,48 @@ class HipBackend : public Backend {
         if (express_) HIP_CK(hipStreamWaitEvent(s, ev_express_, 0));
         return 0;
     }
-    // The two profiles are instances of one on-request block (Lease::prof, req_, Backend::prof_); a kind has its own layout, its own
-    // kernel with its LDS size, and nothing else.  profile() queues the kind's kernel behind the run, then ONE device-to-host copy of
-    // the block on the lease's copy stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes
+    // The fragment image of the batch (FragImage, ambi_pack.hpp) on the device: nothing of it travels with the batch; it goes up on
+    // the request's stream when the device does not hold this version of it (pinned twin, one copy), as the sequence image does.
+    int64_t frag_img_version_ = -1;
+    FragArgs frag_args_{};
+    int fragment_image(hipStream_t s) {
+        Lease* L = lease_;
+        const FragImage& I = hb().frag;
+        const int64_t U = (int64_t)hb().units.size();
+        if ((int64_t)I.pref_off.size() != U || (int64_t)I.cell_off.size() != U || (int64_t)I.n_frag.size() != U) return ST_ERR_BAD_INPUT;   // (not sealed)
+        const int64_t b0 = pad16(2 * (int64_t)I.cells.size()), b1 = b0 + pad16(4 * (int64_t)I.frag_off.size()), b2 = b1 + 8 * U, b3 = b2 + 8 * U, total = b3 + pad16(4 * U);
+        if (frag_img_version_ != I.version || !L->d_frag_img) {
+            if (!L->ev_frag_up) HIP_CK(hipEventCreateWithFlags(&L->ev_frag_up, hipEventDisableTiming));
+            else HIP_CK(hipEventSynchronize(L->ev_frag_up));   // (an earlier upload still reads the twin)
+            if (int rc = lease_device_block(&L->d_frag_img, &L->d_frag_img_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&L->h_frag, nullptr, &L->h_frag_bytes, total)) return rc;
+            if (!I.cells.empty()) memcpy(L->h_frag, I.cells.data(), 2 * I.cells.size());
+            memcpy(L->h_frag + b0, I.frag_off.data(), 4 * I.frag_off.size());
+            memcpy(L->h_frag + b1, I.cell_off.data(), (size_t)(8 * U));
+            memcpy(L->h_frag + b2, I.pref_off.data(), (size_t)(8 * U));
+            memcpy(L->h_frag + b3, I.n_frag.data(), (size_t)(4 * U));
+            HIP_CK(hipMemcpyAsync(L->d_frag_img, L->h_frag, (size_t)total, hipMemcpyHostToDevice, s));
+            HIP_CK(hipEventRecord(L->ev_frag_up, s));
+            frag_img_version_ = I.version;
+        }
+        frag_args_ = FragArgs{reinterpret_cast<const rcell_t*>(L->d_frag_img), reinterpret_cast<const int32_t*>(L->d_frag_img + b0),
+                              reinterpret_cast<const int64_t*>(L->d_frag_img + b1), reinterpret_cast<const int64_t*>(L->d_frag_img + b2),
+                              reinterpret_cast<const int32_t*>(L->d_frag_img + b3)};
+        return 0;
+    }
+    // The profiles are instances of one on-request block (Lease::prof, req_, Backend::prof_); a kind has its own layout, its own
+    // kernel with its LDS size, and nothing else -- but for the fragment kind's image, which goes up in front of its kernel.
+    // profile() queues the kind's kernel behind the run, then ONE device-to-host copy of the block on the lease's copy stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes
     // the results final (wait(): the first run done again with a larger arena, units finished by the parallel search) and, if that
     // moved the results' epoch after the kernel was queued, queues kernel and copy once more.
     int profile_queue(ProfileKind kind, int which, hipStream_t s) {
         Lease* L = lease_;
         RequestBlock& B = L->prof[kind]; Request& R = req_[kind]; ProfileState& P = prof_[kind];
         const int64_t U = (int64_t)hb().units.size();
+        if (kind == kFragment) {   // (the image can change between requests, and with it the layout)
+            if (frag_img_version_ != hb().frag.version) { if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done)); R.laid_out = false; }
+            if (int rc = fragment_image(s)) return rc;
+        }
         if (!R.laid_out) {
             profile_layout(kind);
             const int64_t total = P.bytes + U * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
@@ -2172,12 +2226,14 @@ class HipBackend : public Backend {
             R.laid_out = true;
         }
         if (int rc = behind_results(s, B.ev_src)) return rc;
-        int window = 0, jwin = 0, slots = 0, swin = 0, lds = kProfileScratchBytes;
-        if (kind == kJunction) { junc_profile_windows(&jwin, &slots, &swin); lds += (int)junc_profile_lds_bytes(slots, swin); }
+        int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes;
+        if (kind == kFragment) { frag_profile_windows(&pwin, &slots); lds += (int)frag_profile_lds_bytes(slots, pwin); }
+        else if (kind == kJunction) { junc_profile_windows(&jwin, &slots, &swin); lds += (int)junc_profile_lds_bytes(slots, swin); }
         else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
         if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
         const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        if (kind == kJunction) hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, B.d, (const int64_t*)R.d_off);
+        if (kind == kFragment) hipLaunchKernelGGL(ambi_frag_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, frag_args_, which, pwin, slots, B.d, (const int64_t*)R.d_off);
+        else if (kind == kJunction) hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, B.d, (const int64_t*)R.d_off);
         else hipLaunchKernelGGL(ambi_path_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, window, B.d, (const int64_t*)R.d_off);
         HIP_CK(hipGetLastError());
         HIP_CK(hipEventRecord(B.ev_packed, s));

@@ -128,6 +128,16 @@ int HostBatch::add_graph_chr(const LhGraph& g, int chr, const SolFile* sol, int 
     if (u >= 0) junc_global[u] = gidx;
     // the chromosome's bases, back to back in local id order (ambi_sequence.hpp), when the graph carries them
     if (u >= 0 && (int)g.seq_off.size() == g.n_seg() + 1) seq.set((size_t)u, n, g.seq_bases.data(), g.seq_off.data() + base);
+    // the chromosome's fragments as local ids (ambi_frag_profile.hpp), in the graph's order, with the way back to the graph's list
+    if (u >= 0 && g.n_frag() > 0) {
+        std::vector<rcell_t> fc; std::vector<int64_t> off(1, 0); std::vector<int32_t> fidx;
+        for (int f = 0; f < g.n_frag() && (int)fidx.size() < kMaxUnitFrags; f++) {
+            if (fragment_chr(g, f) != chr) continue;
+            for (int64_t i = g.frag_off[f]; i < g.frag_off[f + 1]; i++) { const int v = g.frag_cells[(size_t)i]; fc.push_back((rcell_t)(v > 0 ? v - base : v + base)); }
+            off.push_back((int64_t)fc.size()); fidx.push_back(f);
+        }
+        if (!fidx.empty()) frag.set((size_t)u, fc.data(), off.data(), (int)fidx.size(), fidx.data());
+    }
     return u;
 }
 
@@ -147,6 +157,7 @@ int HostBatch::add_unit_from(const HostBatch& src, int u) {
     units.push_back(U);
     junc_global.push_back(src.junc_global[u]);
     seq.copy_unit(units.size() - 1, U.n_seg, src.seq, (size_t)u);
+    frag.copy_unit(units.size() - 1, src.frag, (size_t)u);
     if ((size_t)u < src.inject_unit.size() && !src.inject_unit[u].empty()) { inject_unit.resize(units.size()); inject_unit.back() = src.inject_unit[u]; }
     for (int j = 0; j < S.n_junc; j++) {   // (any_sv as add_unit derives it)
         const Junction& J = src.juncs[S.junc_off + j];

@@ -48,9 +48,56 @@ struct SeqImage {
     }
 };
 
+// Fragment image of a batch (ambi_frag_profile.hpp): the units' .juncs fragments as chains of LOCAL signed ids back to back, per
+// unit the int32 prefix frag_off[0..F] of the fragments' lengths (relative to the unit's first cell) and the map from the unit's
+// fragment index to the graph's.  Host memory, with the life of the sequence image: nothing of it travels with the batch; a backend
+// takes it to the device at the first fragment profile request and again when its version has moved.  A unit nobody gave
+// fragments has F = 0.
+constexpr int kMaxUnitFrags = 65535;
+struct FragImage {
+    std::vector<rcell_t> cells;
+    std::vector<int32_t> frag_off;     // all units' prefixes one after the other
+    std::vector<int64_t> cell_off;     // [U] index of a unit's first cell in cells
+    std::vector<int64_t> pref_off;     // [U] index of a unit's frag_off[0], -1: not set yet
+    std::vector<int32_t> n_frag;       // [U] F
+    std::vector<std::vector<int32_t>> graph_index;   // [U] local fragment index -> index in the graph's list (empty: a raw unit)
+    bool any = false;                  // some unit has fragments
+    int max_f = 0;                     // most fragments of a unit
+    int64_t version = 0;               // moves with every change
+    // the fragments of unit `unit`: fragment f = src[off[f] .. off[f + 1]) (off ascending, every fragment two cells at least, the
+    // whole below 2^31 cells: the callers check); a second call replaces the first
+    void set(size_t unit, const rcell_t* src, const int64_t* off, int n, const int32_t* gidx) {
+        if (pref_off.size() <= unit) { cell_off.resize(unit + 1, 0); pref_off.resize(unit + 1, -1); n_frag.resize(unit + 1, 0); graph_index.resize(unit + 1); }
+        cell_off[unit] = (int64_t)cells.size();
+        pref_off[unit] = (int64_t)frag_off.size();
+        n_frag[unit] = n;
+        for (int f = 0; f <= n; f++) frag_off.push_back((int32_t)(n > 0 ? off[f] - off[0] : 0));
+        if (n > 0) cells.insert(cells.end(), src + off[0], src + off[n]);
+        graph_index[unit].assign(gidx, gidx + (gidx ? n : 0));
+        if (n > 0) any = true;
+        if (n > max_f) max_f = n;
+        version++;
+    }
+    // every unit has a prefix afterwards (F = 0 where nothing was attached); idempotent
+    void seal(const std::vector<UnitIn>& units) {
+        if (pref_off.size() < units.size()) { cell_off.resize(units.size(), 0); pref_off.resize(units.size(), -1); n_frag.resize(units.size(), 0); graph_index.resize(units.size()); }
+        for (size_t u = 0; u < units.size(); u++)
+            if (pref_off[u] < 0) { cell_off[u] = (int64_t)cells.size(); pref_off[u] = (int64_t)frag_off.size(); frag_off.push_back(0); version++; }
+    }
+    // unit u of another image (ambi_batch_run_sharded deals units to shares)
+    void copy_unit(size_t unit, const FragImage& from, size_t u) {
+        if (u >= from.pref_off.size() || from.pref_off[u] < 0) return;
+        const int n = from.n_frag[u];
+        std::vector<int64_t> off((size_t)n + 1);
+        for (int f = 0; f <= n; f++) off[(size_t)f] = from.cell_off[u] + from.frag_off[(size_t)from.pref_off[u] + (size_t)f];
+        set(unit, from.cells.data(), off.data(), n, from.graph_index[u].empty() ? nullptr : from.graph_index[u].data());
+    }
+};
+
 struct HostBatch {
     std::vector<UnitIn> units;
     SeqImage seq;                      // bases of the units' segments (empty unless sequences were attached)
+    FragImage frag;                    // .juncs fragments of the units (empty unless fragments were attached)
     std::vector<double> seg_cn;
     std::vector<Junction> juncs;
     std::vector<JuncEnds> junc_ends;   // junc_ends(juncs[i]) of every record

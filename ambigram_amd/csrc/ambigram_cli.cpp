@@ -255,6 +255,12 @@ int run_sc_bfb(Args& A) {
 // chromosomes, which belongs to no unit: count 0), source chromosome name, source segment id, source strand, target chromosome
 // name, target segment id, target strand, input CN, count in the final path, count - CN -- from the device's junction usage
 // profile of the final paths (ambi_batch_junc_profile); stdout and the side files are unchanged.
+// --frag_profile <file> [--frags <file>] (the check a user with long reads does first: does the printed path contain the fragments that
+// were given as evidence for it?): the lines of the fragment file (--frags; by default the file of --juncdb) are read as signed
+// chains (ambi_graph_read_fragments: the graph stays as it is) and, after the run, one tab-separated row per fragment in file order --
+// sample, chromosome index (-1 for a fragment of fewer than two cells or one that spans chromosomes, which belongs to no unit:
+// 0 0 -1), fragment index, cells, occurrences, occurrences of the reverse complement, first position -- comes from the device's
+// fragment support profile of the final paths (ambi_batch_frag_profile); stdout and the side files are unchanged.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -283,6 +289,9 @@ int run_bfb(Args& A) {
     const double solver_timeout = A.kv.count("solver_timeout") ? atof(A.kv["solver_timeout"].c_str()) : 0;   // extension: seconds, 0 = none
     const std::string cn_profile = A.kv.count("cn_profile") ? A.kv["cn_profile"] : "";
     const std::string junc_profile = A.kv.count("junc_profile") ? A.kv["junc_profile"] : "";
+    const std::string frag_profile = A.kv.count("frag_profile") ? A.kv["frag_profile"] : "";
+    const std::string frags = A.kv.count("frags") ? A.kv["frags"] : juncs;
+    if (!frag_profile.empty() && frags.empty()) { std::cerr << "--frag_profile needs a fragment file: --frags <file> or --juncdb <file>" << std::endl; return 2; }
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
     const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
@@ -331,6 +340,14 @@ int run_bfb(Args& A) {
                 std::cerr << "--junc_profile: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
                 return 2;
             }
+        }
+        if (!frag_profile.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << "--frag_profile: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
+                return 2;
+            }
+            if ((rc = ambi_graph_read_fragments(g, frags.c_str())) != 0) return die("--frags " + frags + ": " + ambi_error_string(rc));
         }
         if (!out_fasta.empty()) {
             ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
@@ -459,6 +476,27 @@ int run_bfb(Args& A) {
                 fprintf(pf, "%s\t%d\t%s\t%d\t%c\t%s\t%d\t%c\t%g\t%d\t%g\n", S.lh.c_str(), chr_of[j], ns, src[j], sdir[j] > 0 ? '+' : '-', nt, tgt[j],
                         tdir[j] > 0 ? '+' : '-', cn[j], count[j], (double)count[j] - cn[j]);
             }
+        }
+        fclose(pf);
+    }
+    if (!frag_profile.empty()) {
+        if ((rc = ambi_batch_frag_profile(b, 1, nullptr)) != 0 || (rc = ambi_batch_frag_profile_wait(b)) != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+        FILE* pf = fopen(frag_profile.c_str(), "w");
+        if (!pf) return die("Cannot open file " + frag_profile);
+        for (Sample& S : samples) {
+            const int nf = ambi_graph_fragments(S.g, nullptr, 0, nullptr, 0, nullptr);
+            std::vector<int64_t> off((size_t)nf + 1, 0);
+            std::vector<int32_t> chr_of((size_t)nf + 1, -1), fwd((size_t)nf, 0), rev((size_t)nf, 0), first((size_t)nf, -1);
+            ambi_graph_fragments(S.g, nullptr, 0, off.data(), nf + 1, chr_of.data());
+            for (int c = 0; c < S.n_chr; c++) {
+                const int fu = ambi_batch_unit_frag_support(b, S.unit[c], nullptr, nullptr, nullptr, nullptr, INT32_MAX);
+                if (fu < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(fu)); }
+                std::vector<int32_t> uf(fu), ur(fu), ui(fu), idx(fu);
+                if ((rc = ambi_batch_unit_frag_support(b, S.unit[c], uf.data(), ur.data(), ui.data(), idx.data(), fu)) < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                for (int f = 0; f < fu; f++) if (idx[f] >= 0 && idx[f] < nf) { fwd[idx[f]] = uf[f]; rev[idx[f]] = ur[f]; first[idx[f]] = ui[f]; }
+            }
+            for (int f = 0; f < nf; f++)
+                fprintf(pf, "%s\t%d\t%d\t%lld\t%d\t%d\t%d\n", S.lh.c_str(), chr_of[f], f, (long long)(off[f + 1] - off[f]), fwd[f], rev[f], first[f]);
         }
         fclose(pf);
     }
@@ -649,13 +687,17 @@ int main(int argc, char** argv) {
     if (A.help) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
-                     "[--junc_profile <file>] [--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
                      "  --junc_profile <file> (--op bfb): one tab-separated row per junction after the run, in file order: sample, chromosome index (-1 between "
                      "chromosomes), source chromosome, source segment id, source strand, target chromosome, target segment id, target strand, input CN, count in "
                      "the final path, count - CN (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --frag_profile <file> (--op bfb): one tab-separated row per fragment (line of the fragment file read as one signed chain) after the run, "
+                     "in file order: sample, chromosome index (-1: no unit), fragment index, cells, occurrences in the final path, occurrences of the reverse "
+                     "complement, first position or -1 (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --frags <file>: the fragment file of --frag_profile (default: the file of --juncdb)\n"
                      "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
                      "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
                      "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";

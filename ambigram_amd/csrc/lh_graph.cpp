@@ -290,6 +290,58 @@ int read_juncs(LhGraph& g, const std::string& path) {   // LGM.cpp:5096-5156
     return LH_OK;
 }
 
+int set_fragments(LhGraph& g, const int32_t* cells, const int64_t* frag_off, int n) {
+    if (g.trx) return LH_ERR_UNSUPPORTED;   // (as read_juncs: the ids of the file are not the rebuilt graph's)
+    if (n < 0 || (n > 0 && (!cells || !frag_off || frag_off[0] != 0))) return LH_ERR_MALFORMED;
+    for (int f = 0; f < n; f++) if (frag_off[f + 1] < frag_off[f]) return LH_ERR_MALFORMED;
+    const int64_t total = n > 0 ? frag_off[n] : 0;
+    for (int64_t i = 0; i < total; i++) {
+        const int64_t id = cells[i] < 0 ? -(int64_t)cells[i] : cells[i];
+        if (id < 1 || id > g.n_seg()) return LH_ERR_UNKNOWN_SEG;
+    }
+    g.frag_cells.assign(cells, cells + total);
+    g.frag_off.assign(1, 0);
+    for (int f = 0; f < n; f++) g.frag_off.push_back(frag_off[f + 1]);
+    return LH_OK;
+}
+
+int read_fragments(LhGraph& g, const std::string& path) {
+    if (g.trx) return LH_ERR_UNSUPPORTED;
+    std::vector<int32_t> cells;
+    std::vector<int64_t> off(1, 0);
+    if (!path.empty()) {
+        std::ifstream f(path);
+        std::string line;
+        while (std::getline(f, line)) {
+            std::istringstream iss(line);
+            std::string w;
+            size_t got = 0;
+            while (iss >> w) {   // the token form of read_juncs: digits and one strand character, '+' or anything else
+                const int id = atoi(w.substr(0, w.size() - 1).c_str());
+                if (id < 1 || id > g.n_seg()) return LH_ERR_UNKNOWN_SEG;
+                cells.push_back(w.back() == '+' ? id : -id);
+                got++;
+            }
+            if (got) off.push_back((int64_t)cells.size());
+        }
+    }
+    return set_fragments(g, cells.data(), off.data(), (int)off.size() - 1);
+}
+
+int fragment_chr(const LhGraph& g, int f) {
+    if (f < 0 || f >= g.n_frag() || g.frag_off[f + 1] - g.frag_off[f] < 2) return -1;
+    const int first = std::abs(g.frag_cells[(size_t)g.frag_off[f]]);
+    for (int c = 0; c < g.n_chr(); c++) {
+        if (first < g.source_ids[c] || first > g.sink_ids[c]) continue;
+        for (int64_t i = g.frag_off[f]; i < g.frag_off[f + 1]; i++) {
+            const int id = std::abs(g.frag_cells[(size_t)i]);
+            if (id < g.source_ids[c] || id > g.sink_ids[c]) return -1;
+        }
+        return c;
+    }
+    return -1;
+}
+
 // Graph::writeGraph (Graph.cpp:239-266): the graph as it stands (after the copy-number maths and any .juncs additions) back
 // into .lh text.  The reference writes a fixed sample name ("TEST"), only these header keys, every segment with its
 // lower-bound flag ('B': a freshly read segment always has it, Segment.cpp:16) and numbers through operator<< of a default

@@ -48,6 +48,11 @@ struct LhGraph {
     // bases of the segments (set_sequences / read_fasta; empty: none): segment id i + 1 = seq_bases[seq_off[i] .. seq_off[i + 1])
     std::vector<uint8_t> seq_bases;
     std::vector<int64_t> seq_off;
+    // .juncs fragments (read_fragments / set_fragments; empty: none): fragment f = frag_cells[frag_off[f] .. frag_off[f + 1]), signed
+    // segment ids of the file in the order of the line.  Evidence to check paths against (ambi_frag_profile.hpp), never input of a stage.
+    std::vector<int32_t> frag_cells;
+    std::vector<int64_t> frag_off;
+    int n_frag() const { return frag_off.empty() ? 0 : (int)frag_off.size() - 1; }
 
     int n_seg() const { return (int)seg_id.size(); }
     int n_junc() const { return (int)j_src.size(); }
@@ -96,6 +101,15 @@ void set_partitions(LhGraph& g);                                   // localhap.c
 int read_fasta(LhGraph& g, const std::string& path);
 // the same store from memory: segment id i + 1 = bases[seg_off[i] .. seg_off[i + 1]), any byte values; false: offsets not ascending from 0
 bool set_sequences(LhGraph& g, const uint8_t* bases, const int64_t* seg_off);
+// Every non-empty line of a .juncs file as ONE signed chain of segment ids, in the token form and with the codes of read_juncs
+// (a file that cannot be read holds no line; an id outside the graph, which is also what a malformed token gives:
+// LH_ERR_UNKNOWN_SEG; a graph rebuilt for PROP I1 / C1: LH_ERR_UNSUPPORTED).  Unlike read_juncs it leaves the graph as it is: no
+// junction, no component, no line of the log.  A second call replaces the first; on an error the graph keeps what it had.
+int read_fragments(LhGraph& g, const std::string& path);
+// the same from memory: fragment f = cells[frag_off[f] .. frag_off[f + 1]) (offsets ascending from 0)
+int set_fragments(LhGraph& g, const int32_t* cells, const int64_t* frag_off, int n);
+// the chromosome whose [source, sink] id range holds every segment of fragment f; -1: fewer than two cells, or none does
+int fragment_chr(const LhGraph& g, int f);
 
 // ---- TRX-BFB, PROP I1 / C1 (localhap.cpp:79-88, :263): a translocation that happened BEFORE the BFB cycles -----------------------
 // insertBeforeBFB / concatBeforeBFB (LGM.cpp:4195-4395) rebuild the graph -- the inserted segments spliced into the main

@@ -146,6 +146,22 @@ int ambi_graph_components(const ambi_graph_t* g, int32_t* ids, int32_t ids_cap, 
 int ambi_graph_set_sequences(ambi_graph_t* g, const uint8_t* bases, const int64_t* seg_off);
 int ambi_graph_read_fasta(ambi_graph_t* g, const char* fasta_path);
 int64_t ambi_graph_sequences(const ambi_graph_t* g, uint8_t* bases, int64_t cap, int64_t* seg_off);
+/* Fragments: every non-empty line of a .juncs file as ONE signed chain of segment ids, kept in the order of the line -- the
+ * evidence a path is checked against (ambi_batch_frag_profile).  The reference's README calls these lines "possible fragments on
+ * BFB paths"; readComponents (LocalGenomicMap.cpp:5096-5156) throws the order away before the ILP sees it.
+ * ambi_graph_read_fragments: the token form and the return codes of ambi_graph_read_juncs (a file that cannot be read holds no line;
+ *   an id outside the graph, which is also what a malformed token gives: AMBI_ERR_UNKNOWN_SEG).  It does NOT change the graph: no
+ *   junction, no component, no line of the log.  A second call replaces the fragments of the first.
+ * ambi_graph_set_fragments: the same from memory: fragment f = cells[frag_off[f] .. frag_off[f + 1]), frag_off[0 .. n] ascending from
+ *   0, cells = signed segment ids of the file.  AMBI_ERR_MALFORMED for offsets that do not ascend from 0.
+ * Both return AMBI_ERR_UNSUPPORTED on a graph rebuilt for PROP I1 / C1, as ambi_graph_read_juncs does.
+ * ambi_graph_fragments: the fragments back (at most cap cells, off_cap offsets: n + 1 are needed) and, in unit_chr (n entries when
+ *   off_cap > n), the chromosome every fragment belongs to: the one whose [source, sink] id range holds all of its segments, -1
+ *   for a fragment of fewer than two cells or one that spans chromosomes (it keeps its index and belongs to no unit).  Returns n.
+ * Attach them before the graph's chromosomes are added to a batch: ambi_batch_add_chromosome* copies a unit's fragments. */
+int ambi_graph_read_fragments(ambi_graph_t* g, const char* juncs_path);
+int ambi_graph_set_fragments(ambi_graph_t* g, const int32_t* cells, const int64_t* frag_off, int32_t n);
+int32_t ambi_graph_fragments(const ambi_graph_t* g, int32_t* cells, int64_t cap, int64_t* frag_off, int32_t off_cap, int32_t* unit_chr);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch of units.  A unit = one chromosome of one sample = one iteration of the loop localhap.cpp:111-265:
@@ -361,6 +377,48 @@ int ambi_batch_unit_junc_usage(const ambi_batch_t* b, int32_t unit, int32_t* cou
  * trip): [ambi_unit_junc_profile_t[n_units]] padded to 16 bytes, then per unit count int32[m] padded to 16 bytes.  Valid after
  * ambi_batch_junc_profile_wait until the next ambi_batch_junc_profile; not available for a sharded batch. */
 int ambi_batch_junc_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+
+/* The fragment support profile of every unit's path, computed ON THE DEVICE (ambi_frag_profile_kernel): how often the path contains
+ * every fragment of the unit's .juncs evidence (ambi_graph_read_fragments; README of the reference: "possible fragments on BFB
+ * paths"), in either direction, and where first.  With the path cells c[0..P) that ambi_batch_unit_path(unit, which) returns (as
+ * local ids) and the unit's fragments f = 0..F-1 in the graph's order:
+ *   a fragment (f_0 .. f_{L-1}), L >= 2, occurs at i when c[i + k] == f_k for all k, 0 <= i <= P - L; occurrences may overlap;
+ *   fwd[f] = occurrences of f, rev[f] = occurrences of its reverse complement (-f_{L-1} .. -f_0), 0 when that equals f (a
+ *   palindrome such as 3+ 3- is counted once), first[f] = the smallest i over both directions, -1 when there is none.
+ * All fields are exact integers.  Per unit 3 F int32 travel to the host instead of the path's cells.  The fragments go to the
+ * device with the first request (and again after they changed), never with ambi_batch_upload. */
+typedef struct {
+    int32_t status;             /* the unit's status (ambi_unit_result_t::status) */
+    int32_t cells;              /* P; a unit with a negative status or without a path has every field but status and frags zero */
+    int32_t frags;              /* F */
+    int32_t frags_supported;    /* fragments with fwd + rev > 0 */
+    int32_t first_unsupported;  /* lowest fragment index without an occurrence, -1 if none */
+    int32_t max_count;          /* max over the fragments of fwd + rev */
+    int32_t longest_supported;  /* cells of the longest supported fragment, 0 if none */
+    int32_t reserved;
+    int64_t occurrences;        /* sum over the fragments of fwd + rev */
+} ambi_unit_frag_profile_t;
+/* The fragments of a raw unit (ambi_batch_add_unit): fragment f = cells[frag_off[f] .. frag_off[f + 1]), LOCAL signed ids, frag_off
+ * ascending from 0; a second call replaces the first.  AMBI_ERR_ARG for a fragment of fewer than two cells, an id outside
+ * 1..n_seg, more than 65535 fragments or 2^31 cells and more; AMBI_ERR_STATE after ambi_batch_run_sharded (the shares hold copies). */
+int ambi_batch_set_unit_fragments(ambi_batch_t* b, int32_t unit, const int32_t* cells, const int64_t* frag_off, int32_t n);
+/* Queues the fragment profile of the LAST run's results behind that run on hip_stream (which as for ambi_batch_profile), then one
+ * device-to-host copy of the block on the engine's copy stream: hip_stream is not blocked.  A batch without any fragment is
+ * served: every unit gets frags = 0.  AMBI_ERR_STATE before any run, AMBI_ERR_ARG for another `which`.  After
+ * ambi_batch_run_sharded the call goes to every share, on the share's own stream. */
+int ambi_batch_frag_profile(ambi_batch_t* b, int32_t which, void* hip_stream);
+/* Blocks until the fragment profile is in host memory.  Makes the run's results final first (ambi_batch_wait) and profiles once
+ * more if that changed them after the request was queued. */
+int ambi_batch_frag_profile_wait(ambi_batch_t* b);
+/* A unit's summary; AMBI_ERR_STATE without a waited-for fragment profile of the last run. */
+int ambi_batch_unit_frag_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_frag_profile_t* out);
+/* A unit's values per fragment: fwd, rev and first as above, graph_index[f] = the fragment's index in the graph's list
+ * (ambi_graph_fragments; f itself for a raw unit).  Any pointer may be NULL.  Returns F; AMBI_ERR_ARG when cap < F. */
+int ambi_batch_unit_frag_support(const ambi_batch_t* b, int32_t unit, int32_t* fwd, int32_t* rev, int32_t* first, int32_t* graph_index, int32_t cap);
+/* The fragment profile block in DEVICE memory, for collectives: [ambi_unit_frag_profile_t[n_units]] padded to 16 bytes, then per
+ * unit fwd int32[F], rev int32[F] and first int32[F], each array padded to 16 bytes.  Valid after ambi_batch_frag_profile_wait until
+ * the next ambi_batch_frag_profile; not available for a sharded batch. */
+int ambi_batch_frag_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
 
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
