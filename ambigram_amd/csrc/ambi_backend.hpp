@@ -255,23 +255,17 @@ class Backend {
         if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
         else P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
     }
-    // patterns per window and table slots of the bound batch (AMBI_FPROFILE_FRAG_WINDOW can only shrink the window)
-    void frag_profile_windows(int* pwin, int* slots) const {
-        const char* e = ambi_env("AMBI_FPROFILE_FRAG_WINDOW");
-        *pwin = frag_window(prof_hb_->frag.max_f, e ? atoi(e) : 0);
+    // The windows of the bound batch; the environment variables (tests) can only shrink them (capped_window).
+    static int env_int(const char* name) { const char* e = ambi_env(name); return e ? atoi(e) : 0; }   // 0 when unset
+    void frag_profile_windows(int* pwin, int* slots) const {   // patterns per window and table slots
+        *pwin = frag_window(prof_hb_->frag.max_f, env_int("AMBI_FPROFILE_FRAG_WINDOW"));
         *slots = frag_slots(*pwin);
     }
-    int profile_window_of() const {      // segments per window of the bound batch (AMBI_PROFILE_WINDOW can only shrink it)
-        const char* e = ambi_env("AMBI_PROFILE_WINDOW");
-        return profile_window(prof_hb_->max_n, e ? atoi(e) : 0);
-    }
-    // junctions per pass, table slots and segments per window of the bound batch (AMBI_JPROFILE_* can only shrink the windows)
-    void junc_profile_windows(int* jwin, int* slots, int* swin) const {
-        const char* ej = ambi_env("AMBI_JPROFILE_JUNC_WINDOW");
-        const char* es = ambi_env("AMBI_JPROFILE_SEG_WINDOW");
-        *jwin = junc_window(prof_hb_->max_m, ej ? atoi(ej) : 0);
+    int profile_window_of() const { return profile_window(prof_hb_->max_n, env_int("AMBI_PROFILE_WINDOW")); }   // segments per window
+    void junc_profile_windows(int* jwin, int* slots, int* swin) const {   // junctions per pass, table slots and segments per window
+        *jwin = junc_window(prof_hb_->max_m, env_int("AMBI_JPROFILE_JUNC_WINDOW"));
         *slots = junc_slots(*jwin);
-        *swin = junc_seg_window(prof_hb_->max_n, es ? atoi(es) : 0);
+        *swin = junc_seg_window(prof_hb_->max_n, env_int("AMBI_JPROFILE_SEG_WINDOW"));
     }
     int sequence_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
         const int U = (int)prof_hb_->units.size();

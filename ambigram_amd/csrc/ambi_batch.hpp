@@ -233,4 +233,21 @@ constexpr int kStageSlots = 32;
 
 AMBI_HD UnitOut* unit_out(uint8_t* results, int u) { return reinterpret_cast<UnitOut*>(results) + u; }
 
+// The path of unit u as every reader of the result blob selects it (which = 0: getBFB's; 1: after indelBFB, which is `path` when
+// path_ind_stored == 0): its cells, its length AS STORED, the unit's status and its capacity.  What a negative status or a length
+// above the capacity means is the caller's rule.  (The fields are read in this order on purpose: built as one aggregate with the
+// pointer first, the same function cost ambi_seq_extents_kernel 12 SGPRs and a wave per SIMD; profiles/r21_notes.md.)
+struct UnitPath { const rcell_t* cells; int len, status, path_cap; };
+AMBI_HD UnitPath unit_path(const UnitIn* units, const uint8_t* results, int u, int which) {
+    const UnitIn& U = units[u];
+    const UnitOut* h = reinterpret_cast<const UnitOut*>(results) + u;
+    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
+    UnitPath Q;
+    Q.len = which ? h->path_indel_len : h->path_len;
+    Q.status = h->status;
+    Q.path_cap = U.path_cap;
+    Q.cells = reinterpret_cast<const rcell_t*>(results + U.res_off + ((which && h->path_ind_stored) ? L.path_ind : L.path));   // else the edited path equals `path`
+    return Q;
+}
+
 }  // namespace ambi

@@ -23,6 +23,10 @@
 //                                                  (ambi_junc_profile.hpp)                         <- the same cells + a hash table in LDS
 //   ambi_frag_profile_kernel      1 block / unit   on request: occurrences of every .juncs fragment in the path, both directions,
 //                                                  + summary (ambi_frag_profile.hpp)               <- the same cells + chained patterns in LDS
+//                                                  (the three profile kernels share unit prologue, chunked cell read and window rule --
+//                                                  profile_path, path_load_chunk, capped_window of ambi_profile.hpp -- and the two tables
+//                                                  their probe, lds_find / lds_claim of ambi_junc_profile.hpp; every reader of a unit's
+//                                                  path in the result blob selects it with unit_path of ambi_batch.hpp)
 // Every kernel but the two plan kernels is a wrapper around the stage functions of ambi_stages.hpp (ambi_exchange.hpp,
 // ambi_profile.hpp for the pack / expand and profile kernels), which the host simulation runs as well, the four table kernels
 // (blocks_build, enumerate_blocks, enumerate, enumerate_wide; their logic is under stage_enumerate's banner) included.  The
@@ -586,7 +590,7 @@ __global__ __launch_bounds__(256) void ambi_pack_runs_write_kernel(BatchArgs A, 
     BlockGroup g(scratch);
     pack_runs_write_unit(g, A, (int)blockIdx.x, which, run_off, run_start, run_len, cap);
 }
-// ---- copy-number profile of the paths (ambi_profile.hpp; launched by HipBackend::profile only) ----
+// ---- copy-number profile of the paths (ambi_profile.hpp; launched by HipBackend::profile_queue only) ----
 // One workgroup of 256 threads per unit, grid-stride over the units.  Group memory: 256 bytes for the group's reductions, then
 // the two difference arrays of `window` segments.
 constexpr int kProfileThreads = 256, kProfileScratchBytes = 256;
@@ -598,7 +602,7 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_path_profile_kernel(Batc
         __syncthreads();
     }
 }
-// ---- junction usage profile of the paths (ambi_junc_profile.hpp; launched by HipBackend::junc_profile only) ----
+// ---- junction usage profile of the paths (ambi_junc_profile.hpp; launched by HipBackend::profile_queue only) ----
 // One workgroup of 256 threads per unit, grid-stride over the units.  Group memory: 256 bytes for the group's reductions, then
 // the hash table of `slots` slots (key, lowest index, count: 12 bytes each) and the difference array of `swin` segments.
 __global__ __launch_bounds__(kProfileThreads) void ambi_junc_profile_kernel(BatchArgs A, int which, int jwin, int slots, int swin, uint8_t* block, const int64_t* off) {

@@ -18,16 +18,7 @@
 
 namespace ambi {
 
-// the path the exchange carries (which = 0: getBFB's; 1: after indelBFB, which is `path` when path_ind_stored == 0)
-AMBI_HD const rcell_t* unit_final_path(const BatchArgs& A, int u, int which, int* len) {
-    const UnitIn& U = A.units[u];
-    const UnitOut* h = unit_out(A.results, u);
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    const bool stored = which && h->path_ind_stored;   // else the edited path equals `path`
-    *len = which ? h->path_indel_len : h->path_len;
-    return reinterpret_cast<const rcell_t*>(A.results + U.res_off + (stored ? L.path_ind : L.path));
-}
-
+// The path the exchange carries is unit_path (ambi_batch.hpp), its length as stored.
 // lengths[u] and pack_off[0 .. n_units] (prefix sum of the lengths), *total = all cells.  One group for the whole batch.
 template <class G>
 AMBI_HD void pack_scan(const G& g, const BatchArgs& A, int which, int32_t* lengths, int64_t* pack_off, int64_t* total) {
@@ -50,20 +41,19 @@ AMBI_HD void pack_scan(const G& g, const BatchArgs& A, int which, int32_t* lengt
 // the cells of unit u to cells[pack_off[u] ..), those below `cap` only.  One group per unit.
 template <class G>
 AMBI_HD void pack_copy_unit(const G& g, const BatchArgs& A, int u, int which, const int64_t* pack_off, int32_t* cells, int64_t cap) {
-    const UnitIn& U = A.units[u];
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    const bool stored = which && unit_out(A.results, u)->path_ind_stored;   // else the edited path equals `path`
-    const rcell_t* src = reinterpret_cast<const rcell_t*>(A.results + U.res_off + (stored ? L.path_ind : L.path));
+    const rcell_t* src = unit_path(A.units, A.results, u, which).cells;
+    const int seg_base = A.units[u].seg_base;
     const int64_t off = pack_off[u], len = pack_off[u + 1] - off;
     for (int64_t i = g.tid(); i < len; i += g.size())
-        if (off + i < cap) cells[off + i] = abs_cell(src[i], U.seg_base);
+        if (off + i < cap) cells[off + i] = abs_cell(src[i], seg_base);
 }
 
 // ---- run-length form: two passes over the path in the result blob, one group per unit each ----
 template <class G>
 AMBI_HD void pack_runs_count_unit(const G& g, const BatchArgs& A, int u, int which, int32_t* lengths, int32_t* run_counts) {
-    int P;
-    const rcell_t* src = unit_final_path(A, u, which, &P);
+    const UnitPath Q = unit_path(A.units, A.results, u, which);
+    const rcell_t* src = Q.cells;
+    const int P = Q.len;
     int mine = 0;
     for (int i = g.tid(); i < P; i += g.size()) mine += (i == 0 || src[i] != src[i - 1] + 1) ? 1 : 0;
     const int total = g.sum_i32(mine);
@@ -87,8 +77,9 @@ AMBI_HD void pack_runs_scan(const G& g, const BatchArgs& A, const int32_t* lengt
 template <class G>
 AMBI_HD void pack_runs_write_unit(const G& g, const BatchArgs& A, int u, int which, const int64_t* run_off, int32_t* run_start, int32_t* run_len,
                                   int64_t cap) {
-    int P;
-    const rcell_t* src = unit_final_path(A, u, which, &P);
+    const UnitPath Q = unit_path(A.units, A.results, u, which);
+    const rcell_t* src = Q.cells;
+    const int P = Q.len;
     const int64_t off = run_off[u];
     const int n = (int)(run_off[u + 1] - off);
     if (off + n > cap) return;   // the caller's buffers are too small: nothing is written for this unit (totals tell)

@@ -65,11 +65,7 @@ struct FragArgs {
 // raising the function's ceiling.  AMBI_FPROFILE_FRAG_WINDOW (tests) can only shrink it.
 constexpr int kFragWindowCap = 2048, kFragMinSlots = 8;
 constexpr int kFragCompare = 8;   // cells of a candidate compared per round
-AMBI_HD int frag_window(int max_f, int asked) {
-    int w = max_f < 1 ? 1 : (max_f > kFragWindowCap / 2 ? kFragWindowCap : 2 * max_f);
-    if (asked > 0 && asked < w) w = asked;
-    return w;
-}
+AMBI_HD int frag_window(int max_f, int asked) { return capped_window(max_f > kFragWindowCap / 2 ? kFragWindowCap : 2 * max_f, kFragWindowCap, asked); }
 AMBI_HD int frag_slots(int pwin) {   // load factor <= 1/2
     int t = kFragMinSlots;
     while (t < 2 * pwin) t <<= 1;
@@ -106,34 +102,18 @@ AMBI_HD FragTable frag_table(void* lds, int slots, int pwin) {
     T.slots = slots; T.pwin = pwin;
     return T;
 }
-// slot of a key or -1; at most `slots` probes
-AMBI_HD int frag_find(const FragTable& T, uint32_t key) {
-    const int mask = T.slots - 1;
-    int s = (int)(junc_mix(key) & (uint32_t)mask);
-    for (int k = 0; k < T.slots; k++, s = (s + 1) & mask) {
-        const uint32_t have = T.key[s];
-        if (have == key) return s;
-        if (have == 0) return -1;
-    }
-    return -1;
-}
-// pattern j of the window in front of the chain of its first step; false: the table is full of other keys (never: <= pwin keys)
+// pattern j of the window in front of the chain of its first step (lds_claim, ambi_junc_profile.hpp); false: the table is full of
+// other keys (never: <= pwin keys)
 AMBI_HD bool frag_insert(const FragTable& T, uint32_t key, int j) {
-    const int mask = T.slots - 1;
-    int s = (int)(junc_mix(key) & (uint32_t)mask);
-    for (int k = 0; k < T.slots; k++, s = (s + 1) & mask) {
-        const uint32_t have = (uint32_t)atomic_cas_i32(reinterpret_cast<int*>(T.key + s), 0, (int)key);
-        if (have != 0 && have != key) continue;
-        int old = T.head[s];
-        for (;;) {   // (nobody walks a chain before the barrier behind the insertions)
-            T.next[j] = old;
-            const int got = atomic_cas_i32(T.head + s, old, j);
-            if (got == old) break;
-            old = got;
-        }
-        return true;
+    const int s = lds_claim(T.key, T.slots, key);
+    if (s < 0) return false;
+    int old = T.head[s];
+    for (;;) {   // (nobody walks a chain before the barrier behind the insertions)
+        T.next[j] = old;
+        const int got = atomic_cas_i32(T.head + s, old, j);
+        if (got == old) return true;
+        old = got;
     }
-    return false;
 }
 
 // cell k of pattern (f, dir): fc = the unit's fragment cells, [a, b) = the fragment's cells
@@ -175,13 +155,13 @@ AMBI_HD void stage_frag_profile(const G& g, const rcell_t* cells, int P, const r
                 const int s = base + tid * kProfileChunk;
                 if (s >= P) continue;
                 rcell_t c[kProfileChunk];
-                const int e = junc_load_cells(cells, P, vec, s, c);
-                int prev = s > 0 ? (int)cells[s - 1] : 0;   // the steps (i - 1, i) of the chunk need the cell in front of it
+                int prev;
+                const int e = path_load_chunk(cells, P, vec, s, c, prev);
                 for (int k = 0; k < e; k++) {
                     const int cur = c[k];
                     if (s + k > 0) {
                         const int i = s + k - 1;            // the step (c[i], c[i + 1])
-                        const int slot = frag_find(T, junc_key(prev, cur));
+                        const int slot = lds_find(T.key, T.slots, junc_key(prev, cur));
                         for (int j = slot >= 0 ? T.head[slot] : -1; j >= 0; j = T.next[j]) {
                             const int p = w0 + j, dir = p & 1;
                             const int a = foff[p >> 1], b = foff[(p >> 1) + 1], L = b - a;
@@ -233,33 +213,26 @@ AMBI_HD void stage_frag_profile(const G& g, const rcell_t* cells, int P, const r
     }
 }
 
-// One unit of a batch: reads UnitIn and UnitOut, profiles the path ambi_batch_unit_path(unit, which) returns against the unit's
-// fragments into the fragment profile block.  SHORTCUT and INFEASIBLE units like any other; a unit with a negative status or
-// without a path gets zero counts, first = -1 and a summary that is zero but for the status and the number of fragments.
-// Whole group.
+// One unit of a batch: profiles the path ambi_batch_unit_path(unit, which) returns (profile_path) against the unit's fragments into
+// the fragment profile block.  SHORTCUT and INFEASIBLE units like any other; a unit with a negative status or without a path
+// gets zero counts, first = -1 and a summary that is zero but for the status and the number of fragments.  Whole group.
 template <class G>
 AMBI_HD void frag_profile_unit(const G& g, const UnitIn* units, const FragArgs& I, const uint8_t* results, int u, int which, const FragTable& T,
                                uint8_t* block, const int64_t* off) {
-    const UnitIn& U = units[u];
-    const UnitOut* h = reinterpret_cast<const UnitOut*>(results) + u;
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    const uint8_t* r = results + U.res_off;
     const int F = I.n_frag[u];
-    int P = which ? h->path_indel_len : h->path_len;
-    if (P > U.path_cap) P = 0;   // (never: the finish stages refuse such a path)
+    const ProfilePath Q = profile_path(units, results, u, which);
     const int64_t arr = frag_profile_arr_bytes(F);
     int32_t* fwd = reinterpret_cast<int32_t*>(block + off[u]);
     int32_t* rev = reinterpret_cast<int32_t*>(block + off[u] + arr);
     int32_t* first = reinterpret_cast<int32_t*>(block + off[u] + 2 * arr);
     UnitFragProfile* out = reinterpret_cast<UnitFragProfile*>(block) + u;
-    if (h->status < 0 || P <= 0) {
+    if (Q.P == 0) {
         for (int f = g.tid(); f < F; f += g.size()) { fwd[f] = 0; rev[f] = 0; first[f] = -1; }
-        if (g.tid() == 0) { UnitFragProfile z{}; z.status = h->status; z.frags = F; *out = z; }
+        if (g.tid() == 0) { UnitFragProfile z{}; z.status = Q.status; z.frags = F; *out = z; }
         return;
     }
-    const rcell_t* cells = reinterpret_cast<const rcell_t*>(r + ((which && h->path_ind_stored) ? L.path_ind : L.path));
-    stage_frag_profile(g, cells, P, I.cells + I.cell_off[u], I.frag_off + I.pref_off[u], F, T, fwd, rev, first, out);
-    if (g.tid() == 0) out->status = h->status;
+    stage_frag_profile(g, Q.cells, Q.P, I.cells + I.cell_off[u], I.frag_off + I.pref_off[u], F, T, fwd, rev, first, out);
+    if (g.tid() == 0) out->status = Q.status;
 }
 
 }  // namespace ambi

@@ -35,7 +35,7 @@
 // the unit again; with the key hash a bijection this ends.  No unit is refused.
 //
 // Only group-memory atomics are used (compare-and-swap + min at insertion, add at a hit), no atomic on device memory.
-// SPMD over the group policies of ambi_group.hpp: BlockGroup in ambi_junc_profile_kernel, HostGroup in Backend::junc_profile's
+// SPMD over the group policies of ambi_group.hpp: BlockGroup in ambi_junc_profile_kernel, HostGroup in Backend::profile's
 // default (the host simulation) and in tests/tools/junc_profile_stage_check.cpp.
 #pragma once
 #include <vector>
@@ -66,18 +66,8 @@ static_assert(sizeof(UnitJuncProfile) == 40, "UnitJuncProfile is ambi_unit_junc_
 // the 64 KB a launch gets without raising the function's ceiling); AMBI_JPROFILE_JUNC_WINDOW and AMBI_JPROFILE_SEG_WINDOW (tests)
 // can only shrink them.
 constexpr int kJuncWindowCap = 2048, kJuncSegWindowCap = 2048, kJuncMinSlots = 8;
-AMBI_HD int junc_window(int max_m, int asked) {
-    int w = max_m < 1 ? 1 : max_m;
-    if (w > kJuncWindowCap) w = kJuncWindowCap;
-    if (asked > 0 && asked < w) w = asked;
-    return w;
-}
-AMBI_HD int junc_seg_window(int max_n, int asked) {
-    int w = max_n < 1 ? 1 : max_n;
-    if (w > kJuncSegWindowCap) w = kJuncSegWindowCap;
-    if (asked > 0 && asked < w) w = asked;
-    return w;
-}
+AMBI_HD int junc_window(int max_m, int asked) { return capped_window(max_m, kJuncWindowCap, asked); }
+AMBI_HD int junc_seg_window(int max_n, int asked) { return capped_window(max_n, kJuncSegWindowCap, asked); }
 AMBI_HD int junc_slots(int jwin) {   // load factor <= 1/2
     int t = kJuncMinSlots;
     while (t < 2 * jwin) t <<= 1;
@@ -125,26 +115,33 @@ AMBI_HD uint32_t junc_mix(uint32_t h) {
 AMBI_HD bool junc_in_part(uint32_t canon, int nparts, int part) {
     return nparts == 1 || (int)(junc_mix(canon ^ 0x9e3779b9u) % (uint32_t)nparts) == part;
 }
-// slot of a key or -1; at most `slots` probes (a full table ends the walk as an empty slot does)
-AMBI_HD int junc_find(const JuncTable& T, uint32_t canon) {
-    const int mask = T.slots - 1;
-    int s = (int)(junc_mix(canon) & (uint32_t)mask);
-    for (int k = 0; k < T.slots; k++, s = (s + 1) & mask) {
-        const uint32_t have = T.key[s];
-        if (have == canon) return s;
+// An open-addressing table in group memory: key[slots] (a power of two), 0 = empty, linear probing from junc_mix(k), at most
+// `slots` probes (a full table ends the walk as an empty slot does).  lds_find: the slot of key k or -1.  lds_claim: the slot
+// that holds k from now on (compare-and-swap of 0 to k), or -1 when the table is full of other keys.
+AMBI_HD int lds_find(const uint32_t* key, int slots, uint32_t k) {
+    const int mask = slots - 1;
+    int s = (int)(junc_mix(k) & (uint32_t)mask);
+    for (int i = 0; i < slots; i++, s = (s + 1) & mask) {
+        const uint32_t have = key[s];
+        if (have == k) return s;
         if (have == 0) return -1;
     }
     return -1;
 }
-// false: the table is full of other keys
-AMBI_HD bool junc_insert(const JuncTable& T, uint32_t canon, int j) {
-    const int mask = T.slots - 1;
-    int s = (int)(junc_mix(canon) & (uint32_t)mask);
-    for (int k = 0; k < T.slots; k++, s = (s + 1) & mask) {
-        const uint32_t have = (uint32_t)atomic_cas_i32(reinterpret_cast<int*>(T.key + s), 0, (int)canon);
-        if (have == 0 || have == canon) { atomic_min_i32(T.val + s, j); return true; }
+AMBI_HD int lds_claim(uint32_t* key, int slots, uint32_t k) {
+    const int mask = slots - 1;
+    int s = (int)(junc_mix(k) & (uint32_t)mask);
+    for (int i = 0; i < slots; i++, s = (s + 1) & mask) {
+        const uint32_t have = (uint32_t)atomic_cas_i32(reinterpret_cast<int*>(key + s), 0, (int)k);
+        if (have == 0 || have == k) return s;
     }
-    return false;
+    return -1;
+}
+// junction j into its class: the lowest index stays; false: the table is full of other keys
+AMBI_HD bool junc_insert(const JuncTable& T, uint32_t canon, int j) {
+    const int s = lds_claim(T.key, T.slots, canon);
+    if (s >= 0) atomic_min_i32(T.val + s, j);
+    return s >= 0;
 }
 
 // one event of a run boundary into the window [w0, w0 + wn) of the difference array: a run over the segments a..b crosses the
@@ -154,17 +151,6 @@ AMBI_HD void junc_post(int32_t* d, int w0, int wn, int c, bool begin) {
     const int j = (c > 0 ? c : -c) - w0;
     if (j < 0 || j >= wn) return;
     atomic_add_i32(d + j, (c > 0) == begin ? 1 : -1);
-}
-
-// the chunk [s, s + kProfileChunk) of a thread, read as the profile stage reads it; returns the cells of the chunk inside the path
-AMBI_HD int junc_load_cells(const rcell_t* cells, int P, bool vec, int s, rcell_t (&c)[kProfileChunk]) {
-    for (int q = 0; q < kProfileChunk / 4; q++) {
-        const int at = s + 4 * q;
-        if (at >= P) { for (int k = 0; k < 4; k++) c[4 * q + k] = 0; continue; }
-        if (vec) { const ProfileCell4 w = *reinterpret_cast<const ProfileCell4*>(cells + at); for (int k = 0; k < 4; k++) c[4 * q + k] = w.v[k]; }
-        else for (int k = 0; k < 4; k++) c[4 * q + k] = at + k < P ? cells[at + k] : (rcell_t)0;
-    }
-    return s + kProfileChunk < P ? kProfileChunk : P - s;
 }
 
 // cells: the unit's path (local signed ids), P > 0 cells, readable up to the next multiple of four cells; ends / cn: the unit's m
@@ -204,8 +190,8 @@ AMBI_HD void stage_junc_profile(const G& g, const rcell_t* cells, int P, int n, 
                     const int s = base + tid * kProfileChunk;
                     if (s >= P) continue;
                     rcell_t c[kProfileChunk];
-                    const int e = junc_load_cells(cells, P, vec, s, c);
-                    int prev = s > 0 ? (int)cells[s - 1] : 0;   // the boundaries (i - 1, i) of the chunk need the cell in front of it
+                    int prev;
+                    const int e = path_load_chunk(cells, P, vec, s, c, prev);
                     for (int k = 0; k < e; k++) {
                         const int cur = c[k];
                         if (s + k == 0) junc_post(T.diff, w0, wn, cur, true);
@@ -214,7 +200,7 @@ AMBI_HD void stage_junc_profile(const G& g, const rcell_t* cells, int P, int n, 
                             junc_post(T.diff, w0, wn, cur, true);
                             const uint32_t canon = junc_canon(prev, cur);
                             if (boundary && junc_in_part(canon, nparts, part)) {
-                                const int slot = junc_find(T, canon);
+                                const int slot = lds_find(T.key, T.slots, canon);
                                 if (slot >= 0) { atomic_add_i32(T.cnt + slot, 1); matched++; }
                                 else { unmatched++; if (s + k - 1 < first) first = s + k - 1; }
                             }
@@ -237,7 +223,7 @@ AMBI_HD void stage_junc_profile(const G& g, const rcell_t* cells, int P, int n, 
                         if (x > 0 && seg < n) {
                             const uint32_t canon = junc_canon(seg, seg + 1);
                             if (junc_in_part(canon, nparts, part)) {
-                                const int slot = junc_find(T, canon);
+                                const int slot = lds_find(T.key, T.slots, canon);
                                 if (slot >= 0) { atomic_add_i32(T.cnt + slot, x); matched += x; }
                                 else { unmatched += x; flag = 1; lost = true; }
                             }
@@ -252,8 +238,8 @@ AMBI_HD void stage_junc_profile(const G& g, const rcell_t* cells, int P, int n, 
                         const int s = base + tid * kProfileChunk;
                         if (s >= P) continue;
                         rcell_t c[kProfileChunk];
-                        const int e = junc_load_cells(cells, P, vec, s, c);
-                        int prev = s > 0 ? (int)cells[s - 1] : 0;
+                        int prev;
+                        const int e = path_load_chunk(cells, P, vec, s, c, prev);
                         for (int k = 0; k < e; k++) {
                             const int cur = c[k];
                             if (s + k > 0 && cur == prev + 1) {
@@ -271,7 +257,7 @@ AMBI_HD void stage_junc_profile(const G& g, const rcell_t* cells, int P, int n, 
                 const JuncEnds E = ends[j];
                 const uint32_t canon = junc_canon(E.s, E.t);
                 if (!junc_in_part(canon, nparts, part)) continue;
-                const int slot = junc_find(T, canon);
+                const int slot = lds_find(T.key, T.slots, canon);
                 const int c = (slot >= 0 && T.val[slot] == j) ? T.cnt[slot] : 0;
                 out_count[j] = c;
                 used += c > 0;
@@ -292,29 +278,24 @@ AMBI_HD void stage_junc_profile(const G& g, const rcell_t* cells, int P, int n, 
     }
 }
 
-// One unit of a batch: reads UnitIn and UnitOut, profiles the path ambi_batch_unit_path(unit, which) returns against the unit's
-// junctions into the junction profile block.  SHORTCUT and INFEASIBLE units like any other; a unit with a negative status or
-// without a path gets zero counts and a summary that is zero but for the status.  Whole group.
+// One unit of a batch: profiles the path ambi_batch_unit_path(unit, which) returns (profile_path) against the unit's junctions into
+// the junction profile block.  SHORTCUT and INFEASIBLE units like any other; a unit with a negative status or without a path
+// gets zero counts and a summary that is zero but for the status.  Whole group.
 template <class G>
 AMBI_HD void junc_profile_unit(const G& g, const UnitIn* units, const JuncEnds* junc_ends, const double* junc_cn, const uint8_t* results, int u,
                                int which, int jwin, const JuncTable& T, uint8_t* block, const int64_t* off) {
     const UnitIn& U = units[u];
-    const UnitOut* h = reinterpret_cast<const UnitOut*>(results) + u;
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    const uint8_t* r = results + U.res_off;
     const int m = U.n_junc;
-    int P = which ? h->path_indel_len : h->path_len;
-    if (P > U.path_cap) P = 0;   // (never: the finish stages refuse such a path)
+    const ProfilePath Q = profile_path(units, results, u, which);
     int32_t* count = reinterpret_cast<int32_t*>(block + off[u]);
     UnitJuncProfile* out = reinterpret_cast<UnitJuncProfile*>(block) + u;
-    if (h->status < 0 || P <= 0) {
+    if (Q.P == 0) {
         for (int j = g.tid(); j < m; j += g.size()) count[j] = 0;
-        if (g.tid() == 0) { UnitJuncProfile z{}; z.status = h->status; *out = z; }
+        if (g.tid() == 0) { UnitJuncProfile z{}; z.status = Q.status; *out = z; }
         return;
     }
-    const rcell_t* cells = reinterpret_cast<const rcell_t*>(r + ((which && h->path_ind_stored) ? L.path_ind : L.path));
-    stage_junc_profile(g, cells, P, U.n_seg, junc_ends + U.junc_off, junc_cn + U.junc_off, m, jwin, T, count, out);
-    if (g.tid() == 0) out->status = h->status;
+    stage_junc_profile(g, Q.cells, Q.P, U.n_seg, junc_ends + U.junc_off, junc_cn + U.junc_off, m, jwin, T, count, out);
+    if (g.tid() == 0) out->status = Q.status;
 }
 
 }  // namespace ambi

@@ -44,16 +44,44 @@ struct UnitProfile {
 };
 static_assert(sizeof(UnitProfile) == 40, "UnitProfile is ambi_unit_profile_t");
 
-// Segments per window: the largest unit of the batch, capped so that the two difference arrays take 32 KB of group memory
-// (four workgroups of the profile kernel still fit a CU's 160 KB); AMBI_PROFILE_WINDOW (tests) can only shrink it.
-constexpr int kProfileWindowCap = 4096;
-constexpr int kProfileChunk = 8;   // cells per thread and tile: two 8-byte loads (per-unit arrays of the blob are 8-byte padded)
-AMBI_HD int profile_window(int max_n, int asked) {
-    int w = max_n < 1 ? 1 : max_n;
-    if (w > kProfileWindowCap) w = kProfileWindowCap;
+// ---- what the three on-request profiles (this one, ambi_junc_profile.hpp, ambi_frag_profile.hpp) share ----
+// The window rule: the largest unit of the batch, capped, and what a test asks for can only shrink it.
+AMBI_HD int capped_window(int max, int cap, int asked) {
+    int w = max < 1 ? 1 : max;
+    if (w > cap) w = cap;
     if (asked > 0 && asked < w) w = asked;
     return w;
 }
+
+// The unit prologue: the path of unit u to profile (unit_path, ambi_batch.hpp), or P = 0 -- the unit gets its kind's empty result --
+// for a negative status, no path, or a length above the capacity (never: the finish stages refuse such a path).
+struct ProfilePath { const rcell_t* cells; int P, status; };
+AMBI_HD ProfilePath profile_path(const UnitIn* units, const uint8_t* results, int u, int which) {
+    const UnitPath Q = unit_path(units, results, u, which);
+    return ProfilePath{Q.cells, (Q.status < 0 || Q.len <= 0 || Q.len > Q.path_cap) ? 0 : Q.len, Q.status};
+}
+
+// The chunked cell read: a thread's chunk [s, s + kProfileChunk) of the path as two 8-byte loads (vec: the path is 8-byte
+// aligned; per-unit arrays of the blob are 8-byte padded) or cell by cell, zero behind P (but for the padding of the 8-byte word
+// that holds cell P - 1).  Returns e, the cells of the chunk inside the path -- the caller's loop is `k < e` --; prev = the cell
+// in front of the chunk (0 in front of the path): the steps (i - 1, i) of the chunk need it.
+constexpr int kProfileChunk = 8;   // cells per thread and tile
+struct ProfileCell4 { rcell_t v[4]; } __attribute__((aligned(8)));
+AMBI_HD int path_load_chunk(const rcell_t* cells, int P, bool vec, int s, rcell_t (&c)[kProfileChunk], int& prev) {
+    for (int q = 0; q < kProfileChunk / 4; q++) {
+        const int at = s + 4 * q;
+        if (at >= P) { for (int k = 0; k < 4; k++) c[4 * q + k] = 0; continue; }
+        if (vec) { const ProfileCell4 w = *reinterpret_cast<const ProfileCell4*>(cells + at); for (int k = 0; k < 4; k++) c[4 * q + k] = w.v[k]; }
+        else for (int k = 0; k < 4; k++) c[4 * q + k] = at + k < P ? cells[at + k] : (rcell_t)0;
+    }
+    prev = s > 0 ? (int)cells[s - 1] : 0;
+    return s + kProfileChunk < P ? kProfileChunk : P - s;
+}
+
+// Segments per window: the largest unit of the batch, capped so that the two difference arrays take 32 KB of group memory
+// (four workgroups of the profile kernel still fit a CU's 160 KB); AMBI_PROFILE_WINDOW (tests) can only shrink it.
+constexpr int kProfileWindowCap = 4096;
+AMBI_HD int profile_window(int max_n, int asked) { return capped_window(max_n, kProfileWindowCap, asked); }
 AMBI_HD int64_t profile_bins_bytes(int window) { return int64_t(2) * 4 * window; }
 
 // Profile block: [UnitProfile[U]] [per unit: fwd i32 (n+1), rev i32 (n+1)], every per-unit array on a 16-byte boundary, slot 0
@@ -65,8 +93,6 @@ inline int64_t profile_block_layout(const std::vector<UnitIn>& units, std::vecto
     for (size_t u = 0; u < units.size(); u++) { off[u] = o; o += 2 * profile_rev_off(units[u].n_seg); }
     return o;
 }
-
-struct ProfileCell4 { rcell_t v[4]; } __attribute__((aligned(8)));
 
 // one event of a run boundary into the window [w0, w0 + wn) of the difference arrays (begin: the cell begins a run, else it ends one)
 AMBI_HD void profile_post(int32_t* df, int32_t* dr, int w0, int wn, int c, bool begin) {
@@ -102,14 +128,8 @@ AMBI_HD void stage_path_profile(const G& g, const rcell_t* cells, int P, int n, 
             const int s = base + tid * kProfileChunk;
             if (s >= P) continue;
             rcell_t c[kProfileChunk];
-            for (int q = 0; q < kProfileChunk / 4; q++) {
-                const int at = s + 4 * q;
-                if (at >= P) { for (int k = 0; k < 4; k++) c[4 * q + k] = 0; continue; }
-                if (vec) { const ProfileCell4 w = *reinterpret_cast<const ProfileCell4*>(cells + at); for (int k = 0; k < 4; k++) c[4 * q + k] = w.v[k]; }
-                else for (int k = 0; k < 4; k++) c[4 * q + k] = at + k < P ? cells[at + k] : (rcell_t)0;
-            }
-            int prev = s > 0 ? (int)cells[s - 1] : 0;
-            const int e = s + kProfileChunk < P ? kProfileChunk : P - s;
+            int prev;
+            const int e = path_load_chunk(cells, P, vec, s, c, prev);
             for (int k = 0; k < e; k++) {
                 const int cur = c[k];
                 if (s + k == 0) { profile_post(df, dr, w0, wn, cur, true); runs += first; }
@@ -155,32 +175,28 @@ AMBI_HD void stage_path_profile(const G& g, const rcell_t* cells, int P, int n, 
     }
 }
 
-// One unit of a batch: reads UnitIn and UnitOut, profiles the path ambi_batch_unit_path(unit, which) returns (which = 0: getBFB's;
-// 1: after indelBFB, which is `path` when path_ind_stored == 0) into the profile block.  SHORTCUT and INFEASIBLE units, whose
-// path is 1+..n+, like any other; a unit with a negative status or without a path gets zero counts and a summary that is zero
-// but for the status.  Whole group.
+// One unit of a batch: profiles the path ambi_batch_unit_path(unit, which) returns (profile_path) into the profile block.  SHORTCUT
+// and INFEASIBLE units, whose path is 1+..n+, like any other; a unit with a negative status or without a path gets zero counts
+// and a summary that is zero but for the status.  Whole group.
 template <class G>
 AMBI_HD void profile_unit(const G& g, const UnitIn* units, const uint8_t* results, int u, int which, int window, int32_t* bins,
                           uint8_t* block, const int64_t* off) {
     const UnitIn& U = units[u];
-    const UnitOut* h = reinterpret_cast<const UnitOut*>(results) + u;
     const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
     const uint8_t* r = results + U.res_off;
     const int n = U.n_seg;
-    int P = which ? h->path_indel_len : h->path_len;
-    if (P > U.path_cap) P = 0;   // (never: the finish stages refuse such a path)
+    const ProfilePath Q = profile_path(units, results, u, which);
     int32_t* fwd = reinterpret_cast<int32_t*>(block + off[u]);
     int32_t* rev = reinterpret_cast<int32_t*>(block + off[u] + profile_rev_off(n));
     UnitProfile* out = reinterpret_cast<UnitProfile*>(block) + u;
-    if (h->status < 0 || P <= 0) {
+    if (Q.P == 0) {
         for (int i = g.tid(); i <= n; i += g.size()) { fwd[i] = 0; rev[i] = 0; }
-        if (g.tid() == 0) { UnitProfile z{}; z.status = h->status; *out = z; }
+        if (g.tid() == 0) { UnitProfile z{}; z.status = Q.status; *out = z; }
         return;
     }
-    const rcell_t* cells = reinterpret_cast<const rcell_t*>(r + ((which && h->path_ind_stored) ? L.path_ind : L.path));
-    stage_path_profile(g, cells, P, n, reinterpret_cast<const int32_t*>(r + L.target_cn), reinterpret_cast<const double*>(r + L.seg_cn), window,
+    stage_path_profile(g, Q.cells, Q.P, n, reinterpret_cast<const int32_t*>(r + L.target_cn), reinterpret_cast<const double*>(r + L.seg_cn), window,
                        bins, fwd, rev, out);
-    if (g.tid() == 0) out->status = h->status;
+    if (g.tid() == 0) out->status = Q.status;
 }
 
 }  // namespace ambi

@@ -85,13 +85,9 @@ AMBI_HD int seq_prefix_find(const int64_t* off, int lo, int hi, int64_t key) {
 
 // the path ambi_batch_unit_path(unit, which) returns, or P = 0 for a unit with a negative status or without a path
 AMBI_HD const rcell_t* seq_unit_path(const UnitIn* units, const uint8_t* results, int u, int which, int* len) {
-    const UnitIn& U = units[u];
-    const UnitOut* h = reinterpret_cast<const UnitOut*>(results) + u;
-    const UnitLayout L = unit_layout(U.n_seg, U.bkp_cap, U.path_cap, U.out_cap);
-    int P = which ? h->path_indel_len : h->path_len;
-    if (h->status < 0 || P < 0 || P > U.path_cap) P = 0;
-    *len = P;
-    return reinterpret_cast<const rcell_t*>(results + U.res_off + ((which && h->path_ind_stored) ? L.path_ind : L.path));
+    const UnitPath Q = unit_path(units, results, u, which);
+    *len = (Q.status < 0 || Q.len < 0 || Q.len > Q.path_cap) ? 0 : Q.len;
+    return Q.cells;
 }
 
 // byte range of the run of `len` cells that starts with cell c: [lo, hi) relative to the unit's store (ids outside 1..n, which no

@@ -93,6 +93,22 @@ def test_profile_stage_under_asan_ubsan():
     assert r.returncode == 0 and "SANITIZED RUN CLEAN" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
+def test_stage_check_under_asan_ubsan(tmp_path):
+    """tests/tools/path_profile_stage_check.cpp: the stage on the host group against a cell-by-cell transcription, and the chunked
+    cell read the three profile stages share on its own (path lengths around the tile edges, the cells at every offset from an
+    8-byte boundary, windows of 1 .. n + 1, single runs, single-cell runs, -n .. -1, a last run that ends at n, fold-back turns),
+    every buffer of exactly its stated size, as a stand-alone program under AddressSanitizer + UBSan."""
+    exe = str(tmp_path / "path_profile_stage_check")
+    src = os.path.join(ROOT, "tests", "tools", "path_profile_stage_check.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                        "-Wall", "-Wno-sign-compare", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "ambigram_amd", "csrc"),
+                        "-o", exe, src], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0 and "path_profile_stage_check: ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+
+
 def _sharded(lib, oracle, workdir, devices):
     items = pc.many_units(oracle, workdir)
     records = [oc for _, _, oc in items]
