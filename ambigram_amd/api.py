@@ -49,6 +49,12 @@ class UnitFragProfile(C.Structure):     # ambi_unit_frag_profile_t
                                          "reserved")] + [("occurrences", C.c_int64)]
 
 
+class UnitEvidenceProfile(C.Structure):     # ambi_unit_evidence_profile_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "steps", "steps_covered", "max_depth", "first_uncovered", "longest_uncovered",
+                                         "longest_uncovered_at", "juncs", "juncs_used", "juncs_covered", "juncs_uncovered",
+                                         "unmatched_covered")] + [("depth_sum", C.c_int64)]
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -133,6 +139,13 @@ def _declare(L):
         "ambi_batch_unit_frag_profile": (C.c_int, [vp, i32, _P(UnitFragProfile)]),
         "ambi_batch_unit_frag_support": (C.c_int, [vp, i32, pi32, pi32, pi32, pi32, i32]),
         "ambi_batch_frag_profile_device": (C.c_int, [vp, _P(vp), pi64]),
+        "ambi_batch_evidence_profile": (C.c_int, [vp, i32, vp]),
+        "ambi_batch_evidence_profile_wait": (C.c_int, [vp]),
+        "ambi_batch_unit_evidence_profile": (C.c_int, [vp, i32, _P(UnitEvidenceProfile)]),
+        "ambi_batch_unit_evidence_juncs": (C.c_int, [vp, i32, pi32, pi32, pi32, pi32, i32]),
+        "ambi_batch_unit_evidence_depth": (C.c_int, [vp, i32, i64, i64, pi32]),
+        "ambi_batch_evidence_profile_device": (C.c_int, [vp, _P(vp), pi64]),
+        "ambi_batch_evidence_depth_device": (C.c_int, [vp, _P(vp), pi64, pi64, i32]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
         "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
         "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
@@ -662,6 +675,54 @@ class Batch:
         p, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.ambi_batch_frag_profile_device(self.h, C.byref(p), C.byref(n)), "frag_profile_device")
         return p.value or 0, n.value
+
+    def evidence_profile(self, which=1, stream=None):
+        """Queues the evidence depth profile of the last run's paths behind that run (ambi_batch_evidence_profile): per step of a
+        unit's path (which: 0 getBFB's, 1 the final one) the number of fragment occurrences over it, per junction its covered
+        traversals; `stream` is not blocked."""
+        self._ck(self.lib.ambi_batch_evidence_profile(self.h, which, C.c_void_p(stream or 0)), "evidence_profile")
+
+    def evidence_profile_wait(self):
+        """Waits for the evidence profile in host memory (the run's results are final first); unit_evidence_profile /
+        unit_evidence_juncs / unit_evidence_depth answer afterwards."""
+        self._ck(self.lib.ambi_batch_evidence_profile_wait(self.h), "evidence_profile_wait")
+
+    def unit_evidence_profile(self, u):
+        r = UnitEvidenceProfile()
+        self._ck(self.lib.ambi_batch_unit_evidence_profile(self.h, u, C.byref(r)), "unit_evidence_profile")
+        return {k: getattr(r, k) for k, _ in UnitEvidenceProfile._fields_}
+
+    def unit_evidence_juncs(self, u):
+        """(count, covered, min_depth, graph_index): int32 arrays over the unit's junctions -- steps credited to the junction, those
+        of them under at least one fragment occurrence, the smallest depth over them (-1: never taken), and the junction's index
+        in Graph.junctions() (its own for a unit added with add_unit)."""
+        m = self._ck(self.lib.ambi_batch_unit_evidence_juncs(self.h, u, None, None, None, None, 1 << 30), "unit_evidence_juncs")
+        out = [np.zeros(m, np.int32) for _ in range(4)]
+        self._ck(self.lib.ambi_batch_unit_evidence_juncs(self.h, u, *[a.ctypes.data_as(_P(C.c_int32)) for a in out], m), "unit_evidence_juncs")
+        return tuple(out)
+
+    def unit_evidence_depth(self, u, first=0, n=None):
+        """int32 depths of the steps [first, first + n) of a unit (default: to the last step); only this range is downloaded."""
+        if n is None:
+            n = self.unit_evidence_profile(u)["steps"] - first
+        out = np.zeros(max(n, 0), np.int32)
+        self._ck(self.lib.ambi_batch_unit_evidence_depth(self.h, u, first, n, out.ctypes.data_as(_P(C.c_int32))), "unit_evidence_depth")
+        return out
+
+    def evidence_profile_device(self):
+        """(address, bytes) of the evidence profile block in device memory (ambi_batch_evidence_profile_device), for collectives."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._ck(self.lib.ambi_batch_evidence_profile_device(self.h, C.byref(p), C.byref(n)), "evidence_profile_device")
+        return p.value or 0, n.value
+
+    def evidence_depth_device(self):
+        """(address, bytes, unit_off) of the depth area in device memory (ambi_batch_evidence_depth_device): unit u's depths are
+        int32[steps] at byte unit_off[u]."""
+        U = self.size()
+        p, n = C.c_void_p(), C.c_int64()
+        off = np.zeros(U, np.int64)
+        self._ck(self.lib.ambi_batch_evidence_depth_device(self.h, C.byref(p), C.byref(n), off.ctypes.data_as(_P(C.c_int64)), U), "evidence_depth_device")
+        return p.value or 0, n.value, off
 
     def set_unit_sequences(self, u, bases, seg_off):
         """Bases of a unit added with add_unit (ambi_batch_set_unit_sequences): local segment i + 1 = bases[seg_off[i]:seg_off[i + 1]]."""

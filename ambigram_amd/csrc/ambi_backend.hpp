@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ambi_pack.hpp"
+#include "ambi_evidence_profile.hpp"
 #include "ambi_frag_profile.hpp"
 #include "ambi_junc_profile.hpp"
 #include "ambi_profile.hpp"
@@ -86,15 +87,17 @@ class Backend {
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
 
     // ---- on-request profiles of every unit's path (which: 0 getBFB, 1 after indelBFB) ----
-    // Three kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand), the
-    // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts) and the fragment support profile
-    // (ambi_frag_profile.hpp: occurrences of every .juncs fragment in either direction), each a block [summary[U]][per unit counts].
+    // Four kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand), the
+    // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts), the fragment support profile
+    // (ambi_frag_profile.hpp: occurrences of every .juncs fragment in either direction) and the evidence depth profile
+    // (ambi_evidence_profile.hpp: fragment occurrences over every step, per junction its covered traversals), each a block
+    // [summary[U]][per unit counts]; the evidence kind has a depth area beside its block that stays where it was computed.
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
-    // simulation); the HIP engine overrides the three virtual entries with its kernels and never reaches it.
+    // simulation); the HIP engine overrides the virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2 };
-    static constexpr int kProfileKinds = 3;
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3 };
+    static constexpr int kProfileKinds = 4;
     void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
     virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
@@ -104,7 +107,8 @@ class Backend {
         ProfileState& P = prof_[kind];
         profile_layout(kind);
         P.blob.assign((size_t)P.bytes, 0);
-        if (kind == kFragment) host_frag_profile(blob.data(), which, P);
+        if (kind == kEvidence) host_evidence_profile(blob.data(), which, P);
+        else if (kind == kFragment) host_frag_profile(blob.data(), which, P);
         else if (kind == kJunction) host_junc_profile(blob.data(), which, P);
         else host_profile(blob.data(), which, P);
         P.view = nullptr;
@@ -172,6 +176,38 @@ class Backend {
         if (rev && F > 0) memcpy(rev, p + arr, sizeof(int32_t) * (size_t)F);
         if (first && F > 0) memcpy(first, p + 2 * arr, sizeof(int32_t) * (size_t)F);
         return F;
+    }
+
+    int evidence_summary(int unit, UnitEvidenceProfile* out) const {
+        const ProfileState& P = prof_[kEvidence];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitEvidenceProfile*>(P.view)[unit];
+        return 0;
+    }
+    int evidence_counts(int unit, int32_t* count, int32_t* covered, int32_t* min_depth, int cap) const {   // m values each; returns m
+        const ProfileState& P = prof_[kEvidence];
+        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
+        const int m = prof_hb_->units[(size_t)unit].n_junc;
+        if (cap < m) return ST_ERR_BAD_INPUT;
+        const uint8_t* p = P.view + P.off[(size_t)unit];
+        const int64_t arr = evidence_arr_bytes(m);
+        if (count && m > 0) memcpy(count, p, sizeof(int32_t) * (size_t)m);
+        if (covered && m > 0) memcpy(covered, p + arr, sizeof(int32_t) * (size_t)m);
+        if (min_depth && m > 0) memcpy(min_depth, p + 2 * arr, sizeof(int32_t) * (size_t)m);
+        return m;
+    }
+    // the depths of the steps [first, first + n) of a unit to host memory (nothing else of the depth area travels), and the area where
+    // it was computed (device memory of the HIP engine) with every unit's byte offset in it; valid after profile_wait(kEvidence)
+    virtual int evidence_depth_copy(int unit, int64_t first, int64_t n, int32_t* out) {
+        const ProfileState& P = prof_[kEvidence];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) memcpy(out, reinterpret_cast<const uint8_t*>(depth_.data()) + depth_off_[(size_t)unit] + 4 * first, (size_t)(4 * n));
+        return 0;
+    }
+    virtual int evidence_depth_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) {
+        if (!prof_[kEvidence].view) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = depth_.data();
+        return evidence_depth_offsets(bytes, unit_off, cap);
     }
 
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
@@ -252,7 +288,8 @@ class Backend {
     ProfileState prof_[kProfileKinds];   // [ProfileKind]
     void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
         ProfileState& P = prof_[kind];
-        if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
+        if (kind == kEvidence) { P.bytes = evidence_block_layout(prof_hb_->units, P.off); depth_bytes_ = evidence_depth_layout(prof_hb_->units, depth_off_); }
+        else if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
         else P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
     }
     // The windows of the bound batch; the environment variables (tests) can only shrink them (capped_window).
@@ -266,6 +303,19 @@ class Backend {
         *jwin = junc_window(prof_hb_->max_m, env_int("AMBI_JPROFILE_JUNC_WINDOW"));
         *slots = junc_slots(*jwin);
         *swin = junc_seg_window(prof_hb_->max_n, env_int("AMBI_JPROFILE_SEG_WINDOW"));
+    }
+    void evidence_windows(int* jwin, int* slots) const {   // junctions per pass and table slots of the evidence scan stage
+        *jwin = evidence_junc_window(prof_hb_->max_m, env_int("AMBI_JPROFILE_JUNC_WINDOW"));
+        *slots = junc_slots(*jwin);
+    }
+    std::vector<int64_t> depth_off_;     // the evidence kind's depth area: every unit's byte offset and the size (profile_layout)
+    int64_t depth_bytes_ = 0;
+    int evidence_depth_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
+        const int U = (int)depth_off_.size();
+        if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
+        if (bytes) *bytes = depth_bytes_;
+        if (unit_off) for (int u = 0; u < U; u++) unit_off[u] = depth_off_[(size_t)u];
+        return 0;
     }
     int sequence_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
         const int U = (int)prof_hb_->units.size();
@@ -308,6 +358,24 @@ class Backend {
         HostGroup g;
         for (size_t u = 0; u < units.size(); u++) frag_profile_unit(g, units.data(), A, blob, (int)u, which, T, P.blob.data(), P.off.data());
     }
+    void host_evidence_profile(const uint8_t* blob, int which, ProfileState& P) {
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        const FragImage& I = prof_hb_->frag;
+        int pwin, fslots, jwin, slots;
+        frag_profile_windows(&pwin, &fslots);
+        evidence_windows(&jwin, &slots);
+        std::vector<int32_t> lds((size_t)(frag_profile_lds_bytes(fslots, pwin) / 4)), lds2((size_t)(evidence_scan_lds_bytes(slots, 1) / 4));
+        const FragTable T = frag_table(lds.data(), fslots, pwin);
+        const EvidenceTable E = evidence_table(lds2.data(), slots);
+        const FragArgs A{I.cells.data(), I.frag_off.data(), I.cell_off.data(), I.pref_off.data(), I.n_frag.data()};
+        depth_.resize((size_t)(depth_bytes_ / 16) + 1);   // (kept between requests as the device keeps its area: stale values behind it)
+        uint8_t* area = reinterpret_cast<uint8_t*>(depth_.data());
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++) evidence_mark_unit(g, units.data(), A, blob, (int)u, which, T, area, depth_off_.data());
+        for (size_t u = 0; u < units.size(); u++)
+            evidence_scan_unit(g, units.data(), prof_hb_->junc_ends.data(), blob, (int)u, which, jwin, E, area, depth_off_.data(), P.blob.data(), P.off.data());
+    }
+    std::vector<Seq16A> depth_;          // the default implementation's depth area (16-byte aligned)
     std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };
 

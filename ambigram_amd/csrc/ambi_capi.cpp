@@ -115,7 +115,7 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled[Backend::kProfileKinds] = {false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    bool profiled[Backend::kProfileKinds] = {false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
@@ -151,7 +151,7 @@ const char* ambi_error_string(int code) {
         case AMBI_ERR_HIP: return "HIP runtime error";
         case AMBI_ERR_STATE: return "call order violated";
         case AMBI_ERR_ARG: return "bad argument";
-        case AMBI_ERR_TOO_LARGE: return "the sequences of the unit range exceed max_bytes";
+        case AMBI_ERR_TOO_LARGE: return "the sequences of the unit range exceed max_bytes, or a unit's evidence depth bound reaches 2^31";
         default: return lh_error_string(code);
     }
 }
@@ -446,14 +446,14 @@ int ambi_batch_upload(ambi_batch_t* b) {
     b->be->profile_bind(&b->hb);
     int rc = b->be->upload(b->hb, b->cfg);
     if (rc == 0) b->uploaded = true;
-    b->ran = false; b->profiled[0] = b->profiled[1] = b->profiled[2] = false; b->sequenced = false;
+    b->ran = false; for (bool& p : b->profiled) p = false; b->sequenced = false;
     b->be->sequence_reset();
     return rc;
 }
 int ambi_batch_run(ambi_batch_t* b, uint32_t flags, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!b->uploaded) return AMBI_ERR_STATE;
-    b->downloaded = false; b->mail_view = false; b->profiled[0] = b->profiled[1] = b->profiled[2] = false; b->sequenced = false;
+    b->downloaded = false; b->mail_view = false; for (bool& p : b->profiled) p = false; b->sequenced = false;
     b->be->sequence_reset();
     const int rc = b->be->run(flags, hip_stream);
     if (rc == 0) b->ran = true;
@@ -517,7 +517,7 @@ int ambi_batch_run_sharded(ambi_batch_t* b, uint32_t flags, const int32_t* devic
         for (auto& s : b->shards) s->hb.finalize();
     }
     b->hb.finalize();
-    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; b->profiled[0] = b->profiled[1] = b->profiled[2] = false; b->sequenced = false;
+    b->downloaded = false; b->mail_view = false; b->sharded_ready = false; for (bool& p : b->profiled) p = false; b->sequenced = false;
     for (auto& s : b->shards) s->be->sequence_reset();
     // every share on its own (resident) thread, the first one too: set_device changes the current device of the thread that calls it,
     // and the caller's thread keeps the device it had.  Nothing is merged: the getters read a unit where its share left it.
@@ -663,16 +663,21 @@ int ambi_batch_unit_path(const ambi_batch_t* b, int32_t unit, int32_t which, int
     return len;
 }
 // ---- copy-number profile of the paths (ambi_profile.hpp; localhap.cpp:318-351) ----
-// Both kinds (Backend::ProfileKind) go to the batch's backend or, after run_sharded, to every share that holds units: a request on
+// Every kind (Backend::ProfileKind) goes to the batch's backend or, after run_sharded, to every share that holds units: a request on
 // the share's own stream (the backend selects its device for the call)
 static int profile_start(ambi_batch_t* b, Backend::ProfileKind kind, int32_t which, void* hip_stream) {
     if (!b) return AMBI_ERR_ARG;
     if (!(b->sharded_ready || (b->uploaded && b->ran))) return AMBI_ERR_STATE;
     if (which < 0 || which > 1) return AMBI_ERR_ARG;
     b->profiled[kind] = false;
-    if (kind == Backend::kFragment) {   // every unit has a prefix in the image from here on (F = 0 where nothing was attached)
+    if (kind == Backend::kFragment || kind == Backend::kEvidence) {   // every unit has a prefix in the image from here on (F = 0 where nothing was attached)
         b->hb.frag.seal(b->hb.units);
         for (auto& s : b->shards) s->hb.frag.seal(s->hb.units);
+    }
+    if (kind == Backend::kEvidence) {   // depth is int32: refused when a unit's bound reaches 2^31, nothing wraps silently
+        const FragImage& I = b->hb.frag;
+        for (size_t u = 0; u < b->hb.units.size(); u++)
+            if (evidence_depth_overflows(I.frag_off[(size_t)I.pref_off[u] + (size_t)I.n_frag[u]], I.n_frag[u])) return AMBI_ERR_TOO_LARGE;
     }
     if (!b->sharded_ready) return b->be->profile(kind, which, hip_stream);
     for (auto& s : b->shards)
@@ -756,7 +761,7 @@ int ambi_batch_set_unit_fragments(ambi_batch_t* b, int32_t unit, const int32_t* 
     }
     const int64_t zero = 0;
     b->hb.frag.set((size_t)unit, local.data(), n > 0 ? frag_off : &zero, n, nullptr);
-    b->profiled[Backend::kFragment] = false;
+    b->profiled[Backend::kFragment] = false; b->profiled[Backend::kEvidence] = false;
     return 0;
 }
 int ambi_batch_frag_profile(ambi_batch_t* b, int32_t which, void* hip_stream) { return profile_start(b, Backend::kFragment, which, hip_stream); }
@@ -785,6 +790,50 @@ int ambi_batch_unit_frag_support(const ambi_batch_t* b, int32_t unit, int32_t* f
         for (int f = 0; f < F; f++) graph_index[f] = f < (int)map.size() ? map[f] : f;
     }
     return rc;
+}
+// ---- evidence depth profile of the paths (ambi_evidence_profile.hpp; fragments as above, junctions as the junction profile's) ----
+int ambi_batch_evidence_profile(ambi_batch_t* b, int32_t which, void* hip_stream) { return profile_start(b, Backend::kEvidence, which, hip_stream); }
+int ambi_batch_evidence_profile_wait(ambi_batch_t* b) { return profile_wait(b, Backend::kEvidence); }
+int ambi_batch_evidence_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) { return profile_device(b, Backend::kEvidence, dev_ptr, bytes); }
+int ambi_batch_evidence_depth_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kEvidence] || b->sharded_ready) return AMBI_ERR_STATE;   // (one area per share: no single device view)
+    if (unit_off && cap < (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    return b->be->evidence_depth_device(dev_ptr, bytes, unit_off, cap) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_unit_evidence_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_evidence_profile_t* out) {
+    if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kEvidence]) return AMBI_ERR_STATE;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    static_assert(sizeof(ambi_unit_evidence_profile_t) == sizeof(UnitEvidenceProfile), "ambi_unit_evidence_profile_t is ambi::UnitEvidenceProfile");
+    static_assert(sizeof(ambi_unit_evidence_profile_t) == 56, "the evidence summary is 56 bytes");
+    return be->evidence_summary(local, reinterpret_cast<UnitEvidenceProfile*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_unit_evidence_juncs(const ambi_batch_t* b, int32_t unit, int32_t* count, int32_t* covered, int32_t* min_depth, int32_t* graph_index, int32_t cap) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kEvidence]) return AMBI_ERR_STATE;
+    const int m = b->hb.units[unit].n_junc;
+    if (cap < m) return AMBI_ERR_ARG;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    const int rc = be->evidence_counts(local, count, covered, min_depth, cap);
+    if (rc < 0) return AMBI_ERR_STATE;
+    if (graph_index) {
+        const std::vector<int32_t>& map = b->hb.junc_global[unit];   // (empty for a raw unit)
+        for (int j = 0; j < m; j++) graph_index[j] = j < (int)map.size() ? map[j] : j;
+    }
+    return rc;
+}
+int ambi_batch_unit_evidence_depth(ambi_batch_t* b, int32_t unit, int64_t first, int64_t n, int32_t* out) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kEvidence]) return AMBI_ERR_STATE;
+    int local = unit;
+    Backend* be = b->owner(unit, &local);
+    UnitEvidenceProfile s;
+    if (be->evidence_summary(local, &s)) return AMBI_ERR_STATE;
+    if (first < 0 || n < 0 || first > s.steps || n > s.steps - first || (n > 0 && !out)) return AMBI_ERR_ARG;
+    return be->evidence_depth_copy(local, first, n, out) ? AMBI_ERR_STATE : 0;
 }
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
 int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {

@@ -23,7 +23,11 @@
 //                                                  (ambi_junc_profile.hpp)                         <- the same cells + a hash table in LDS
 //   ambi_frag_profile_kernel      1 block / unit   on request: occurrences of every .juncs fragment in the path, both directions,
 //                                                  + summary (ambi_frag_profile.hpp)               <- the same cells + chained patterns in LDS
-//                                                  (the three profile kernels share unit prologue, chunked cell read and window rule --
+//   ambi_evidence_mark_kernel     1 block / unit   on request: the fragment profile's match; every occurrence posts +1 / -1 into the
+//                                                  unit's depth area (ambi_evidence_profile.hpp)   <- the same cells, device-memory atomics
+//   ambi_evidence_scan_kernel     1 block / unit   on request, behind the mark kernel: depth per step by a scan in place, summary,
+//                                                  per junction covered traversals                 <- 4 bytes / step + the cells per pass
+//                                                  (the profile kernels share unit prologue, chunked cell read and window rule --
 //                                                  profile_path, path_load_chunk, capped_window of ambi_profile.hpp -- and the two tables
 //                                                  their probe, lds_find / lds_claim of ambi_junc_profile.hpp; every reader of a unit's
 //                                                  path in the result blob selects it with unit_path of ambi_batch.hpp)
@@ -624,6 +628,28 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_frag_profile_kernel(Batc
         __syncthreads();
     }
 }
+// ---- evidence depth profile of the paths (ambi_evidence_profile.hpp; launched by HipBackend::profile_queue only) ----
+// Two launches, one workgroup of 256 threads per unit each, grid-stride over the units.  The mark kernel posts the occurrences into
+// the depth area with device-memory atomics; the scan kernel reads the area with plain loads, and the kernel boundary between the
+// two is what makes the atomics' results visible to them (the phases are NOT fused: a CU's vector L1 is not refreshed by atomics
+// that went to L2).  Group memory: 256 bytes for the group's reductions, then the fragment profile's table (mark) or the junction
+// table of `slots` slots (key, lowest index, steps, covered steps, minimum depth: 20 bytes each) and 24 bytes per thread (scan).
+__global__ __launch_bounds__(kProfileThreads) void ambi_evidence_mark_kernel(BatchArgs A, FragArgs I, int which, int pwin, int slots, uint8_t* depth, const int64_t* depth_off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    const FragTable T = frag_table(ambi_lds + kProfileScratchBytes, slots, pwin);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        evidence_mark_unit(g, A.units, I, A.results, u, which, T, depth, depth_off);
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(kProfileThreads) void ambi_evidence_scan_kernel(BatchArgs A, int which, int jwin, int slots, uint8_t* depth, const int64_t* depth_off, uint8_t* block, const int64_t* off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    const EvidenceTable T = evidence_table(ambi_lds + kProfileScratchBytes, slots);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        evidence_scan_unit(g, A.units, A.junc_ends, A.results, u, which, jwin, T, depth, depth_off, block, off);
+        __syncthreads();
+    }
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -762,8 +788,11 @@ struct Lease {
     hipStream_t run_stream = nullptr;   // own_stream(): for callers without a stream (ambi_batch_run_sharded's shares)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
     // [Backend::ProfileKind] copy-number profile [UnitProfile[U]][per unit fwd, rev], junction usage profile [UnitJuncProfile[U]][per unit count],
-    // fragment support profile [UnitFragProfile[U]][per unit fwd, rev, first]
+    // fragment support profile [UnitFragProfile[U]][per unit fwd, rev, first], evidence depth profile [UnitEvidenceProfile[U]][per unit
+    // count, covered, min_depth]
     RequestBlock prof[Backend::kProfileKinds];
+    // the evidence kind's depth area: int32 per cell of every unit's path capacity; it never travels to the host as a whole
+    uint8_t* d_depth = nullptr; int64_t d_depth_bytes = 0;
     // the batch's fragment image (HipBackend::fragment_image) [cells][frag_off][cell_off][pref_off][n_frag], its pinned twin and the
     // event behind its last upload (the host writes the twin again only behind it)
     uint8_t* d_frag_img = nullptr; int64_t d_frag_img_bytes = 0;
@@ -1130,6 +1159,7 @@ class HipBackend : public Backend {
                 if (L->h_runs_bytes[k] > kKeepRuns) { (void)hipHostFree(L->h_runs[k]); L->h_runs[k] = nullptr; L->h_runs_bytes[k] = 0; }
             }
             for (RequestBlock& B : L->prof) B.trim(kKeepProfile);
+            if (L->d_depth_bytes > kKeepCells) { (void)hipFree(L->d_depth); L->d_depth = nullptr; L->d_depth_bytes = 0; }
             if (L->d_frag_img_bytes > kKeepProfile) { (void)hipFree(L->d_frag_img); L->d_frag_img = nullptr; L->d_frag_img_bytes = 0; }
             if (L->h_frag_bytes > kKeepProfile) { (void)hipHostFree(L->h_frag); L->h_frag = nullptr; L->h_frag_bytes = 0; }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
@@ -2160,7 +2190,7 @@ class HipBackend : public Backend {
         out->copied_bytes = words * 4 + (runs_hdr_[slot] ? U * (int64_t)sizeof(UnitOut) : 0);
         return 0;
     }
-    // ---- on-request results: the profiles (ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp) and the sequences below ----
+    // ---- on-request results: the profiles (ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp, ambi_evidence_profile.hpp) and the sequences below ----
     // A request works on `stream` behind everything that writes the result blob in the last run: the caller's stream of that run,
     // which has waited for every side stream at the end of run(), and -- for a caller that asks on another stream -- explicitly the
     // events "results complete" of the side streams (lean / list finish kernels, direct edit + full launch) and of the express
@@ -2212,31 +2242,44 @@ class HipBackend : public Backend {
         Lease* L = lease_;
         RequestBlock& B = L->prof[kind]; Request& R = req_[kind]; ProfileState& P = prof_[kind];
         const int64_t U = (int64_t)hb().units.size();
-        if (kind == kFragment) {   // (the image can change between requests, and with it the layout)
-            if (frag_img_version_ != hb().frag.version) { if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done)); R.laid_out = false; }
+        if (kind == kFragment || kind == kEvidence) {   // (the image can change between requests, and with it the fragment kind's layout)
+            if (frag_img_version_ != hb().frag.version) {
+                for (ProfileKind k : {kFragment, kEvidence}) if (req_[k].queued) HIP_CK(hipEventSynchronize(L->prof[k].ev_done));   // (their kernels read the image)
+                req_[kFragment].laid_out = false; R.laid_out = false;
+            }
             if (int rc = fragment_image(s)) return rc;
         }
         if (!R.laid_out) {
             profile_layout(kind);
-            const int64_t total = P.bytes + U * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
+            const int64_t n_off = kind == kEvidence ? 2 * U : U;              // (the evidence kind: the depth area's offsets behind the block's)
+            const int64_t total = P.bytes + n_off * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
+            if (kind == kEvidence) { if (int rc = lease_device_block(&L->d_depth, &L->d_depth_bytes, depth_bytes_ > 0 ? depth_bytes_ : 16)) return rc; }
             if (int rc = lease_device_block(&B.d, &B.d_bytes, total)) return rc;
             if (int rc = lease_pinned_block(&B.h, nullptr, &B.h_bytes, total)) return rc;
             if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
             for (hipEvent_t* e : {&B.ev_src, &B.ev_packed, &B.ev_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
             // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
             memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
+            if (kind == kEvidence) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), depth_off_.data(), (size_t)U * sizeof(int64_t));
             R.d_off = reinterpret_cast<int64_t*>(B.d + P.bytes);
-            HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)U * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)n_off * sizeof(int64_t), hipMemcpyHostToDevice, s));
             R.laid_out = true;
         }
         if (int rc = behind_results(s, B.ev_src)) return rc;
-        int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes;
-        if (kind == kFragment) { frag_profile_windows(&pwin, &slots); lds += (int)frag_profile_lds_bytes(slots, pwin); }
+        int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes, fslots = 0, lds_mark = kProfileScratchBytes;
+        if (kind == kEvidence) {
+            frag_profile_windows(&pwin, &fslots); lds_mark += (int)frag_profile_lds_bytes(fslots, pwin);
+            evidence_windows(&jwin, &slots); lds += (int)evidence_scan_lds_bytes(slots, kProfileThreads);
+        } else if (kind == kFragment) { frag_profile_windows(&pwin, &slots); lds += (int)frag_profile_lds_bytes(slots, pwin); }
         else if (kind == kJunction) { junc_profile_windows(&jwin, &slots, &swin); lds += (int)junc_profile_lds_bytes(slots, swin); }
         else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
         if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
         const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        if (kind == kFragment) hipLaunchKernelGGL(ambi_frag_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, frag_args_, which, pwin, slots, B.d, (const int64_t*)R.d_off);
+        if (kind == kEvidence) {   // (the scan kernel behind the mark kernel on one stream: the boundary orders atomics and loads)
+            hipLaunchKernelGGL(ambi_evidence_mark_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, frag_args_, which, pwin, fslots, L->d_depth, (const int64_t*)(R.d_off + U));
+            HIP_CK(hipGetLastError());
+            hipLaunchKernelGGL(ambi_evidence_scan_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, L->d_depth, (const int64_t*)(R.d_off + U), B.d, (const int64_t*)R.d_off);
+        } else if (kind == kFragment) hipLaunchKernelGGL(ambi_frag_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, frag_args_, which, pwin, slots, B.d, (const int64_t*)R.d_off);
         else if (kind == kJunction) hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, B.d, (const int64_t*)R.d_off);
         else hipLaunchKernelGGL(ambi_path_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, window, B.d, (const int64_t*)R.d_off);
         HIP_CK(hipGetLastError());
@@ -2269,6 +2312,19 @@ class HipBackend : public Backend {
         if (ptr) *ptr = lease_->prof[kind].d;
         if (bytes) *bytes = prof_[kind].bytes;
         return 0;
+    }
+    // the evidence kind's depth area: a range of one unit's depths to the host (everything queued is complete: profile_wait has
+    // returned), and the area itself
+    int evidence_depth_copy(int unit, int64_t first, int64_t n, int32_t* out) override {
+        DeviceGuard dg_(device_);
+        if (!prof_[kEvidence].view || !lease_ || !lease_->d_depth || unit < 0 || unit >= (int)depth_off_.size() || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) HIP_CK(hipMemcpy(out, lease_->d_depth + depth_off_[(size_t)unit] + 4 * first, (size_t)(4 * n), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int evidence_depth_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) override {
+        if (!prof_[kEvidence].view || !lease_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->d_depth;
+        return evidence_depth_offsets(bytes, unit_off, cap);
     }
     // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----
     // sequence() works on `stream` behind everything that writes the result blob in the last run (behind_results): the

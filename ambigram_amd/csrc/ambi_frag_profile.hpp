@@ -24,6 +24,8 @@
 // A fragment is always written by the same thread (f modulo the group size), whichever window holds its patterns, so the thread
 // that completes a fragment with pattern 2f + 1 reads back what itself wrote for 2f.
 //
+// The window set-up and the sweep are frag_window_build / frag_window_sweep, which the evidence depth profile
+// (ambi_evidence_profile.hpp) runs as well with another action on a match.
 // Only group-memory atomics are used, no atomic on device memory.  SPMD over the group policies of ambi_group.hpp: BlockGroup in
 // ambi_frag_profile_kernel, HostGroup in Backend::profile's default (the host simulation) and in
 // tests/tools/frag_profile_stage_check.cpp.
@@ -123,6 +125,65 @@ AMBI_HD bool frag_palindrome(const rcell_t* fc, int a, int b) {
     return true;
 }
 
+// The windowed match, shared by the fragment profile below and the evidence depth profile (ambi_evidence_profile.hpp): the two
+// differ only in what a verified occurrence does.
+// frag_window_build: the patterns [w0, w0 + wn) of the unit into the cleared table; true when the window holds a live pattern (a
+// barrier: the table is complete behind it) -- a window without one needs no sweep.  Whole group.
+template <class G>
+AMBI_HD bool frag_window_build(const G& g, int P, const rcell_t* fc, const int32_t* foff, int w0, int wn, const FragTable& T) {
+    const int tid = g.tid(), sz = g.size();
+    for (int s = tid; s < T.slots; s += sz) { T.key[s] = 0; T.head[s] = -1; }
+    for (int j = tid; j < wn; j += sz) { T.next[j] = -1; T.cnt[j] = 0; T.first[j] = 0x7fffffff; }
+    g.sync();
+    bool mine_any = false;
+    for (int j = tid; j < wn; j += sz) {
+        const int p = w0 + j, f = p >> 1, dir = p & 1;
+        const int a = foff[f], b = foff[f + 1], L = b - a;
+        if (L < 2 || L > P) continue;                       // (no occurrence is possible)
+        if (dir && frag_palindrome(fc, a, b)) continue;     // rc(f) == f: counted once, as f
+        if (frag_insert(T, junc_key(frag_cell(fc, a, b, dir, 0), frag_cell(fc, a, b, dir, 1)), j)) mine_any = true;
+    }
+    return g.any(mine_any);
+}
+// frag_window_sweep: every step of the path against the window's table; match(j, i, L) for every verified occurrence at cell i of the
+// window's pattern j (L cells).  Whole group; no barrier inside.
+template <class G, class M>
+AMBI_HD void frag_window_sweep(const G& g, const rcell_t* cells, int P, bool vec, const rcell_t* fc, const int32_t* foff, int w0, const FragTable& T,
+                               const M& match) {
+    const int tid = g.tid(), sz = g.size();
+    for (int base = 0; base < P; base += sz * kProfileChunk) {
+        const int s = base + tid * kProfileChunk;
+        if (s >= P) continue;
+        rcell_t c[kProfileChunk];
+        int prev;
+        const int e = path_load_chunk(cells, P, vec, s, c, prev);
+        for (int k = 0; k < e; k++) {
+            const int cur = c[k];
+            if (s + k > 0) {
+                const int i = s + k - 1;            // the step (c[i], c[i + 1])
+                const int slot = lds_find(T.key, T.slots, junc_key(prev, cur));
+                for (int j = slot >= 0 ? T.head[slot] : -1; j >= 0; j = T.next[j]) {
+                    const int p = w0 + j, dir = p & 1;
+                    const int a = foff[p >> 1], b = foff[(p >> 1) + 1], L = b - a;
+                    if (i + L > P) continue;        // before anything is read: cells behind P are stale
+                    // eight cells per round, their loads independent of one another: a chain of L dependent 2-byte loads
+                    // was 15 times the junction profile's time on the bench batch (profiles/r20_notes.md)
+                    bool same = true;
+                    for (int q = 2; q < L && same; q += kFragCompare) {
+                        int diff = 0;
+#pragma unroll
+                        for (int t = 0; t < kFragCompare; t++)
+                            if (q + t < L) diff |= (int)cells[i + q + t] ^ frag_cell(fc, a, b, dir, q + t);
+                        same = diff == 0;
+                    }
+                    if (same) match(j, i, L);
+                }
+            }
+            prev = cur;
+        }
+    }
+}
+
 // cells: the unit's path (local signed ids), P > 0 cells, readable up to the next multiple of four cells; fc / foff: the unit's F
 // fragments (foff: F + 1 offsets into fc); T: group memory; out_fwd / out_rev / out_first: F values each; out: every field but
 // `status`.  Whole group.
@@ -137,52 +198,9 @@ AMBI_HD void stage_frag_profile(const G& g, const rcell_t* cells, int P, const r
     const int NP = 2 * F;
     for (int w0 = 0; w0 < NP; w0 += T.pwin) {
         const int wn = NP - w0 < T.pwin ? NP - w0 : T.pwin;
-        // the window's patterns
-        for (int s = tid; s < T.slots; s += sz) { T.key[s] = 0; T.head[s] = -1; }
-        for (int j = tid; j < wn; j += sz) { T.next[j] = -1; T.cnt[j] = 0; T.first[j] = kNone; }
-        g.sync();
-        bool mine_any = false;
-        for (int j = tid; j < wn; j += sz) {
-            const int p = w0 + j, f = p >> 1, dir = p & 1;
-            const int a = foff[f], b = foff[f + 1], L = b - a;
-            if (L < 2 || L > P) continue;                       // (no occurrence is possible)
-            if (dir && frag_palindrome(fc, a, b)) continue;     // rc(f) == f: counted once, as f
-            if (frag_insert(T, junc_key(frag_cell(fc, a, b, dir, 0), frag_cell(fc, a, b, dir, 1)), j)) mine_any = true;
-        }
-        // (any: a barrier; the table is complete behind it)  A window without a live pattern needs no sweep.
-        if (g.any(mine_any)) {
-            for (int base = 0; base < P; base += sz * kProfileChunk) {
-                const int s = base + tid * kProfileChunk;
-                if (s >= P) continue;
-                rcell_t c[kProfileChunk];
-                int prev;
-                const int e = path_load_chunk(cells, P, vec, s, c, prev);
-                for (int k = 0; k < e; k++) {
-                    const int cur = c[k];
-                    if (s + k > 0) {
-                        const int i = s + k - 1;            // the step (c[i], c[i + 1])
-                        const int slot = lds_find(T.key, T.slots, junc_key(prev, cur));
-                        for (int j = slot >= 0 ? T.head[slot] : -1; j >= 0; j = T.next[j]) {
-                            const int p = w0 + j, dir = p & 1;
-                            const int a = foff[p >> 1], b = foff[(p >> 1) + 1], L = b - a;
-                            if (i + L > P) continue;        // before anything is read: cells behind P are stale
-                            // eight cells per round, their loads independent of one another: a chain of L dependent 2-byte loads
-                            // was 15 times the junction profile's time on the bench batch (profiles/r20_notes.md)
-                            bool same = true;
-                            for (int q = 2; q < L && same; q += kFragCompare) {
-                                int diff = 0;
-#pragma unroll
-                                for (int t = 0; t < kFragCompare; t++)
-                                    if (q + t < L) diff |= (int)cells[i + q + t] ^ frag_cell(fc, a, b, dir, q + t);
-                                same = diff == 0;
-                            }
-                            if (same) { atomic_add_i32(T.cnt + j, 1); atomic_min_i32(T.first + j, i); }
-                        }
-                    }
-                    prev = cur;
-                }
-            }
-        }
+        // a match is a group-memory add on the pattern's count and a group-memory min on its first position
+        if (frag_window_build(g, P, fc, foff, w0, wn, T))
+            frag_window_sweep(g, cells, P, vec, fc, foff, w0, T, [cnt = T.cnt, first = T.first](int j, int i, int) { atomic_add_i32(cnt + j, 1); atomic_min_i32(first + j, i); });
         g.sync();
         // the window's counts to the block: fragment f by thread f mod size, in every window
         const int flo = w0 >> 1, fhi = (w0 + wn - 1) >> 1;

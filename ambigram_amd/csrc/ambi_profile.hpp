@@ -44,7 +44,7 @@ struct UnitProfile {
 };
 static_assert(sizeof(UnitProfile) == 40, "UnitProfile is ambi_unit_profile_t");
 
-// ---- what the three on-request profiles (this one, ambi_junc_profile.hpp, ambi_frag_profile.hpp) share ----
+// ---- what the on-request profiles (this one, ambi_junc_profile.hpp, ambi_frag_profile.hpp, ambi_evidence_profile.hpp) share ----
 // The window rule: the largest unit of the batch, capped, and what a test asks for can only shrink it.
 AMBI_HD int capped_window(int max, int cap, int asked) {
     int w = max < 1 ? 1 : max;

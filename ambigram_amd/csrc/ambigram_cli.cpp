@@ -261,6 +261,12 @@ int run_sc_bfb(Args& A) {
 // sample, chromosome index (-1 for a fragment of fewer than two cells or one that spans chromosomes, which belongs to no unit:
 // 0 0 -1), fragment index, cells, occurrences, occurrences of the reverse complement, first position -- comes from the device's
 // fragment support profile of the final paths (ambi_batch_frag_profile); stdout and the side files are unchanged.
+// --evidence_profile <file> / --evidence_depth <file> (which parts of the printed path are backed by the fragments, and which junction
+// traversals are not?): the fragment file as for --frag_profile; after the run the device's evidence depth profile of the final paths
+// (ambi_batch_evidence_profile) gives one tab-separated row per junction in file order -- sample, chromosome index (-1 for a junction
+// between chromosomes: 0 0 -1), junction index, count in the final path, those of them under at least one fragment occurrence, the
+// smallest depth over them or -1 -- and the depth of every final path in run-length form -- sample, chromosome index, first step,
+// steps, depth --; stdout and the side files are unchanged.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -292,6 +298,10 @@ int run_bfb(Args& A) {
     const std::string frag_profile = A.kv.count("frag_profile") ? A.kv["frag_profile"] : "";
     const std::string frags = A.kv.count("frags") ? A.kv["frags"] : juncs;
     if (!frag_profile.empty() && frags.empty()) { std::cerr << "--frag_profile needs a fragment file: --frags <file> or --juncdb <file>" << std::endl; return 2; }
+    const std::string evidence_profile = A.kv.count("evidence_profile") ? A.kv["evidence_profile"] : "";
+    const std::string evidence_depth = A.kv.count("evidence_depth") ? A.kv["evidence_depth"] : "";
+    const std::string evidence_opt = !evidence_profile.empty() ? "--evidence_profile" : !evidence_depth.empty() ? "--evidence_depth" : "";
+    if (!evidence_opt.empty() && frags.empty()) { std::cerr << evidence_opt << " needs a fragment file: --frags <file> or --juncdb <file>" << std::endl; return 2; }
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
     const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
@@ -348,6 +358,14 @@ int run_bfb(Args& A) {
                 return 2;
             }
             if ((rc = ambi_graph_read_fragments(g, frags.c_str())) != 0) return die("--frags " + frags + ": " + ambi_error_string(rc));
+        }
+        if (!evidence_opt.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << evidence_opt << ": " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
+                return 2;
+            }
+            if (frag_profile.empty() && (rc = ambi_graph_read_fragments(g, frags.c_str())) != 0) return die("--frags " + frags + ": " + ambi_error_string(rc));
         }
         if (!out_fasta.empty()) {
             ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
@@ -499,6 +517,44 @@ int run_bfb(Args& A) {
                 fprintf(pf, "%s\t%d\t%d\t%lld\t%d\t%d\t%d\n", S.lh.c_str(), chr_of[f], f, (long long)(off[f + 1] - off[f]), fwd[f], rev[f], first[f]);
         }
         fclose(pf);
+    }
+    if (!evidence_opt.empty()) {
+        if ((rc = ambi_batch_evidence_profile(b, 1, nullptr)) != 0 || (rc = ambi_batch_evidence_profile_wait(b)) != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+        if (!evidence_profile.empty()) {
+            FILE* pf = fopen(evidence_profile.c_str(), "w");
+            if (!pf) return die("Cannot open file " + evidence_profile);
+            for (Sample& S : samples) {
+                const int m = S.n_junc;
+                std::vector<int32_t> count(m, 0), covered(m, 0), min_depth(m, -1), chr_of(m, -1);
+                for (int c = 0; c < S.n_chr; c++) {
+                    const int mu = ambi_batch_unit_evidence_juncs(b, S.unit[c], nullptr, nullptr, nullptr, nullptr, INT32_MAX);
+                    if (mu < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(mu)); }
+                    std::vector<int32_t> cnt(mu), cov(mu), mind(mu), idx(mu);
+                    if ((rc = ambi_batch_unit_evidence_juncs(b, S.unit[c], cnt.data(), cov.data(), mind.data(), idx.data(), mu)) < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                    for (int j = 0; j < mu; j++) if (idx[j] >= 0 && idx[j] < m) { count[idx[j]] = cnt[j]; covered[idx[j]] = cov[j]; min_depth[idx[j]] = mind[j]; chr_of[idx[j]] = c; }
+                }
+                for (int j = 0; j < m; j++) fprintf(pf, "%s\t%d\t%d\t%d\t%d\t%d\n", S.lh.c_str(), chr_of[j], j, count[j], covered[j], min_depth[j]);
+            }
+            fclose(pf);
+        }
+        if (!evidence_depth.empty()) {
+            FILE* pf = fopen(evidence_depth.c_str(), "w");
+            if (!pf) return die("Cannot open file " + evidence_depth);
+            for (Sample& S : samples)
+                for (int c = 0; c < S.n_chr; c++) {
+                    ambi_unit_evidence_profile_t e;
+                    if ((rc = ambi_batch_unit_evidence_profile(b, S.unit[c], &e)) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                    std::vector<int32_t> depth((size_t)e.steps);
+                    if ((rc = ambi_batch_unit_evidence_depth(b, S.unit[c], 0, e.steps, depth.data())) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                    for (int k = 0; k < e.steps;) {
+                        int q = k + 1;
+                        while (q < e.steps && depth[q] == depth[k]) q++;
+                        fprintf(pf, "%s\t%d\t%d\t%d\t%d\n", S.lh.c_str(), c, k, q - k, depth[k]);
+                        k = q;
+                    }
+                }
+            fclose(pf);
+        }
     }
     if (!out_fasta.empty()) {
         FILE* ff = fopen(out_fasta.c_str(), "w");
@@ -687,7 +743,7 @@ int main(int argc, char** argv) {
     if (A.help) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
-                     "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--evidence_profile <file>] [--evidence_depth <file>] [--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
@@ -697,7 +753,12 @@ int main(int argc, char** argv) {
                      "  --frag_profile <file> (--op bfb): one tab-separated row per fragment (line of the fragment file read as one signed chain) after the run, "
                      "in file order: sample, chromosome index (-1: no unit), fragment index, cells, occurrences in the final path, occurrences of the reverse "
                      "complement, first position or -1 (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
-                     "  --frags <file>: the fragment file of --frag_profile (default: the file of --juncdb)\n"
+                     "  --frags <file>: the fragment file of --frag_profile, --evidence_profile and --evidence_depth (default: the file of --juncdb)\n"
+                     "  --evidence_profile <file> (--op bfb): one tab-separated row per junction after the run, in file order: sample, chromosome index (-1 between "
+                     "chromosomes), junction index, count in the final path, those of them under at least one fragment occurrence, smallest fragment depth "
+                     "over them or -1 (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --evidence_depth <file> (--op bfb): the number of fragment occurrences over every step of the final paths in run-length form: sample, "
+                     "chromosome index, first step, steps, depth (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
                      "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
                      "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
                      "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";

@@ -60,7 +60,7 @@ extern "C" {
 #define AMBI_ERR_HIP (-31)
 #define AMBI_ERR_STATE (-32)      /* call order violated (e.g. run before upload) */
 #define AMBI_ERR_ARG (-33)
-#define AMBI_ERR_TOO_LARGE (-34)  /* ambi_batch_sequence: the unit range's sequences exceed max_bytes */
+#define AMBI_ERR_TOO_LARGE (-34)  /* ambi_batch_sequence: the unit range's sequences exceed max_bytes; ambi_batch_evidence_profile: a depth bound of 2^31 */
 /* ambi_graph_read_fasta */
 #define AMBI_ERR_FASTA_OPEN (-40)   /* cannot open the FASTA file */
 #define AMBI_ERR_FASTA_CHROM (-41)  /* a segment's chromosome is not a record of the file */
@@ -419,6 +419,60 @@ int ambi_batch_unit_frag_support(const ambi_batch_t* b, int32_t unit, int32_t* f
  * unit fwd int32[F], rev int32[F] and first int32[F], each array padded to 16 bytes.  Valid after ambi_batch_frag_profile_wait until
  * the next ambi_batch_frag_profile; not available for a sharded batch. */
 int ambi_batch_frag_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+
+/* The evidence depth profile of every unit's path, computed ON THE DEVICE (ambi_evidence_mark_kernel, ambi_evidence_scan_kernel):
+ * how many occurrences of the unit's fragments lie over every step of the path, and which junction traversals none spans.  With
+ * the path cells c[0..P) that ambi_batch_unit_path(unit, which) returns (as local ids), the fragments and their occurrences as for
+ * ambi_batch_frag_profile and the junctions j = 0..m-1 with the crediting rule of ambi_batch_junc_profile:
+ *   step k = (c[k], c[k+1]), k = 0 .. P-2; an occurrence at i of a pattern of L cells covers the steps i .. i+L-2;
+ *   depth[k] = occurrences, over all fragments and both directions, that cover step k;
+ *   count[j] = steps credited to junction j (the junction profile's count), covered[j] = those of them with depth > 0,
+ *   min_depth[j] = the minimum of depth over them, -1 when count[j] == 0.
+ * All fields are exact integers.  depth is int32 and at most 2 * (fragment cells - F) of the unit; a request is refused with
+ * AMBI_ERR_TOO_LARGE when that bound reaches 2^31 for some unit.  The depths stay on the device (4 bytes per cell of every unit's
+ * path capacity); per unit 3 m int32 travel to the host. */
+typedef struct {
+    int32_t status;                /* the unit's status (ambi_unit_result_t::status) */
+    int32_t steps;                 /* P - 1; a unit with a negative status or without a path has every field but status and juncs zero
+                                      and first_uncovered = longest_uncovered_at = -1 */
+    int32_t steps_covered;         /* steps with depth > 0 */
+    int32_t max_depth;             /* max over the steps of depth */
+    int32_t first_uncovered;       /* smallest k with depth[k] == 0, -1 if none */
+    int32_t longest_uncovered;     /* steps of the longest stretch of consecutive steps with depth 0 */
+    int32_t longest_uncovered_at;  /* the smallest start of such a stretch, -1 if none */
+    int32_t juncs;                 /* m */
+    int32_t juncs_used;            /* junctions with count > 0 */
+    int32_t juncs_covered;         /* junctions with count > 0 and covered == count */
+    int32_t juncs_uncovered;       /* junctions with count > 0 and covered == 0 */
+    int32_t unmatched_covered;     /* steps credited to no junction that have depth > 0 */
+    int64_t depth_sum;             /* sum over the steps of depth */
+} ambi_unit_evidence_profile_t;
+/* Queues the evidence profile of the LAST run's results behind that run on hip_stream (which as for ambi_batch_profile): the
+ * fragments go up first when the device does not hold this version of them, then the two kernels, then one device-to-host copy
+ * of the block on the engine's copy stream: hip_stream is not blocked.  A batch without any fragment is served: every depth is 0.
+ * AMBI_ERR_STATE before any run, AMBI_ERR_ARG for another `which`, AMBI_ERR_TOO_LARGE as above (nothing is queued then, and an
+ * earlier evidence profile of this run is no longer readable: the call clears it first).  After ambi_batch_run_sharded the
+ * call goes to every share, on the share's own stream. */
+int ambi_batch_evidence_profile(ambi_batch_t* b, int32_t which, void* hip_stream);
+/* Blocks until the evidence profile is in host memory.  Makes the run's results final first (ambi_batch_wait) and profiles once
+ * more if that changed them after the request was queued. */
+int ambi_batch_evidence_profile_wait(ambi_batch_t* b);
+/* A unit's summary; AMBI_ERR_STATE without a waited-for evidence profile of the last run. */
+int ambi_batch_unit_evidence_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_evidence_profile_t* out);
+/* A unit's values per junction: count, covered and min_depth as above, graph_index[j] = the junction's index in the graph's list
+ * (j itself for a raw unit).  Any pointer may be NULL.  Returns m; AMBI_ERR_ARG when cap < m. */
+int ambi_batch_unit_evidence_juncs(const ambi_batch_t* b, int32_t unit, int32_t* count, int32_t* covered, int32_t* min_depth, int32_t* graph_index, int32_t cap);
+/* The depths of the steps [first, first + n) of a unit to host memory; nothing else is downloaded.  AMBI_ERR_ARG for a range
+ * outside [0, P-1] (a unit without a step takes n = 0 only). */
+int ambi_batch_unit_evidence_depth(ambi_batch_t* b, int32_t unit, int64_t first, int64_t n, int32_t* out);
+/* The evidence profile block in DEVICE memory, for collectives: [ambi_unit_evidence_profile_t[n_units]] padded to 16 bytes, then
+ * per unit count int32[m], covered int32[m] and min_depth int32[m], each array padded to 16 bytes.  Valid after
+ * ambi_batch_evidence_profile_wait until the next ambi_batch_evidence_profile; not available for a sharded batch. */
+int ambi_batch_evidence_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+/* The depth area in DEVICE memory: unit u's depths are int32[steps] at byte unit_off[u] (a multiple of 16; cap >= n_units entries,
+ * or NULL), the slice of a unit without a path holds nothing of meaning.  Valid as the block above; not available for a sharded
+ * batch. */
+int ambi_batch_evidence_depth_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap);
 
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
