@@ -55,6 +55,21 @@ class UnitEvidenceProfile(C.Structure):     # ambi_unit_evidence_profile_t
                                          "unmatched_covered")] + [("depth_sum", C.c_int64)]
 
 
+class UnitFoldProfile(C.Structure):     # ambi_unit_fold_profile_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "steps", "folds", "folds_perfect", "folds_gapped", "folds_open", "folds_unmatched",
+                                         "max_arm", "max_arm_at", "max_cover", "max_cover_at", "steps_covered")] + [("arm_sum", C.c_int64)]
+
+
+def fold_arm(v):
+    """AMBI_FOLD_ARM of an entry of the fold plane (int or array)."""
+    return v & 0xffffff
+
+
+def fold_align(v):
+    """AMBI_FOLD_ALIGN of a non-zero entry of the fold plane (int or array): -1 (no arm), 0 (perfect), 1..4."""
+    return (v >> 24) - 2
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -146,6 +161,13 @@ def _declare(L):
         "ambi_batch_unit_evidence_depth": (C.c_int, [vp, i32, i64, i64, pi32]),
         "ambi_batch_evidence_profile_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_batch_evidence_depth_device": (C.c_int, [vp, _P(vp), pi64, pi64, i32]),
+        "ambi_batch_fold_profile": (C.c_int, [vp, i32, vp]),
+        "ambi_batch_fold_profile_wait": (C.c_int, [vp]),
+        "ambi_batch_unit_fold_profile": (C.c_int, [vp, i32, _P(UnitFoldProfile)]),
+        "ambi_batch_unit_fold_juncs": (C.c_int, [vp, i32, pi32, pi32, pi32, i32]),
+        "ambi_batch_unit_fold_plane": (C.c_int, [vp, i32, i32, i64, i64, pi32]),
+        "ambi_batch_fold_profile_device": (C.c_int, [vp, _P(vp), pi64]),
+        "ambi_batch_fold_planes_device": (C.c_int, [vp, _P(vp), pi64, pi64, i32]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
         "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
         "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
@@ -722,6 +744,54 @@ class Batch:
         p, n = C.c_void_p(), C.c_int64()
         off = np.zeros(U, np.int64)
         self._ck(self.lib.ambi_batch_evidence_depth_device(self.h, C.byref(p), C.byref(n), off.ctypes.data_as(_P(C.c_int64)), U), "evidence_depth_device")
+        return p.value or 0, n.value, off
+
+    def fold_profile(self, which=1, stream=None):
+        """Queues the fold-back arm profile of the last run's paths behind that run (ambi_batch_fold_profile): per fold of a unit's
+        path (which: 0 getBFB's, 1 the final one) its alignment and palindrome arm, per step the folds whose span covers it, per
+        junction its folds and their longest arm; `stream` is not blocked."""
+        self._ck(self.lib.ambi_batch_fold_profile(self.h, which, C.c_void_p(stream or 0)), "fold_profile")
+
+    def fold_profile_wait(self):
+        """Waits for the fold profile in host memory (the run's results are final first); unit_fold_profile / unit_fold_juncs /
+        unit_fold_plane answer afterwards."""
+        self._ck(self.lib.ambi_batch_fold_profile_wait(self.h), "fold_profile_wait")
+
+    def unit_fold_profile(self, u):
+        r = UnitFoldProfile()
+        self._ck(self.lib.ambi_batch_unit_fold_profile(self.h, u, C.byref(r)), "unit_fold_profile")
+        return {k: getattr(r, k) for k, _ in UnitFoldProfile._fields_}
+
+    def unit_fold_juncs(self, u):
+        """(folds, max_arm, graph_index): int32 arrays over the unit's junctions -- folds credited to the junction, the longest arm
+        among them (0: none), and the junction's index in Graph.junctions() (its own for a unit added with add_unit)."""
+        m = self._ck(self.lib.ambi_batch_unit_fold_juncs(self.h, u, None, None, None, 1 << 30), "unit_fold_juncs")
+        out = [np.zeros(m, np.int32) for _ in range(3)]
+        self._ck(self.lib.ambi_batch_unit_fold_juncs(self.h, u, *[a.ctypes.data_as(_P(C.c_int32)) for a in out], m), "unit_fold_juncs")
+        return tuple(out)
+
+    def unit_fold_plane(self, u, plane, first=0, n=None):
+        """int32 entries [first, first + n) of a unit's plane (0: fold, see fold_arm / fold_align; 1: cover; default: to the last
+        step); only this range is downloaded."""
+        if n is None:
+            n = self.unit_fold_profile(u)["steps"] - first
+        out = np.zeros(max(n, 0), np.int32)
+        self._ck(self.lib.ambi_batch_unit_fold_plane(self.h, u, plane, first, n, out.ctypes.data_as(_P(C.c_int32))), "unit_fold_plane")
+        return out
+
+    def fold_profile_device(self):
+        """(address, bytes) of the fold profile block in device memory (ambi_batch_fold_profile_device), for collectives."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._ck(self.lib.ambi_batch_fold_profile_device(self.h, C.byref(p), C.byref(n)), "fold_profile_device")
+        return p.value or 0, n.value
+
+    def fold_planes_device(self):
+        """(address, bytes, unit_off) of both planes in device memory (ambi_batch_fold_planes_device): plane p of unit u is
+        int32[steps] at byte p * (bytes // 2) + unit_off[u]."""
+        U = self.size()
+        p, n = C.c_void_p(), C.c_int64()
+        off = np.zeros(U, np.int64)
+        self._ck(self.lib.ambi_batch_fold_planes_device(self.h, C.byref(p), C.byref(n), off.ctypes.data_as(_P(C.c_int64)), U), "fold_planes_device")
         return p.value or 0, n.value, off
 
     def set_unit_sequences(self, u, bases, seg_off):

@@ -8,6 +8,7 @@
 
 #include "ambi_pack.hpp"
 #include "ambi_evidence_profile.hpp"
+#include "ambi_fold_profile.hpp"
 #include "ambi_frag_profile.hpp"
 #include "ambi_junc_profile.hpp"
 #include "ambi_profile.hpp"
@@ -87,17 +88,19 @@ class Backend {
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
 
     // ---- on-request profiles of every unit's path (which: 0 getBFB, 1 after indelBFB) ----
-    // Four kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand), the
+    // Five kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand), the
     // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts), the fragment support profile
-    // (ambi_frag_profile.hpp: occurrences of every .juncs fragment in either direction) and the evidence depth profile
-    // (ambi_evidence_profile.hpp: fragment occurrences over every step, per junction its covered traversals), each a block
-    // [summary[U]][per unit counts]; the evidence kind has a depth area beside its block that stays where it was computed.
+    // (ambi_frag_profile.hpp: occurrences of every .juncs fragment in either direction), the evidence depth profile
+    // (ambi_evidence_profile.hpp: fragment occurrences over every step, per junction its covered traversals) and the fold-back arm
+    // profile (ambi_fold_profile.hpp: the palindrome arm of every fold, how the arms nest, per junction its folds), each a block
+    // [summary[U]][per unit counts]; the evidence kind has a depth area and the fold kind two planes beside the block that stay where
+    // they were computed.
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
     // simulation); the HIP engine overrides the virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3 };
-    static constexpr int kProfileKinds = 4;
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4 };
+    static constexpr int kProfileKinds = 5;
     void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
     virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
@@ -107,7 +110,8 @@ class Backend {
         ProfileState& P = prof_[kind];
         profile_layout(kind);
         P.blob.assign((size_t)P.bytes, 0);
-        if (kind == kEvidence) host_evidence_profile(blob.data(), which, P);
+        if (kind == kFold) host_fold_profile(blob.data(), which, P);
+        else if (kind == kEvidence) host_evidence_profile(blob.data(), which, P);
         else if (kind == kFragment) host_frag_profile(blob.data(), which, P);
         else if (kind == kJunction) host_junc_profile(blob.data(), which, P);
         else host_profile(blob.data(), which, P);
@@ -210,6 +214,37 @@ class Backend {
         return evidence_depth_offsets(bytes, unit_off, cap);
     }
 
+    int fold_summary(int unit, UnitFoldProfile* out) const {
+        const ProfileState& P = prof_[kFold];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitFoldProfile*>(P.view)[unit];
+        return 0;
+    }
+    int fold_counts(int unit, int32_t* folds, int32_t* max_arm, int cap) const {   // m values each; returns m
+        const ProfileState& P = prof_[kFold];
+        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
+        const int m = prof_hb_->units[(size_t)unit].n_junc;
+        if (cap < m) return ST_ERR_BAD_INPUT;
+        const uint8_t* p = P.view + P.off[(size_t)unit];
+        if (folds && m > 0) memcpy(folds, p, sizeof(int32_t) * (size_t)m);
+        if (max_arm && m > 0) memcpy(max_arm, p + fold_arr_bytes(m), sizeof(int32_t) * (size_t)m);
+        return m;
+    }
+    // the entries [first, first + n) of a unit's plane (0: fold, 1: cover) to host memory (nothing else of the plane area travels),
+    // and the area where it was computed (device memory of the HIP engine: both planes, `bytes` in all, plane p of unit u at
+    // p * bytes / 2 + unit_off[u]); valid after profile_wait(kFold)
+    virtual int fold_plane_copy(int unit, int plane, int64_t first, int64_t n, int32_t* out) {
+        const ProfileState& P = prof_[kFold];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || plane < 0 || plane > 1 || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) memcpy(out, reinterpret_cast<const uint8_t*>(planes_.data()) + plane * plane_bytes_ + plane_off_[(size_t)unit] + 4 * first, (size_t)(4 * n));
+        return 0;
+    }
+    virtual int fold_planes_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) {
+        if (!prof_[kFold].view) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = planes_.data();
+        return fold_plane_offsets(bytes, unit_off, cap);
+    }
+
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
     // sequence() runs pass 0 of the extents stage behind the last run and fetches its totals (count x {bytes, runs}: the one small
     // device-to-host trip of a request), sizes the extent arrays and the output block from them, and queues pass 1 and the fill
@@ -288,7 +323,8 @@ class Backend {
     ProfileState prof_[kProfileKinds];   // [ProfileKind]
     void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
         ProfileState& P = prof_[kind];
-        if (kind == kEvidence) { P.bytes = evidence_block_layout(prof_hb_->units, P.off); depth_bytes_ = evidence_depth_layout(prof_hb_->units, depth_off_); }
+        if (kind == kFold) { P.bytes = fold_block_layout(prof_hb_->units, P.off); plane_bytes_ = fold_plane_layout(prof_hb_->units, plane_off_); }
+        else if (kind == kEvidence) { P.bytes = evidence_block_layout(prof_hb_->units, P.off); depth_bytes_ = evidence_depth_layout(prof_hb_->units, depth_off_); }
         else if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
         else P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
     }
@@ -315,6 +351,20 @@ class Backend {
         if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
         if (bytes) *bytes = depth_bytes_;
         if (unit_off) for (int u = 0; u < U; u++) unit_off[u] = depth_off_[(size_t)u];
+        return 0;
+    }
+    void fold_windows(int* fwin, int* jwin, int* slots) const {   // folds per round, junctions per pass and table slots of the fold stages
+        *fwin = fold_window(env_int("AMBI_FOLD_WINDOW"));
+        *jwin = fold_junc_window(prof_hb_->max_m, env_int("AMBI_JPROFILE_JUNC_WINDOW"));
+        *slots = junc_slots(*jwin);
+    }
+    std::vector<int64_t> plane_off_;     // the fold kind's planes: every unit's byte offset in a plane and ONE plane's size (profile_layout)
+    int64_t plane_bytes_ = 0;
+    int fold_plane_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
+        const int U = (int)plane_off_.size();
+        if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
+        if (bytes) *bytes = 2 * plane_bytes_;
+        if (unit_off) for (int u = 0; u < U; u++) unit_off[u] = plane_off_[(size_t)u];
         return 0;
     }
     int sequence_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
@@ -375,7 +425,22 @@ class Backend {
         for (size_t u = 0; u < units.size(); u++)
             evidence_scan_unit(g, units.data(), prof_hb_->junc_ends.data(), blob, (int)u, which, jwin, E, area, depth_off_.data(), P.blob.data(), P.off.data());
     }
+    void host_fold_profile(const uint8_t* blob, int which, ProfileState& P) {
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        int fwin, jwin, slots;
+        fold_windows(&fwin, &jwin, &slots);
+        std::vector<int32_t> lds((size_t)(fold_arm_lds_bytes(fwin) / 4)), lds2((size_t)(fold_scan_lds_bytes(slots) / 4));
+        const FoldList L = fold_list(lds.data(), fwin);
+        const FoldTable T = fold_table(lds2.data(), slots);
+        planes_.resize((size_t)(2 * plane_bytes_ / 16) + 1);   // (kept between requests as the device keeps its area: stale values behind it)
+        uint8_t* area = reinterpret_cast<uint8_t*>(planes_.data());
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++) fold_arms_unit(g, units.data(), blob, (int)u, which, L, area, plane_bytes_, plane_off_.data());
+        for (size_t u = 0; u < units.size(); u++)
+            fold_scan_unit(g, units.data(), prof_hb_->junc_ends.data(), blob, (int)u, which, jwin, T, area, plane_bytes_, plane_off_.data(), P.blob.data(), P.off.data());
+    }
     std::vector<Seq16A> depth_;          // the default implementation's depth area (16-byte aligned)
+    std::vector<Seq16A> planes_;         // the default implementation's fold and cover planes (16-byte aligned)
     std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };
 

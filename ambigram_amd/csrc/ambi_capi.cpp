@@ -115,7 +115,7 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled[Backend::kProfileKinds] = {false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
@@ -834,6 +834,51 @@ int ambi_batch_unit_evidence_depth(ambi_batch_t* b, int32_t unit, int64_t first,
     if (be->evidence_summary(local, &s)) return AMBI_ERR_STATE;
     if (first < 0 || n < 0 || first > s.steps || n > s.steps - first || (n > 0 && !out)) return AMBI_ERR_ARG;
     return be->evidence_depth_copy(local, first, n, out) ? AMBI_ERR_STATE : 0;
+}
+// ---- fold-back arm profile of the paths (ambi_fold_profile.hpp; junctions as the junction profile's) ----
+int ambi_batch_fold_profile(ambi_batch_t* b, int32_t which, void* hip_stream) { return profile_start(b, Backend::kFold, which, hip_stream); }
+int ambi_batch_fold_profile_wait(ambi_batch_t* b) { return profile_wait(b, Backend::kFold); }
+int ambi_batch_fold_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) { return profile_device(b, Backend::kFold, dev_ptr, bytes); }
+int ambi_batch_fold_planes_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kFold] || b->sharded_ready) return AMBI_ERR_STATE;   // (one area per share: no single device view)
+    if (unit_off && cap < (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    return b->be->fold_planes_device(dev_ptr, bytes, unit_off, cap) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_unit_fold_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_fold_profile_t* out) {
+    if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kFold]) return AMBI_ERR_STATE;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    static_assert(sizeof(ambi_unit_fold_profile_t) == sizeof(UnitFoldProfile), "ambi_unit_fold_profile_t is ambi::UnitFoldProfile");
+    static_assert(sizeof(ambi_unit_fold_profile_t) == 56, "the fold summary is 56 bytes");
+    static_assert(AMBI_FOLD_ARM(0x0200002a) == 42 && AMBI_FOLD_ALIGN(0x0200002a) == 0 && AMBI_FOLD_ALIGN(0x01000000) == -1, "fold_pack of ambi_fold_profile.hpp");
+    return be->fold_summary(local, reinterpret_cast<UnitFoldProfile*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_unit_fold_juncs(const ambi_batch_t* b, int32_t unit, int32_t* folds, int32_t* max_arm, int32_t* graph_index, int32_t cap) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kFold]) return AMBI_ERR_STATE;
+    const int m = b->hb.units[unit].n_junc;
+    if (cap < m) return AMBI_ERR_ARG;
+    int local = unit;
+    const Backend* be = b->owner(unit, &local);
+    const int rc = be->fold_counts(local, folds, max_arm, cap);
+    if (rc < 0) return AMBI_ERR_STATE;
+    if (graph_index) {
+        const std::vector<int32_t>& map = b->hb.junc_global[unit];   // (empty for a raw unit)
+        for (int j = 0; j < m; j++) graph_index[j] = j < (int)map.size() ? map[j] : j;
+    }
+    return rc;
+}
+int ambi_batch_unit_fold_plane(ambi_batch_t* b, int32_t unit, int32_t plane, int64_t first, int64_t n, int32_t* out) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size() || plane < 0 || plane > 1) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kFold]) return AMBI_ERR_STATE;
+    int local = unit;
+    Backend* be = b->owner(unit, &local);
+    UnitFoldProfile s;
+    if (be->fold_summary(local, &s)) return AMBI_ERR_STATE;
+    if (first < 0 || n < 0 || first > s.steps || n > s.steps - first || (n > 0 && !out)) return AMBI_ERR_ARG;
+    return be->fold_plane_copy(local, plane, first, n, out) ? AMBI_ERR_STATE : 0;
 }
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
 int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {

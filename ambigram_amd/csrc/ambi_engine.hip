@@ -27,6 +27,11 @@
 //                                                  unit's depth area (ambi_evidence_profile.hpp)   <- the same cells, device-memory atomics
 //   ambi_evidence_scan_kernel     1 block / unit   on request, behind the mark kernel: depth per step by a scan in place, summary,
 //                                                  per junction covered traversals                 <- 4 bytes / step + the cells per pass
+//   ambi_fold_arm_kernel          1 block / unit   on request: the folds of the path and the palindrome arm around each, short arms per
+//                                                  lane, long ones by whole wavefronts; fold plane and the spans' ends into the cover
+//                                                  plane (ambi_fold_profile.hpp)                   <- the same cells, 2 atomics / fold
+//   ambi_fold_scan_kernel         1 block / unit   on request, behind the arm kernel: cover per step by a scan in place, summary, per
+//                                                  junction its folds and longest arm              <- 8 bytes / step
 //                                                  (the profile kernels share unit prologue, chunked cell read and window rule --
 //                                                  profile_path, path_load_chunk, capped_window of ambi_profile.hpp -- and the two tables
 //                                                  their probe, lds_find / lds_claim of ambi_junc_profile.hpp; every reader of a unit's
@@ -650,6 +655,27 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_evidence_scan_kernel(Bat
         __syncthreads();
     }
 }
+// ---- fold-back arm profile of the paths (ambi_fold_profile.hpp; launched by HipBackend::profile_queue only) ----
+// Two launches as for the evidence kind and for its reason: the arm kernel posts the spans' ends into the cover plane with
+// device-memory atomics, the scan kernel reads the plane with plain loads behind the kernel boundary.  Group memory: 256 bytes for
+// the group's reductions, then the list of `fwin` folds (step, packed value: 8 bytes each) in the arm kernel or the junction table of
+// `slots` slots (key, lowest index, folds, longest arm: 16 bytes each) in the scan kernel.
+__global__ __launch_bounds__(kProfileThreads) void ambi_fold_arm_kernel(BatchArgs A, int which, int fwin, uint8_t* planes, int64_t plane_bytes, const int64_t* plane_off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    const FoldList L = fold_list(ambi_lds + kProfileScratchBytes, fwin);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        fold_arms_unit(g, A.units, A.results, u, which, L, planes, plane_bytes, plane_off);
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(kProfileThreads) void ambi_fold_scan_kernel(BatchArgs A, int which, int jwin, int slots, uint8_t* planes, int64_t plane_bytes, const int64_t* plane_off, uint8_t* block, const int64_t* off) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    const FoldTable T = fold_table(ambi_lds + kProfileScratchBytes, slots);
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        fold_scan_unit(g, A.units, A.junc_ends, A.results, u, which, jwin, T, planes, plane_bytes, plane_off, block, off);
+        __syncthreads();
+    }
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -789,10 +815,13 @@ struct Lease {
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
     // [Backend::ProfileKind] copy-number profile [UnitProfile[U]][per unit fwd, rev], junction usage profile [UnitJuncProfile[U]][per unit count],
     // fragment support profile [UnitFragProfile[U]][per unit fwd, rev, first], evidence depth profile [UnitEvidenceProfile[U]][per unit
-    // count, covered, min_depth]
+    // count, covered, min_depth], fold-back arm profile [UnitFoldProfile[U]][per unit folds, max_arm]
     RequestBlock prof[Backend::kProfileKinds];
     // the evidence kind's depth area: int32 per cell of every unit's path capacity; it never travels to the host as a whole
     uint8_t* d_depth = nullptr; int64_t d_depth_bytes = 0;
+    // the fold kind's planes: the fold plane of every unit, then the cover plane, int32 per cell of path capacity each; allocated at
+    // the first request of the kind
+    uint8_t* d_planes = nullptr; int64_t d_planes_bytes = 0;
     // the batch's fragment image (HipBackend::fragment_image) [cells][frag_off][cell_off][pref_off][n_frag], its pinned twin and the
     // event behind its last upload (the host writes the twin again only behind it)
     uint8_t* d_frag_img = nullptr; int64_t d_frag_img_bytes = 0;
@@ -1160,6 +1189,7 @@ class HipBackend : public Backend {
             }
             for (RequestBlock& B : L->prof) B.trim(kKeepProfile);
             if (L->d_depth_bytes > kKeepCells) { (void)hipFree(L->d_depth); L->d_depth = nullptr; L->d_depth_bytes = 0; }
+            if (L->d_planes_bytes > kKeepCells) { (void)hipFree(L->d_planes); L->d_planes = nullptr; L->d_planes_bytes = 0; }
             if (L->d_frag_img_bytes > kKeepProfile) { (void)hipFree(L->d_frag_img); L->d_frag_img = nullptr; L->d_frag_img_bytes = 0; }
             if (L->h_frag_bytes > kKeepProfile) { (void)hipHostFree(L->h_frag); L->h_frag = nullptr; L->h_frag_bytes = 0; }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
@@ -2190,7 +2220,7 @@ class HipBackend : public Backend {
         out->copied_bytes = words * 4 + (runs_hdr_[slot] ? U * (int64_t)sizeof(UnitOut) : 0);
         return 0;
     }
-    // ---- on-request results: the profiles (ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp, ambi_evidence_profile.hpp) and the sequences below ----
+    // ---- on-request results: the profiles (ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp, ambi_evidence_profile.hpp, ambi_fold_profile.hpp) and the sequences below ----
     // A request works on `stream` behind everything that writes the result blob in the last run: the caller's stream of that run,
     // which has waited for every side stream at the end of run(), and -- for a caller that asks on another stream -- explicitly the
     // events "results complete" of the side streams (lean / list finish kernels, direct edit + full launch) and of the express
@@ -2251,9 +2281,10 @@ class HipBackend : public Backend {
         }
         if (!R.laid_out) {
             profile_layout(kind);
-            const int64_t n_off = kind == kEvidence ? 2 * U : U;              // (the evidence kind: the depth area's offsets behind the block's)
+            const int64_t n_off = kind == kEvidence || kind == kFold ? 2 * U : U;   // (the evidence and fold kinds: the depth area's or the planes' offsets behind the block's)
             const int64_t total = P.bytes + n_off * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
             if (kind == kEvidence) { if (int rc = lease_device_block(&L->d_depth, &L->d_depth_bytes, depth_bytes_ > 0 ? depth_bytes_ : 16)) return rc; }
+            if (kind == kFold) { if (int rc = lease_device_block(&L->d_planes, &L->d_planes_bytes, plane_bytes_ > 0 ? 2 * plane_bytes_ : 16)) return rc; }
             if (int rc = lease_device_block(&B.d, &B.d_bytes, total)) return rc;
             if (int rc = lease_pinned_block(&B.h, nullptr, &B.h_bytes, total)) return rc;
             if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
@@ -2261,13 +2292,15 @@ class HipBackend : public Backend {
             // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
             memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
             if (kind == kEvidence) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), depth_off_.data(), (size_t)U * sizeof(int64_t));
+            if (kind == kFold) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), plane_off_.data(), (size_t)U * sizeof(int64_t));
             R.d_off = reinterpret_cast<int64_t*>(B.d + P.bytes);
             HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)n_off * sizeof(int64_t), hipMemcpyHostToDevice, s));
             R.laid_out = true;
         }
         if (int rc = behind_results(s, B.ev_src)) return rc;
-        int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes, fslots = 0, lds_mark = kProfileScratchBytes;
-        if (kind == kEvidence) {
+        int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes, fslots = 0, lds_mark = kProfileScratchBytes, fwin = 0;
+        if (kind == kFold) { fold_windows(&fwin, &jwin, &slots); lds_mark += (int)fold_arm_lds_bytes(fwin); lds += (int)fold_scan_lds_bytes(slots); }
+        else if (kind == kEvidence) {
             frag_profile_windows(&pwin, &fslots); lds_mark += (int)frag_profile_lds_bytes(fslots, pwin);
             evidence_windows(&jwin, &slots); lds += (int)evidence_scan_lds_bytes(slots, kProfileThreads);
         } else if (kind == kFragment) { frag_profile_windows(&pwin, &slots); lds += (int)frag_profile_lds_bytes(slots, pwin); }
@@ -2275,7 +2308,11 @@ class HipBackend : public Backend {
         else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
         if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
         const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        if (kind == kEvidence) {   // (the scan kernel behind the mark kernel on one stream: the boundary orders atomics and loads)
+        if (kind == kFold) {   // (the scan kernel behind the arm kernel on one stream, as below)
+            hipLaunchKernelGGL(ambi_fold_arm_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, which, fwin, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U));
+            HIP_CK(hipGetLastError());
+            hipLaunchKernelGGL(ambi_fold_scan_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U), B.d, (const int64_t*)R.d_off);
+        } else if (kind == kEvidence) {   // (the scan kernel behind the mark kernel on one stream: the boundary orders atomics and loads)
             hipLaunchKernelGGL(ambi_evidence_mark_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, frag_args_, which, pwin, fslots, L->d_depth, (const int64_t*)(R.d_off + U));
             HIP_CK(hipGetLastError());
             hipLaunchKernelGGL(ambi_evidence_scan_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, L->d_depth, (const int64_t*)(R.d_off + U), B.d, (const int64_t*)R.d_off);
@@ -2325,6 +2362,18 @@ class HipBackend : public Backend {
         if (!prof_[kEvidence].view || !lease_) return ST_ERR_BAD_INPUT;
         if (ptr) *ptr = lease_->d_depth;
         return evidence_depth_offsets(bytes, unit_off, cap);
+    }
+    // the fold kind's planes: a range of one unit's plane to the host, and the area itself
+    int fold_plane_copy(int unit, int plane, int64_t first, int64_t n, int32_t* out) override {
+        DeviceGuard dg_(device_);
+        if (!prof_[kFold].view || !lease_ || !lease_->d_planes || unit < 0 || unit >= (int)plane_off_.size() || plane < 0 || plane > 1 || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) HIP_CK(hipMemcpy(out, lease_->d_planes + plane * plane_bytes_ + plane_off_[(size_t)unit] + 4 * first, (size_t)(4 * n), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int fold_planes_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) override {
+        if (!prof_[kFold].view || !lease_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->d_planes;
+        return fold_plane_offsets(bytes, unit_off, cap);
     }
     // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----
     // sequence() works on `stream` behind everything that writes the result blob in the last run (behind_results): the

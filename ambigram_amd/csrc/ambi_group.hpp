@@ -72,6 +72,8 @@ struct HostGroup {
     AMBI_HD int sub_lane() const { return 0; }
     // number of set flags among the lower threads of my sub-group; *count = set flags in the whole sub-group
     AMBI_HD int flag_rank(bool q, int* count) const { *count = q ? 1 : 0; return 0; }
+    // the flags of my sub-group, bit sub_lane() of the result; no barrier
+    AMBI_HD uint64_t sub_ballot_u64(bool q) const { return q ? 1ull : 0ull; }
     // the same over the WHOLE group: number of set flags among the lower threads; *count = set flags in the group
     AMBI_HD int flag_exscan(bool q, int* count) const { *count = q ? 1 : 0; return 0; }
 };
@@ -163,6 +165,7 @@ struct WaveGroup {
         return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
     }
     __device__ inline int flag_exscan(bool q, int* count) const { return flag_rank(q, count); }
+    __device__ inline uint64_t sub_ballot_u64(bool q) const { return __ballot(q); }
 };
 
 // One workgroup. `scratch` points at >= 40 ints of LDS reserved for the reductions (16-byte aligned for exscan_i64, see above).
@@ -231,6 +234,7 @@ struct BlockGroup {
     __device__ inline int n_subs() const { return nwaves(); }
     __device__ inline int sub_lane() const { return (int)(threadIdx.x & 63u); }
     __device__ inline int flag_rank(bool q, int* count) const { WaveGroup w; return w.flag_rank(q, count); }
+    __device__ inline uint64_t sub_ballot_u64(bool q) const { return __ballot(q); }
     __device__ inline int flag_exscan(bool q, int* count) const { return exscan_i32(q ? 1 : 0, count); }
     __device__ inline int first_flag(bool q) const { const int m = min_i32(q ? (int)threadIdx.x : 0x7fffffff); return m == 0x7fffffff ? -1 : m; }
 };

@@ -267,6 +267,13 @@ int run_sc_bfb(Args& A) {
 // between chromosomes: 0 0 -1), junction index, count in the final path, those of them under at least one fragment occurrence, the
 // smallest depth over them or -1 -- and the depth of every final path in run-length form -- sample, chromosome index, first step,
 // steps, depth --; stdout and the side files are unchanged.
+// --fold_profile <file> / --fold_arms <file> (where does the printed path fold back, how long are the palindromes and how deeply do
+// they nest?): after the run the device's fold-back arm profile of the final paths (ambi_batch_fold_profile) gives, in
+// --fold_profile, one tab-separated `U` row per chromosome -- U, sample, chromosome index, status, steps, folds, perfect, gapped and
+// open folds, folds of no junction, longest arm and its step, largest cover and its step, covered steps, sum of the arms -- and
+// one `J` row per junction in file order -- J, sample, chromosome index (-1 for a junction between chromosomes: 0 0), junction
+// index, folds, longest arm --; in --fold_arms one row per fold -- sample, chromosome index, step k, alignment (-1: no arm, 0:
+// perfect, 1..4), arm, nesting (cover[k] - 1) --; stdout and the side files are unchanged.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -302,6 +309,9 @@ int run_bfb(Args& A) {
     const std::string evidence_depth = A.kv.count("evidence_depth") ? A.kv["evidence_depth"] : "";
     const std::string evidence_opt = !evidence_profile.empty() ? "--evidence_profile" : !evidence_depth.empty() ? "--evidence_depth" : "";
     if (!evidence_opt.empty() && frags.empty()) { std::cerr << evidence_opt << " needs a fragment file: --frags <file> or --juncdb <file>" << std::endl; return 2; }
+    const std::string fold_profile = A.kv.count("fold_profile") ? A.kv["fold_profile"] : "";
+    const std::string fold_arms = A.kv.count("fold_arms") ? A.kv["fold_arms"] : "";
+    const std::string fold_opt = !fold_profile.empty() ? "--fold_profile" : !fold_arms.empty() ? "--fold_arms" : "";
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
     const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
@@ -366,6 +376,13 @@ int run_bfb(Args& A) {
                 return 2;
             }
             if (frag_profile.empty() && (rc = ambi_graph_read_fragments(g, frags.c_str())) != 0) return die("--frags " + frags + ": " + ambi_error_string(rc));
+        }
+        if (!fold_opt.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << fold_opt << ": " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
+                return 2;
+            }
         }
         if (!out_fasta.empty()) {
             ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
@@ -552,6 +569,46 @@ int run_bfb(Args& A) {
                         fprintf(pf, "%s\t%d\t%d\t%d\t%d\n", S.lh.c_str(), c, k, q - k, depth[k]);
                         k = q;
                     }
+                }
+            fclose(pf);
+        }
+    }
+    if (!fold_opt.empty()) {
+        if ((rc = ambi_batch_fold_profile(b, 1, nullptr)) != 0 || (rc = ambi_batch_fold_profile_wait(b)) != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+        if (!fold_profile.empty()) {
+            FILE* pf = fopen(fold_profile.c_str(), "w");
+            if (!pf) return die("Cannot open file " + fold_profile);
+            for (Sample& S : samples) {
+                const int m = S.n_junc;
+                std::vector<int32_t> folds(m, 0), max_arm(m, 0), chr_of(m, -1);
+                for (int c = 0; c < S.n_chr; c++) {
+                    ambi_unit_fold_profile_t e;
+                    if ((rc = ambi_batch_unit_fold_profile(b, S.unit[c], &e)) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                    fprintf(pf, "U\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%lld\n", S.lh.c_str(), c, e.status, e.steps, e.folds, e.folds_perfect,
+                            e.folds_gapped, e.folds_open, e.folds_unmatched, e.max_arm, e.max_arm_at, e.max_cover, e.max_cover_at, e.steps_covered, (long long)e.arm_sum);
+                    const int mu = ambi_batch_unit_fold_juncs(b, S.unit[c], nullptr, nullptr, nullptr, INT32_MAX);
+                    if (mu < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(mu)); }
+                    std::vector<int32_t> cnt(mu), arm(mu), idx(mu);
+                    if ((rc = ambi_batch_unit_fold_juncs(b, S.unit[c], cnt.data(), arm.data(), idx.data(), mu)) < 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                    for (int j = 0; j < mu; j++) if (idx[j] >= 0 && idx[j] < m) { folds[idx[j]] = cnt[j]; max_arm[idx[j]] = arm[j]; chr_of[idx[j]] = c; }
+                }
+                for (int j = 0; j < m; j++) fprintf(pf, "J\t%s\t%d\t%d\t%d\t%d\n", S.lh.c_str(), chr_of[j], j, folds[j], max_arm[j]);
+            }
+            fclose(pf);
+        }
+        if (!fold_arms.empty()) {
+            FILE* pf = fopen(fold_arms.c_str(), "w");
+            if (!pf) return die("Cannot open file " + fold_arms);
+            for (Sample& S : samples)
+                for (int c = 0; c < S.n_chr; c++) {
+                    ambi_unit_fold_profile_t e;
+                    if ((rc = ambi_batch_unit_fold_profile(b, S.unit[c], &e)) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                    std::vector<int32_t> fold((size_t)e.steps), cover((size_t)e.steps);
+                    if ((rc = ambi_batch_unit_fold_plane(b, S.unit[c], 0, 0, e.steps, fold.data())) != 0 || (rc = ambi_batch_unit_fold_plane(b, S.unit[c], 1, 0, e.steps, cover.data())) != 0) {
+                        fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc));
+                    }
+                    for (int k = 0; k < e.steps; k++)
+                        if (fold[k]) fprintf(pf, "%s\t%d\t%d\t%d\t%d\t%d\n", S.lh.c_str(), c, k, AMBI_FOLD_ALIGN(fold[k]), AMBI_FOLD_ARM(fold[k]), cover[k] - 1);
                 }
             fclose(pf);
         }
@@ -743,7 +800,8 @@ int main(int argc, char** argv) {
     if (A.help) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
-                     "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--evidence_profile <file>] [--evidence_depth <file>] [--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--evidence_profile <file>] [--evidence_depth <file>] [--fold_profile <file>] [--fold_arms <file>] "
+                     "[--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
@@ -759,6 +817,12 @@ int main(int argc, char** argv) {
                      "over them or -1 (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
                      "  --evidence_depth <file> (--op bfb): the number of fragment occurrences over every step of the final paths in run-length form: sample, "
                      "chromosome index, first step, steps, depth (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --fold_profile <file> (--op bfb): the fold-back structure of the final paths after the run: one tab-separated U row per chromosome "
+                     "(U, sample, chromosome index, status, steps, folds, perfect, gapped, open, folds of no junction, longest arm, its step, largest cover, its "
+                     "step, covered steps, sum of arms) and one J row per junction in file order (J, sample, chromosome index or -1, junction index, folds, "
+                     "longest arm) (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --fold_arms <file> (--op bfb): one tab-separated row per fold of the final paths: sample, chromosome index, step, alignment (-1 no arm, "
+                     "0 perfect, 1..4 one or two unpaired cells), arm in cells, nesting (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
                      "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
                      "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
                      "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";

@@ -474,6 +474,65 @@ int ambi_batch_evidence_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t*
  * batch. */
 int ambi_batch_evidence_depth_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap);
 
+/* The fold-back arm profile of every unit's path, computed ON THE DEVICE (ambi_fold_arm_kernel, ambi_fold_scan_kernel): where the
+ * path folds back, how long the reverse-complement palindrome around every fold is, and how deeply the palindromes nest -- the
+ * structure that makes a path a breakage-fusion-bridge path.  With the path cells c[0..P) that ambi_batch_unit_path(unit, which)
+ * returns (as local ids), the steps k = 0 .. P-2 and the junctions j = 0..m-1 with the crediting rule of ambi_batch_junc_profile:
+ *   fold: a step whose two cells have opposite sign (where printBFB prints `|`);
+ *   alignments a = 0..4 with (dl, dr) = (0,1) (-1,1) (0,2) (-2,1) (0,3): the perfect fold-back, then one or two unpaired cells on the
+ *   left or on the right.  With i = k + dl and j = k + dr, arm_a is the largest r >= 0 with i-t >= 0, j+t < P and c[i-t] == -c[j+t]
+ *   for all t < r; 0 when i < 0 or j >= P;
+ *   a fold's alignment and arm: the smallest a with arm_a > 0 and that arm; alignment -1 and arm 0 when there is none;
+ *   span: a fold with arm r > 0 covers the steps i-r+1 .. j+r-2, k among them;
+ *   cover[s] = folds whose span covers step s; the nesting of a fold at k is cover[k] - 1;
+ *   folds[j] = folds credited to junction j, max_arm[j] = the longest arm among them (0 when there are none).
+ * All fields are exact integers.  Two int32 planes stay on the device (4 bytes each per cell of every unit's path capacity):
+ *   plane 0, fold[k]: 0 for a step that is no fold, else (alignment + 2) << 24 | arm (arms stay below 2^22);
+ *   plane 1, cover[k].
+ * Per unit 2 m int32 travel to the host. */
+#define AMBI_FOLD_ARM(v) ((int32_t)((v) & 0xffffff))
+#define AMBI_FOLD_ALIGN(v) ((int32_t)(((v) >> 24) - 2))
+typedef struct {
+    int32_t status;           /* the unit's status (ambi_unit_result_t::status) */
+    int32_t steps;            /* P - 1; a unit with a negative status or without a path has every field but status zero and
+                                 max_arm_at = max_cover_at = -1 */
+    int32_t folds;            /* steps whose two cells have opposite sign */
+    int32_t folds_perfect;    /* folds with alignment 0 */
+    int32_t folds_gapped;     /* folds with alignment 1..4 */
+    int32_t folds_open;       /* folds with alignment -1: no arm */
+    int32_t folds_unmatched;  /* folds credited to no junction */
+    int32_t max_arm;          /* the longest arm */
+    int32_t max_arm_at;       /* the smallest k of a fold with that arm, -1 if max_arm == 0 */
+    int32_t max_cover;        /* max over the steps of cover */
+    int32_t max_cover_at;     /* the smallest step with that cover, -1 if max_cover == 0 */
+    int32_t steps_covered;    /* steps with cover > 0 */
+    int64_t arm_sum;          /* sum of the arms of all folds */
+} ambi_unit_fold_profile_t;
+/* Queues the fold profile of the LAST run's results behind that run on hip_stream (which as for ambi_batch_profile): the two
+ * kernels, then one device-to-host copy of the block on the engine's copy stream: hip_stream is not blocked.  The planes are
+ * allocated at the first request; a failure to allocate them is this call's error.  AMBI_ERR_STATE before any run, AMBI_ERR_ARG for
+ * another `which`.  After ambi_batch_run_sharded the call goes to every share, on the share's own stream. */
+int ambi_batch_fold_profile(ambi_batch_t* b, int32_t which, void* hip_stream);
+/* Blocks until the fold profile is in host memory.  Makes the run's results final first (ambi_batch_wait) and profiles once more
+ * if that changed them after the request was queued. */
+int ambi_batch_fold_profile_wait(ambi_batch_t* b);
+/* A unit's summary; AMBI_ERR_STATE without a waited-for fold profile of the last run. */
+int ambi_batch_unit_fold_profile(const ambi_batch_t* b, int32_t unit, ambi_unit_fold_profile_t* out);
+/* A unit's values per junction: folds and max_arm as above, graph_index[j] = the junction's index in the graph's list (j itself
+ * for a raw unit).  Any pointer may be NULL.  Returns m; AMBI_ERR_ARG when cap < m. */
+int ambi_batch_unit_fold_juncs(const ambi_batch_t* b, int32_t unit, int32_t* folds, int32_t* max_arm, int32_t* graph_index, int32_t cap);
+/* The entries [first, first + n) of a unit's plane (0: fold, 1: cover) to host memory; nothing else is downloaded.  AMBI_ERR_ARG
+ * for another plane or a range outside [0, P-1] (a unit without a step takes n = 0 only). */
+int ambi_batch_unit_fold_plane(ambi_batch_t* b, int32_t unit, int32_t plane, int64_t first, int64_t n, int32_t* out);
+/* The fold profile block in DEVICE memory, for collectives: [ambi_unit_fold_profile_t[n_units]] padded to 16 bytes, then per unit
+ * folds int32[m] and max_arm int32[m], each array padded to 16 bytes.  Valid after ambi_batch_fold_profile_wait until the next
+ * ambi_batch_fold_profile; not available for a sharded batch. */
+int ambi_batch_fold_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+/* Both planes in DEVICE memory, `bytes` in all: the fold planes of all units in the first half, the cover planes in the second;
+ * plane p of unit u is int32[steps] at byte p * (bytes / 2) + unit_off[u] (a multiple of 16; cap >= n_units entries, or NULL), the
+ * slices of a unit without a path hold nothing of meaning.  Valid as the block above; not available for a sharded batch. */
+int ambi_batch_fold_planes_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap);
+
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
  * through `bedtools getfasta -s`, all records joined).
