@@ -70,6 +70,32 @@ def fold_align(v):
     return (v >> 24) - 2
 
 
+class PathCompare(C.Structure):     # ambi_path_compare_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "len_a", "len_b", "dmax")] + [(k, C.c_int32 * 2) for k in ("prefix", "suffix", "dist", "lcs")]
+
+
+# the same as a structured numpy dtype (Batch.path_compare_results), 48 bytes
+PATH_COMPARE_DTYPE = np.dtype([(k, np.int32) for k in ("status", "len_a", "len_b", "dmax")] + [(k, np.int32, (2,)) for k in ("prefix", "suffix", "dist", "lcs")])
+COMPARE_DMAX_CAP, COMPARE_DMAX_DEFAULT = 1024, 64
+
+
+def compare_unit(u, which=1):
+    """AMBI_COMPARE_UNIT: the side of a pair that is ambi_batch_unit_path(u, which)."""
+    return 2 * u + which
+
+
+def compare_given(t):
+    """AMBI_COMPARE_GIVEN: the side of a pair that is the t-th path of Batch.set_compare_paths."""
+    return ~t
+
+
+def compare_all_pairs(sides):
+    """All pairs (sides[i], sides[j]), i < j, as an int32 array [n * (n - 1) / 2, 2] for Batch.path_compare -- the single-cell case: one
+    unit per cell over a shared segmentation, every cell's path against every other's."""
+    s = list(sides)
+    return np.array([(s[i], s[j]) for i in range(len(s)) for j in range(i + 1, len(s))], np.int32).reshape(-1, 2)
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -168,6 +194,11 @@ def _declare(L):
         "ambi_batch_unit_fold_plane": (C.c_int, [vp, i32, i32, i64, i64, pi32]),
         "ambi_batch_fold_profile_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_batch_fold_planes_device": (C.c_int, [vp, _P(vp), pi64, pi64, i32]),
+        "ambi_batch_set_compare_paths": (C.c_int, [vp, pi32, pi64, i32]),
+        "ambi_batch_path_compare": (C.c_int, [vp, pi32, i32, i32, vp]),
+        "ambi_batch_path_compare_wait": (C.c_int, [vp]),
+        "ambi_batch_path_compare_result": (C.c_int, [vp, i32, _P(PathCompare)]),
+        "ambi_batch_path_compare_device": (C.c_int, [vp, _P(vp), pi64]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
         "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
         "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
@@ -793,6 +824,45 @@ class Batch:
         off = np.zeros(U, np.int64)
         self._ck(self.lib.ambi_batch_fold_planes_device(self.h, C.byref(p), C.byref(n), off.ctypes.data_as(_P(C.c_int64)), U), "fold_planes_device")
         return p.value or 0, n.value, off
+
+    def set_compare_paths(self, paths):
+        """The given paths of the batch (ambi_batch_set_compare_paths): a list of paths in the local signed ids of whatever they are
+        compared with; path t is the side compare_given(t).  Replaces the earlier set."""
+        paths = [np.ascontiguousarray(p, np.int32).reshape(-1) for p in paths]
+        off = np.zeros(len(paths) + 1, np.int64)
+        if paths:
+            off[1:] = np.cumsum([len(p) for p in paths])
+        cells = np.concatenate(paths) if paths else np.zeros(0, np.int32)
+        self._ck(self.lib.ambi_batch_set_compare_paths(self.h, cells.ctypes.data_as(_P(C.c_int32)), off.ctypes.data_as(_P(C.c_int64)), len(paths)), "set_compare_paths")
+
+    def path_compare(self, pairs, dmax=COMPARE_DMAX_DEFAULT, stream=None):
+        """Queues the comparison of the pairs (an [n, 2] array of sides: compare_unit / compare_given) over the last run's paths behind
+        that run (ambi_batch_path_compare): per pair and orientation the common prefix and suffix, and the indel distance and LCS if
+        the distance is at most dmax (0 .. 1024); `stream` is not blocked."""
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        self._ck(self.lib.ambi_batch_path_compare(self.h, p.ctypes.data_as(_P(C.c_int32)), len(p), dmax, C.c_void_p(stream or 0)), "path_compare")
+        self._n_compared = len(p)                       # (of the request the engine took)
+
+    def path_compare_wait(self):
+        """Waits for the comparison in host memory (the run's results are final first); path_compare_results answers afterwards."""
+        self._ck(self.lib.ambi_batch_path_compare_wait(self.h), "path_compare_wait")
+
+    def path_compare_results(self):
+        """The results of the last request as a structured array (PATH_COMPARE_DTYPE): status, len_a, len_b, dmax and, per orientation,
+        prefix, suffix, dist, lcs."""
+        self._ck(self.lib.ambi_batch_path_compare_device(self.h, None, None), "path_compare_results")   # (the state check: a waited-for request of the last run)
+        out = np.zeros(getattr(self, "_n_compared", 0), PATH_COMPARE_DTYPE)
+        r = PathCompare()
+        for i in range(len(out)):
+            self._ck(self.lib.ambi_batch_path_compare_result(self.h, i, C.byref(r)), "path_compare_results")
+            out[i] = np.frombuffer(bytes(r), PATH_COMPARE_DTYPE)[0]
+        return out
+
+    def path_compare_device(self):
+        """(address, bytes) of the results in device memory (ambi_batch_path_compare_device), for collectives."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._ck(self.lib.ambi_batch_path_compare_device(self.h, C.byref(p), C.byref(n)), "path_compare_device")
+        return p.value or 0, n.value
 
     def set_unit_sequences(self, u, bases, seg_off):
         """Bases of a unit added with add_unit (ambi_batch_set_unit_sequences): local segment i + 1 = bases[seg_off[i]:seg_off[i + 1]]."""

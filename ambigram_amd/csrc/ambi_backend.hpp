@@ -11,6 +11,7 @@
 #include "ambi_fold_profile.hpp"
 #include "ambi_frag_profile.hpp"
 #include "ambi_junc_profile.hpp"
+#include "ambi_path_compare.hpp"
 #include "ambi_profile.hpp"
 #include "ambi_sequence.hpp"
 
@@ -94,13 +95,14 @@ class Backend {
     // (ambi_evidence_profile.hpp: fragment occurrences over every step, per junction its covered traversals) and the fold-back arm
     // profile (ambi_fold_profile.hpp: the palindrome arm of every fold, how the arms nest, per junction its folds), each a block
     // [summary[U]][per unit counts]; the evidence kind has a depth area and the fold kind two planes beside the block that stay where
-    // they were computed.
+    // they were computed.  A sixth kind shares the life cycle but not the shape: the path comparison (ambi_path_compare.hpp) takes a list
+    // of pairs and a cap with the request (compare() below) and its block is [PathCompare[n_pairs]].
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
     // simulation); the HIP engine overrides the virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4 };
-    static constexpr int kProfileKinds = 5;
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4, kCompare = 5 };
+    static constexpr int kProfileKinds = 6;
     void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
     virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
@@ -110,7 +112,8 @@ class Backend {
         ProfileState& P = prof_[kind];
         profile_layout(kind);
         P.blob.assign((size_t)P.bytes, 0);
-        if (kind == kFold) host_fold_profile(blob.data(), which, P);
+        if (kind == kCompare) host_compare(blob.data(), P);
+        else if (kind == kFold) host_fold_profile(blob.data(), which, P);
         else if (kind == kEvidence) host_evidence_profile(blob.data(), which, P);
         else if (kind == kFragment) host_frag_profile(blob.data(), which, P);
         else if (kind == kJunction) host_junc_profile(blob.data(), which, P);
@@ -245,6 +248,28 @@ class Backend {
         return fold_plane_offsets(bytes, unit_off, cap);
     }
 
+    // ---- path comparison (ambi_path_compare.hpp): kCompare ----
+    // compare() keeps the WHOLE request -- the pairs' sides (2 * unit + which, or ~t for the t-th given path), the cap and a copy of
+    // the given paths as they were when it was made -- and queues it as the other kinds are queued (profile(kCompare)).  A request that
+    // profile_wait() has to queue again finds all of it here: the caller may replace its set of given paths between a request and
+    // its wait, and the request still compares what it named.  The copy is taken only when the caller's set has another version.
+    // A given side beyond the copied set is refused here as well, whatever the caller checked.
+    int compare(const ComparePaths* given, const int32_t* pairs, int n_pairs, int dmax, void* stream) {
+        if (!given || n_pairs < 0 || (n_pairs > 0 && !pairs) || dmax < 0 || dmax > kCompareDmaxCap) return ST_ERR_BAD_INPUT;
+        for (int64_t i = 0; i < 2 * (int64_t)n_pairs; i++) if (pairs[i] < 0 && ~pairs[i] >= given->n()) return ST_ERR_BAD_INPUT;
+        if (cmp_given_.version != given->version) cmp_given_ = *given;
+        cmp_dmax_ = dmax;
+        cmp_pairs_.assign(pairs, pairs + 2 * (size_t)n_pairs);
+        return profile(kCompare, 1, stream);
+    }
+    int compare_pairs() const { return (int)(cmp_pairs_.size() / 2); }
+    int compare_result(int pair, PathCompare* out) const {
+        const ProfileState& P = prof_[kCompare];
+        if (!P.view || pair < 0 || pair >= compare_pairs() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const PathCompare*>(P.view)[pair];
+        return 0;
+    }
+
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
     // sequence() runs pass 0 of the extents stage behind the last run and fetches its totals (count x {bytes, runs}: the one small
     // device-to-host trip of a request), sizes the extent arrays and the output block from them, and queues pass 1 and the fill
@@ -323,7 +348,8 @@ class Backend {
     ProfileState prof_[kProfileKinds];   // [ProfileKind]
     void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
         ProfileState& P = prof_[kind];
-        if (kind == kFold) { P.bytes = fold_block_layout(prof_hb_->units, P.off); plane_bytes_ = fold_plane_layout(prof_hb_->units, plane_off_); }
+        if (kind == kCompare) { P.bytes = compare_block_bytes(compare_pairs()); P.off.clear(); }
+        else if (kind == kFold) { P.bytes = fold_block_layout(prof_hb_->units, P.off); plane_bytes_ = fold_plane_layout(prof_hb_->units, plane_off_); }
         else if (kind == kEvidence) { P.bytes = evidence_block_layout(prof_hb_->units, P.off); depth_bytes_ = evidence_depth_layout(prof_hb_->units, depth_off_); }
         else if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
         else P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
@@ -379,6 +405,11 @@ class Backend {
     int seq_state_ = 0;                  // 0: no request; 1: lengths known; 2: sequence_wait() has returned, the getters answer
     bool seq_queued_ = false;            // the stages of the last request have been queued (false behind kSeqTooLarge)
     const HostBatch* prof_hb_ = nullptr;
+    // the compare kind's request (compare()); workgroups of a request: AMBI_COMPARE_GRID (tests) can only shrink it
+    ComparePaths cmp_given_;             // (version 0: the empty set, as the caller's before its first set)
+    std::vector<int32_t> cmp_pairs_;
+    int cmp_dmax_ = kCompareDmaxDefault;
+    int compare_grid() const { return capped_window(compare_pairs(), kCompareGridCap, env_int("AMBI_COMPARE_GRID")); }
   private:
     void host_profile(const uint8_t* blob, int which, ProfileState& P) {
         const std::vector<UnitIn>& units = prof_hb_->units;
@@ -438,6 +469,16 @@ class Backend {
         for (size_t u = 0; u < units.size(); u++) fold_arms_unit(g, units.data(), blob, (int)u, which, L, area, plane_bytes_, plane_off_.data());
         for (size_t u = 0; u < units.size(); u++)
             fold_scan_unit(g, units.data(), prof_hb_->junc_ends.data(), blob, (int)u, which, jwin, T, area, plane_bytes_, plane_off_.data(), P.blob.data(), P.off.data());
+    }
+    void host_compare(const uint8_t* blob, ProfileState& P) {
+        std::vector<Seq16A> image((size_t)(cmp_given_.image_bytes() / 16) + 1);
+        uint8_t* img = reinterpret_cast<uint8_t*>(image.data());
+        cmp_given_.image(img);
+        const CompareGiven given = compare_given(img, cmp_given_);
+        std::vector<int32_t> V((size_t)(compare_lds_bytes(cmp_dmax_) / 4));
+        HostGroup g;
+        for (int i = 0; i < compare_pairs(); i++)
+            compare_pair(g, prof_hb_->units.data(), blob, given, cmp_pairs_.data(), i, cmp_dmax_, V.data(), reinterpret_cast<PathCompare*>(P.blob.data()));
     }
     std::vector<Seq16A> depth_;          // the default implementation's depth area (16-byte aligned)
     std::vector<Seq16A> planes_;         // the default implementation's fold and cover planes (16-byte aligned)

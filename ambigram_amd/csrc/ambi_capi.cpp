@@ -115,7 +115,8 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    ComparePaths cmp;         // the given paths of ambi_batch_set_compare_paths (ambi_path_compare.hpp); not part of the batch image
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
     bool mail_view = false;   // header / final paths / output junctions are read from the backend's pinned mailbox (ambi_batch_fetch_paths)
@@ -879,6 +880,54 @@ int ambi_batch_unit_fold_plane(ambi_batch_t* b, int32_t unit, int32_t plane, int
     if (be->fold_summary(local, &s)) return AMBI_ERR_STATE;
     if (first < 0 || n < 0 || first > s.steps || n > s.steps - first || (n > 0 && !out)) return AMBI_ERR_ARG;
     return be->fold_plane_copy(local, plane, first, n, out) ? AMBI_ERR_STATE : 0;
+}
+// ---- path comparison (ambi_path_compare.hpp): the request carries its pairs and its cap, the life cycle is the profiles' ----
+int ambi_batch_set_compare_paths(ambi_batch_t* b, const int32_t* cells, const int64_t* off, int32_t n) {
+    if (!b || n < 0 || (n > 0 && (!cells || !off || off[0] != 0))) return AMBI_ERR_ARG;
+    for (int t = 0; t < n; t++) {
+        const int64_t len = off[t + 1] - off[t];
+        if (len < 1 || len > kComparePathCap) return AMBI_ERR_ARG;
+        for (int64_t i = off[t]; i < off[t + 1]; i++) if (cells[i] == 0 || cells[i] > kCompareCellCap || cells[i] < -kCompareCellCap) return AMBI_ERR_ARG;
+    }
+    ComparePaths& C = b->cmp;
+    C.cells.clear(); C.off.clear(); C.len.clear();
+    for (int t = 0; t < n; t++) {   // every path on a multiple of four cells: the 8-byte loads of the trim
+        C.off.push_back((int64_t)C.cells.size()); C.len.push_back((int32_t)(off[t + 1] - off[t]));
+        for (int64_t i = off[t]; i < off[t + 1]; i++) C.cells.push_back((rcell_t)cells[i]);
+        while (C.cells.size() & 3) C.cells.push_back((rcell_t)0);
+    }
+    C.version++;
+    b->profiled[Backend::kCompare] = false;
+    return 0;
+}
+int ambi_batch_path_compare(ambi_batch_t* b, const int32_t* pairs, int32_t n_pairs, int32_t dmax, void* hip_stream) {
+    if (!b || n_pairs < 0 || (n_pairs > 0 && !pairs)) return AMBI_ERR_ARG;
+    if (b->sharded_ready) return AMBI_ERR_UNSUPPORTED;   // (a pair may span shares)
+    if (!(b->uploaded && b->ran)) return AMBI_ERR_STATE;
+    if (dmax < 0 || dmax > kCompareDmaxCap) return AMBI_ERR_ARG;
+    static_assert(AMBI_COMPARE_DMAX_CAP == kCompareDmaxCap && AMBI_COMPARE_DMAX_DEFAULT == kCompareDmaxDefault, "the caps of ambi_path_compare.hpp");
+    static_assert(AMBI_COMPARE_UNIT(3, 1) == 7 && AMBI_COMPARE_GIVEN(0) == -1 && AMBI_COMPARE_GIVEN(2) == -3, "compare_side of ambi_path_compare.hpp");
+    const int64_t U = (int64_t)b->hb.units.size(), T = b->cmp.n();
+    for (int64_t i = 0; i < 2 * (int64_t)n_pairs; i++) {
+        const int64_t side = pairs[i];
+        if (side >= 0 ? side >= 2 * U : ~side >= T) return AMBI_ERR_ARG;
+    }
+    b->profiled[Backend::kCompare] = false;
+    const int rc = b->be->compare(&b->cmp, pairs, n_pairs, dmax, hip_stream);
+    return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc;
+}
+int ambi_batch_path_compare_wait(ambi_batch_t* b) {
+    if (b && b->sharded_ready) return AMBI_ERR_UNSUPPORTED;
+    return profile_wait(b, Backend::kCompare);
+}
+int ambi_batch_path_compare_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes) { return profile_device(b, Backend::kCompare, dev_ptr, bytes); }
+int ambi_batch_path_compare_result(const ambi_batch_t* b, int32_t pair, ambi_path_compare_t* out) {
+    if (!b || !out) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kCompare]) return AMBI_ERR_STATE;
+    if (pair < 0 || pair >= b->be->compare_pairs()) return AMBI_ERR_ARG;
+    static_assert(sizeof(ambi_path_compare_t) == sizeof(PathCompare), "ambi_path_compare_t is ambi::PathCompare");
+    static_assert(sizeof(ambi_path_compare_t) == 48, "a pair's result is 48 bytes");
+    return b->be->compare_result(pair, reinterpret_cast<PathCompare*>(out)) ? AMBI_ERR_STATE : 0;
 }
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
 int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {

@@ -32,6 +32,9 @@
 //                                                  plane (ambi_fold_profile.hpp)                   <- the same cells, 2 atomics / fold
 //   ambi_fold_scan_kernel         1 block / unit   on request, behind the arm kernel: cover per step by a scan in place, summary, per
 //                                                  junction its folds and longest arm              <- 8 bytes / step
+//   ambi_path_compare_kernel      1 block / pair   on request: common ends and indel distance of pairs of paths, both orientations:
+//                                                  trim by whole-group sweeps, then Myers' greedy rounds up to dmax, long snakes by
+//                                                  whole wavefronts (ambi_path_compare.hpp)        <- both paths twice when the trim ends it
 //                                                  (the profile kernels share unit prologue, chunked cell read and window rule --
 //                                                  profile_path, path_load_chunk, capped_window of ambi_profile.hpp -- and the two tables
 //                                                  their probe, lds_find / lds_claim of ambi_junc_profile.hpp; every reader of a unit's
@@ -676,6 +679,17 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_fold_scan_kernel(BatchAr
         __syncthreads();
     }
 }
+// ---- path comparison (ambi_path_compare.hpp; launched by HipBackend::profile_queue only) ----
+// One workgroup of 256 threads per pair, grid-stride over the pairs.  Group memory: 256 bytes for the group's reductions, then the
+// diagonal array V of 2 * dmax + 3 ints (8204 bytes at the cap of 1024).
+__global__ __launch_bounds__(kProfileThreads) void ambi_path_compare_kernel(BatchArgs A, CompareGiven given, const int32_t* pairs, int n_pairs, int dmax, PathCompare* out) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    int32_t* V = reinterpret_cast<int32_t*>(ambi_lds + kProfileScratchBytes);
+    for (int i = (int)blockIdx.x; i < n_pairs; i += (int)gridDim.x) {
+        compare_pair(g, A.units, A.results, given, pairs, i, dmax, V, out);
+        __syncthreads();
+    }
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -822,6 +836,12 @@ struct Lease {
     // the fold kind's planes: the fold plane of every unit, then the cover plane, int32 per cell of path capacity each; allocated at
     // the first request of the kind
     uint8_t* d_planes = nullptr; int64_t d_planes_bytes = 0;
+    // the compare kind's given paths (ComparePaths::image: [off][len][cells]), a device buffer of their own beside the batch image,
+    // the pinned twin that carries them up and the event behind the last upload (the host writes the twin again only behind it).
+    // The kind's block prof[kCompare] is [PathCompare[n_pairs]] with the request's pairs behind it
+    uint8_t* d_cmp_img = nullptr; int64_t d_cmp_img_bytes = 0;
+    uint8_t* h_cmp = nullptr; int64_t h_cmp_bytes = 0;
+    hipEvent_t ev_cmp_up = nullptr;
     // the batch's fragment image (HipBackend::fragment_image) [cells][frag_off][cell_off][pref_off][n_frag], its pinned twin and the
     // event behind its last upload (the host writes the twin again only behind it)
     uint8_t* d_frag_img = nullptr; int64_t d_frag_img_bytes = 0;
@@ -1190,6 +1210,8 @@ class HipBackend : public Backend {
             for (RequestBlock& B : L->prof) B.trim(kKeepProfile);
             if (L->d_depth_bytes > kKeepCells) { (void)hipFree(L->d_depth); L->d_depth = nullptr; L->d_depth_bytes = 0; }
             if (L->d_planes_bytes > kKeepCells) { (void)hipFree(L->d_planes); L->d_planes = nullptr; L->d_planes_bytes = 0; }
+            if (L->d_cmp_img_bytes > kKeepProfile) { (void)hipFree(L->d_cmp_img); L->d_cmp_img = nullptr; L->d_cmp_img_bytes = 0; }
+            if (L->h_cmp_bytes > kKeepProfile) { (void)hipHostFree(L->h_cmp); L->h_cmp = nullptr; L->h_cmp_bytes = 0; }
             if (L->d_frag_img_bytes > kKeepProfile) { (void)hipFree(L->d_frag_img); L->d_frag_img = nullptr; L->d_frag_img_bytes = 0; }
             if (L->h_frag_bytes > kKeepProfile) { (void)hipHostFree(L->h_frag); L->h_frag = nullptr; L->h_frag_bytes = 0; }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
@@ -1201,7 +1223,7 @@ class HipBackend : public Backend {
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
 
@@ -1267,7 +1289,7 @@ class HipBackend : public Backend {
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
         hbp_ = &hb_in; cfg_ = cfg;
@@ -2263,6 +2285,29 @@ class HipBackend : public Backend {
                               reinterpret_cast<const int32_t*>(L->d_frag_img + b3)};
         return 0;
     }
+    // The given paths of the compare kind (ComparePaths, ambi_path_compare.hpp) in a device buffer of their own: they go up on the
+    // request's stream when the device does not hold this version of them (pinned twin, one copy), as the fragment image does.  The
+    // batch image is not touched.
+    int64_t cmp_img_version_ = -1;
+    CompareGiven cmp_args_{};
+    int compare_image(hipStream_t s) {
+        Lease* L = lease_;
+        const ComparePaths& I = cmp_given_;
+        const int64_t total = I.image_bytes();
+        if (cmp_img_version_ != I.version || !L->d_cmp_img) {
+            if (req_[kCompare].queued) HIP_CK(hipEventSynchronize(L->prof[kCompare].ev_done));   // (its kernel reads the buffer)
+            if (!L->ev_cmp_up) HIP_CK(hipEventCreateWithFlags(&L->ev_cmp_up, hipEventDisableTiming));
+            else HIP_CK(hipEventSynchronize(L->ev_cmp_up));   // (an earlier upload still reads the twin)
+            if (int rc = lease_device_block(&L->d_cmp_img, &L->d_cmp_img_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&L->h_cmp, nullptr, &L->h_cmp_bytes, total)) return rc;
+            I.image(L->h_cmp);
+            HIP_CK(hipMemcpyAsync(L->d_cmp_img, L->h_cmp, (size_t)total, hipMemcpyHostToDevice, s));
+            HIP_CK(hipEventRecord(L->ev_cmp_up, s));
+            cmp_img_version_ = I.version;
+        } else HIP_CK(hipStreamWaitEvent(s, L->ev_cmp_up, 0));   // (the upload may have gone up on another stream)
+        cmp_args_ = compare_given(L->d_cmp_img, I);
+        return 0;
+    }
     // The profiles are instances of one on-request block (Lease::prof, req_, Backend::prof_); a kind has its own layout, its own
     // kernel with its LDS size, and nothing else -- but for the fragment kind's image, which goes up in front of its kernel.
     // profile() queues the kind's kernel behind the run, then ONE device-to-host copy of the block on the lease's copy stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes
@@ -2279,9 +2324,16 @@ class HipBackend : public Backend {
             }
             if (int rc = fragment_image(s)) return rc;
         }
+        const bool cmp = kind == kCompare;
+        const int64_t n_pairs = compare_pairs();
+        if (cmp) {   // (pairs and cap come with the request: laid out every time, once the last request's copy and upload have left block and twin)
+            if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done));
+            R.laid_out = false;
+            if (int rc = compare_image(s)) return rc;
+        }
         if (!R.laid_out) {
             profile_layout(kind);
-            const int64_t n_off = kind == kEvidence || kind == kFold ? 2 * U : U;   // (the evidence and fold kinds: the depth area's or the planes' offsets behind the block's)
+            const int64_t n_off = cmp ? n_pairs : kind == kEvidence || kind == kFold ? 2 * U : U;   // (the evidence and fold kinds: the depth area's or the planes' offsets behind the block's; the compare kind: the pairs, two int32 each)
             const int64_t total = P.bytes + n_off * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
             if (kind == kEvidence) { if (int rc = lease_device_block(&L->d_depth, &L->d_depth_bytes, depth_bytes_ > 0 ? depth_bytes_ : 16)) return rc; }
             if (kind == kFold) { if (int rc = lease_device_block(&L->d_planes, &L->d_planes_bytes, plane_bytes_ > 0 ? 2 * plane_bytes_ : 16)) return rc; }
@@ -2290,16 +2342,18 @@ class HipBackend : public Backend {
             if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
             for (hipEvent_t* e : {&B.ev_src, &B.ev_packed, &B.ev_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
             // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
-            memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
+            if (cmp) { if (n_pairs > 0) memcpy(B.h + P.bytes, cmp_pairs_.data(), (size_t)n_pairs * sizeof(int64_t)); }
+            else memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
             if (kind == kEvidence) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), depth_off_.data(), (size_t)U * sizeof(int64_t));
             if (kind == kFold) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), plane_off_.data(), (size_t)U * sizeof(int64_t));
             R.d_off = reinterpret_cast<int64_t*>(B.d + P.bytes);
-            HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)n_off * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (n_off > 0) HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)n_off * sizeof(int64_t), hipMemcpyHostToDevice, s));
             R.laid_out = true;
         }
         if (int rc = behind_results(s, B.ev_src)) return rc;
         int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes, fslots = 0, lds_mark = kProfileScratchBytes, fwin = 0;
-        if (kind == kFold) { fold_windows(&fwin, &jwin, &slots); lds_mark += (int)fold_arm_lds_bytes(fwin); lds += (int)fold_scan_lds_bytes(slots); }
+        if (cmp) lds += (int)compare_lds_bytes(cmp_dmax_);
+        else if (kind == kFold) { fold_windows(&fwin, &jwin, &slots); lds_mark += (int)fold_arm_lds_bytes(fwin); lds += (int)fold_scan_lds_bytes(slots); }
         else if (kind == kEvidence) {
             frag_profile_windows(&pwin, &fslots); lds_mark += (int)frag_profile_lds_bytes(fslots, pwin);
             evidence_windows(&jwin, &slots); lds += (int)evidence_scan_lds_bytes(slots, kProfileThreads);
@@ -2308,7 +2362,9 @@ class HipBackend : public Backend {
         else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
         if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
         const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        if (kind == kFold) {   // (the scan kernel behind the arm kernel on one stream, as below)
+        if (cmp) {   // (a workgroup per pair; a request without pairs launches nothing)
+            if (n_pairs > 0) hipLaunchKernelGGL(ambi_path_compare_kernel, dim3(compare_grid()), dim3(kProfileThreads), lds, s, A_, cmp_args_, (const int32_t*)R.d_off, (int)n_pairs, cmp_dmax_, reinterpret_cast<PathCompare*>(B.d));
+        } else if (kind == kFold) {   // (the scan kernel behind the arm kernel on one stream, as below)
             hipLaunchKernelGGL(ambi_fold_arm_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, which, fwin, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U));
             HIP_CK(hipGetLastError());
             hipLaunchKernelGGL(ambi_fold_scan_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U), B.d, (const int64_t*)R.d_off);

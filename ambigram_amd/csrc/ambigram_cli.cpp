@@ -4,6 +4,7 @@
 // the external `cbc`, appended simulation_sv.txt and time.csv), same exit codes for unreadable .lh / missing .sol.
 // The per-chromosome stages run on the GPU through libambigram_hip.so; the ILP model is built on the host
 // (ambi_ilp_build) and solved by whatever `cbc` is on PATH, exactly as the reference shells out (localhap.cpp:179-181).
+#include <cctype>
 #include <chrono>
 #include <cstdint>
 #include <cmath>
@@ -274,6 +275,13 @@ int run_sc_bfb(Args& A) {
 // one `J` row per junction in file order -- J, sample, chromosome index (-1 for a junction between chromosomes: 0 0), junction
 // index, folds, longest arm --; in --fold_arms one row per fold -- sample, chromosome index, step k, alignment (-1: no arm, 0:
 // perfect, 1..4), arm, nesting (cover[k] - 1) --; stdout and the side files are unchanged.
+// --path_compare <file> [--truth <file>] [--compare_dmax N] (how close are two paths?): after the run the device's path comparison
+// (ambi_batch_path_compare) gives one tab-separated `P` row per chromosome, the path of getBFB against the path after indelBFB -- P,
+// sample, chromosome index, status, len_a, len_b, dmax, prefix, suffix, dist and lcs, each for the orientation as is and for the
+// reverse complement --; with --truth also one `T` row per chromosome that has a truth line, the final path against that line.  A
+// truth file has one line per chromosome in printing order: a path as it is printed here (`|` is ignored, ids are global), or `.`
+// for none; an id outside the chromosome, a missing line or a line that is no path is an error found when the sample is read, in front of the run.  N: 0 .. 1024, default 64; a distance above it is -1.  stdout and the side
+// files are unchanged.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -312,6 +320,11 @@ int run_bfb(Args& A) {
     const std::string fold_profile = A.kv.count("fold_profile") ? A.kv["fold_profile"] : "";
     const std::string fold_arms = A.kv.count("fold_arms") ? A.kv["fold_arms"] : "";
     const std::string fold_opt = !fold_profile.empty() ? "--fold_profile" : !fold_arms.empty() ? "--fold_arms" : "";
+    const std::string path_compare = A.kv.count("path_compare") ? A.kv["path_compare"] : "", truth = A.kv.count("truth") ? A.kv["truth"] : "";
+    const int compare_dmax = A.kv.count("compare_dmax") ? atoi(A.kv["compare_dmax"].c_str()) : AMBI_COMPARE_DMAX_DEFAULT;
+    if (path_compare.empty() && (!truth.empty() || A.kv.count("compare_dmax"))) { std::cerr << "--truth and --compare_dmax go with --path_compare <file>" << std::endl; return 2; }
+    if (!path_compare.empty() && (compare_dmax < 0 || compare_dmax > AMBI_COMPARE_DMAX_CAP)) { std::cerr << "--compare_dmax: 0 .. " << AMBI_COMPARE_DMAX_CAP << std::endl; return 2; }
+    if (!path_compare.empty() && A.kv.count("devices")) { std::cerr << "--path_compare: not available with --devices (a pair may span shares)" << std::endl; return 2; }
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
     const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
@@ -333,6 +346,8 @@ int run_bfb(Args& A) {
         while (std::getline(ss, f, ',')) if (!f.empty()) files.push_back(f);
         if (files.empty()) files.push_back(A.kv["in_lh"]);
     }
+    if (!truth.empty() && files.size() > 1) { std::cerr << "--truth: one sample only (a truth file has one line per chromosome of one sample)" << std::endl; return 2; }
+    std::vector<std::vector<int32_t>> truth_cells;   // --truth: [chromosome] the line's path in local ids, empty for `.`
     int rc;
     std::vector<Sample> samples(files.size());
     ambi_batch_t* b; ambi_batch_create(&b);
@@ -382,6 +397,40 @@ int run_bfb(Args& A) {
             if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
                 std::cerr << fold_opt << ": " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
                 return 2;
+            }
+        }
+        if (!path_compare.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << "--path_compare: " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device comparison" << std::endl;
+                return 2;
+            }
+            if (!truth.empty()) {   // the truth file is read here, in front of anything printed or run: one line per chromosome, in printing order
+                std::ifstream tf(truth);
+                if (!tf) return die("Cannot open file " + truth);
+                int32_t ns, nj, nc;
+                ambi_graph_sizes(g, &ns, &nj, &nc);
+                truth_cells.assign((size_t)nc, std::vector<int32_t>());
+                for (int c = 0; c < nc; c++) {
+                    std::string line;
+                    if (!std::getline(tf, line)) { std::cerr << "--truth: " << truth << " has no line for chromosome " << c << std::endl; return 2; }
+                    while (!line.empty() && isspace((unsigned char)line.back())) line.pop_back();
+                    if (line == ".") continue;
+                    int32_t s, e;
+                    ambi_graph_chromosome(g, c, &s, &e);
+                    // a path as it is printed: <id><+|->..., `|` between fold-back arms ignored, ids global
+                    size_t at = 0;
+                    while (at < line.size()) {
+                        if (line[at] == '|' || isspace((unsigned char)line[at])) { at++; continue; }
+                        long id = 0; size_t digits = 0;
+                        while (at < line.size() && isdigit((unsigned char)line[at]) && digits < 9) { id = id * 10 + (line[at] - '0'); at++; digits++; }
+                        if (digits == 0 || at >= line.size() || (line[at] != '+' && line[at] != '-')) { std::cerr << "--truth: line " << c + 1 << " of " << truth << " is no path (<id><+|-> ...)" << std::endl; return 2; }
+                        if (id < s || id > e) { std::cerr << "--truth: segment " << id << " on line " << c + 1 << " of " << truth << " lies outside chromosome " << c << " (" << s << " .. " << e << ")" << std::endl; return 2; }
+                        truth_cells[(size_t)c].push_back((int32_t)(line[at] == '+' ? id - s + 1 : -(id - s + 1)));
+                        at++;
+                    }
+                    if (truth_cells[(size_t)c].empty()) { std::cerr << "--truth: line " << c + 1 << " of " << truth << " is empty (`.`: no truth for the chromosome)" << std::endl; return 2; }
+                }
             }
         }
         if (!out_fasta.empty()) {
@@ -613,6 +662,37 @@ int run_bfb(Args& A) {
             fclose(pf);
         }
     }
+    if (!path_compare.empty()) {
+        // pairs in row order: per chromosome `P` (path against path_indel), then `T` (final path against the truth line) if it has one
+        struct Row { char tag; size_t si; int c; };
+        std::vector<Row> rows;
+        std::vector<int32_t> pairs, given;
+        std::vector<int64_t> given_off(1, 0);
+        for (size_t si = 0; si < samples.size(); si++) {
+            Sample& S = samples[si];
+            for (int c = 0; c < S.n_chr; c++) {
+                pairs.push_back(AMBI_COMPARE_UNIT(S.unit[c], 0)); pairs.push_back(AMBI_COMPARE_UNIT(S.unit[c], 1));
+                rows.push_back(Row{'P', si, c});
+                if (truth.empty() || truth_cells[(size_t)c].empty()) continue;   // (--truth: one sample; `.`: no truth for the chromosome)
+                given.insert(given.end(), truth_cells[(size_t)c].begin(), truth_cells[(size_t)c].end());
+                given_off.push_back((int64_t)given.size());
+                pairs.push_back(AMBI_COMPARE_UNIT(S.unit[c], 1)); pairs.push_back(AMBI_COMPARE_GIVEN((int32_t)given_off.size() - 2));
+                rows.push_back(Row{'T', si, c});
+            }
+        }
+        if ((rc = ambi_batch_set_compare_paths(b, given.data(), given_off.data(), (int32_t)given_off.size() - 1)) != 0 ||
+            (rc = ambi_batch_path_compare(b, pairs.data(), (int32_t)rows.size(), compare_dmax, nullptr)) != 0 || (rc = ambi_batch_path_compare_wait(b)) != 0)
+            return die(std::string("engine: ") + ambi_error_string(rc));
+        FILE* pf = fopen(path_compare.c_str(), "w");
+        if (!pf) return die("Cannot open file " + path_compare);
+        for (size_t i = 0; i < rows.size(); i++) {
+            ambi_path_compare_t r;
+            if ((rc = ambi_batch_path_compare_result(b, (int32_t)i, &r)) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+            fprintf(pf, "%c\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", rows[i].tag, samples[rows[i].si].lh.c_str(), rows[i].c, r.status, r.len_a, r.len_b, r.dmax,
+                    r.prefix[0], r.prefix[1], r.suffix[0], r.suffix[1], r.dist[0], r.dist[1], r.lcs[0], r.lcs[1]);
+        }
+        fclose(pf);
+    }
     if (!out_fasta.empty()) {
         FILE* ff = fopen(out_fasta.c_str(), "w");
         if (!ff) return die("Cannot open file " + out_fasta);
@@ -801,7 +881,7 @@ int main(int argc, char** argv) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
                      "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--evidence_profile <file>] [--evidence_depth <file>] [--fold_profile <file>] [--fold_arms <file>] "
-                     "[--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--path_compare <file> [--truth <file>] [--compare_dmax N]] [--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
@@ -823,6 +903,11 @@ int main(int argc, char** argv) {
                      "longest arm) (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
                      "  --fold_arms <file> (--op bfb): one tab-separated row per fold of the final paths: sample, chromosome index, step, alignment (-1 no arm, "
                      "0 perfect, 1..4 one or two unpaired cells), arm in cells, nesting (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
+                     "  --path_compare <file> [--truth <file>] [--compare_dmax N] (--op bfb): one tab-separated P row per chromosome after the run, the path "
+                     "before indelBFB against the path after it: P, sample, chromosome index, status, len_a, len_b, dmax, then prefix, suffix, dist, lcs for the "
+                     "orientation as is and for the reverse complement (dist: insertions plus deletions, -1 above N; N 0..1024, default 64); with --truth a T row "
+                     "per chromosome, the final path against that chromosome's line of the truth file (a printed path with global ids, or `.`; one sample only) "
+                     "(PROP I1 / C1 / I2 / C2 samples and --devices are refused, exit status 2)\n"
                      "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
                      "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
                      "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";

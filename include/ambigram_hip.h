@@ -533,6 +533,54 @@ int ambi_batch_fold_profile_device(ambi_batch_t* b, void** dev_ptr, int64_t* byt
  * slices of a unit without a path hold nothing of meaning.  Valid as the block above; not available for a sharded batch. */
 int ambi_batch_fold_planes_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap);
 
+/* Path comparison ON THE DEVICE (ambi_path_compare_kernel): how close are two paths -- a reconstructed path against the simulated
+ * truth, a unit's path before indelBFB against the path after it, one cell's path against another cell's under --op sc_bfb.  A
+ * pair is two sides (A, B); a side is a unit's path ambi_batch_unit_path(unit, which), AMBI_COMPARE_UNIT(unit, which), or a path
+ * GIVEN by the caller in the local signed ids of whatever it is compared with, AMBI_COMPARE_GIVEN(t).  With the cells a[0..la) and
+ * b[0..lb) and the two orientations o = 0: B0 = b and o = 1: the reverse complement B1[i] = -b[lb-1-i]:
+ *   prefix[o]: the largest p with a[t] == Bo[t] for all t < p;
+ *   suffix[o]: the largest s <= min(la, lb) - prefix[o] with a[la-1-t] == Bo[lb-1-t] for all t < s;
+ *   dist[o]:   the fewest single-cell insertions plus deletions that turn a into Bo if that is <= dmax, otherwise -1;
+ *   lcs[o]:    (la + lb - dist[o]) / 2, the longest common subsequence, or -1 when dist[o] is -1.
+ * All fields are exact integers.  The common ends are trimmed and the rest goes through Myers' greedy diff, at most dmax rounds:
+ * the cost of a pair grows with its distance, not with the product of the lengths. */
+#define AMBI_COMPARE_UNIT(u, which) ((int32_t)(2 * (u) + (which)))
+#define AMBI_COMPARE_GIVEN(t) ((int32_t)~(t))
+#define AMBI_COMPARE_DMAX_CAP 1024
+#define AMBI_COMPARE_DMAX_DEFAULT 64
+typedef struct {
+    int32_t status;      /* 0; or the status of the first side that is a unit with a negative status or without a path
+                            (AMBI_ERR_BAD_INPUT for a unit without a path whose own status is not negative: a failure is never
+                            0): every field below but the lengths is then 0, dist and lcs are -1 */
+    int32_t len_a;       /* la (0 for a side that failed) */
+    int32_t len_b;       /* lb */
+    int32_t dmax;        /* the request's cap */
+    int32_t prefix[2];   /* [orientation] */
+    int32_t suffix[2];
+    int32_t dist[2];
+    int32_t lcs[2];
+} ambi_path_compare_t;
+/* The given paths of the batch: n paths, path t = cells[off[t] .. off[t+1]) in local signed ids (off has n + 1 entries, off[0] = 0).
+ * Replaces the earlier set; n = 0 drops it.  They are kept on the host and travel to a device buffer of their own with the next
+ * request; the batch image is not touched.  A request keeps the set it was made with: replacing the set between
+ * ambi_batch_path_compare and its wait does not change what that request compares.  AMBI_ERR_ARG for a cell that is 0 or beyond +-32767, or a path without a cell or with
+ * more than 4 194 304. */
+int ambi_batch_set_compare_paths(ambi_batch_t* b, const int32_t* cells, const int64_t* off, int32_t n);
+/* Queues the comparison of n_pairs pairs (pairs[2 i], pairs[2 i + 1]: the sides of pair i) over the LAST run's results behind
+ * that run on hip_stream: the given paths if the device does not hold them, the pairs, one kernel (a workgroup per pair), then one
+ * device-to-host copy of the block on the engine's copy stream: hip_stream is not blocked.  dmax: 0 .. AMBI_COMPARE_DMAX_CAP.
+ * AMBI_ERR_STATE before any run; AMBI_ERR_ARG for a side that names no unit, no `which` or no given path, or another dmax;
+ * AMBI_ERR_UNSUPPORTED after ambi_batch_run_sharded (a pair may span shares). */
+int ambi_batch_path_compare(ambi_batch_t* b, const int32_t* pairs, int32_t n_pairs, int32_t dmax, void* hip_stream);
+/* Blocks until the results are in host memory.  Makes the run's results final first (ambi_batch_wait) and compares once more if
+ * that changed them after the request was queued. */
+int ambi_batch_path_compare_wait(ambi_batch_t* b);
+/* The result of pair `pair` of the last request; AMBI_ERR_STATE without a waited-for comparison of the last run. */
+int ambi_batch_path_compare_result(const ambi_batch_t* b, int32_t pair, ambi_path_compare_t* out);
+/* The results in DEVICE memory, for collectives: ambi_path_compare_t[n_pairs], padded to 16 bytes.  Valid after
+ * ambi_batch_path_compare_wait until the next ambi_batch_path_compare. */
+int ambi_batch_path_compare_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
  * through `bedtools getfasta -s`, all records joined).
