@@ -96,6 +96,33 @@ def compare_all_pairs(sides):
     return np.array([(s[i], s[j]) for i in range(len(s)) for j in range(i + 1, len(s))], np.int32).reshape(-1, 2)
 
 
+class PathAlign(C.Structure):       # ambi_path_align_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "len_a", "len_b", "orient", "prefix", "suffix", "dist", "n_runs")]
+
+
+class AlignRun(C.Structure):        # ambi_align_run_t
+    _fields_ = [(k, C.c_int32) for k in ("a_pos", "b_pos", "len", "kind")]
+
+
+# the same as structured numpy dtypes (Batch.path_align_results), 32 and 16 bytes
+PATH_ALIGN_DTYPE = np.dtype([(k, np.int32) for k in ("status", "len_a", "len_b", "orient", "prefix", "suffix", "dist", "n_runs")])
+ALIGN_RUN_DTYPE = np.dtype([(k, np.int32) for k in ("a_pos", "b_pos", "len", "kind")])
+ALIGN_DMAX_CAP = 1024
+
+
+def align_from_compare(pairs, results):
+    """The triples (A, B, orient) for Batch.path_align from the pairs of a comparison and its results (Batch.path_compare_results):
+    every pair in the orientation with the smaller dist, ties as is; a pair whose two dist are both -1 is dropped.  An int32 array
+    [n, 3]."""
+    out = []
+    for (a, b), r in zip(np.asarray(pairs, np.int32).reshape(-1, 2).tolist(), results):
+        d0, d1 = int(r["dist"][0]), int(r["dist"][1])
+        if d0 < 0 and d1 < 0:
+            continue
+        out.append((a, b, 1 if d0 < 0 or 0 <= d1 < d0 else 0))
+    return np.array(out, np.int32).reshape(-1, 3)
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -199,6 +226,11 @@ def _declare(L):
         "ambi_batch_path_compare_wait": (C.c_int, [vp]),
         "ambi_batch_path_compare_result": (C.c_int, [vp, i32, _P(PathCompare)]),
         "ambi_batch_path_compare_device": (C.c_int, [vp, _P(vp), pi64]),
+        "ambi_batch_path_align": (C.c_int, [vp, pi32, i32, i32, vp]),
+        "ambi_batch_path_align_wait": (C.c_int, [vp]),
+        "ambi_batch_path_align_result": (C.c_int, [vp, i32, _P(PathAlign)]),
+        "ambi_batch_path_align_runs": (C.c_int, [vp, i32, _P(AlignRun), i32, pi32]),
+        "ambi_batch_path_align_device": (C.c_int, [vp, _P(vp), pi64, pi64]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
         "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
         "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
@@ -863,6 +895,41 @@ class Batch:
         p, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.ambi_batch_path_compare_device(self.h, C.byref(p), C.byref(n)), "path_compare_device")
         return p.value or 0, n.value
+
+    def path_align(self, triples, dmax=COMPARE_DMAX_DEFAULT, stream=None):
+        """Queues the alignment of the entries (an [n, 3] array: two sides as in path_compare, and the orientation 0 or 1;
+        align_from_compare makes them from a comparison) over the last run's paths behind that run (ambi_batch_path_align): per
+        entry a canonical shortest insert / delete script as maximal runs if the distance is at most dmax (0 .. 1024); `stream` is
+        not blocked."""
+        t = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+        self._ck(self.lib.ambi_batch_path_align(self.h, t.ctypes.data_as(_P(C.c_int32)), len(t), dmax, C.c_void_p(stream or 0)), "path_align")
+        self._n_aligned = len(t)                        # (of the request the engine took)
+
+    def path_align_wait(self):
+        """Waits for the alignment in host memory (the run's results are final first); path_align_results answers afterwards."""
+        self._ck(self.lib.ambi_batch_path_align_wait(self.h), "path_align_wait")
+
+    def path_align_results(self):
+        """(headers, runs) of the last request: a structured array (PATH_ALIGN_DTYPE) -- status, len_a, len_b, orient, prefix, suffix,
+        dist, n_runs -- and per entry a structured array (ALIGN_RUN_DTYPE) of its n_runs runs a_pos, b_pos, len, kind."""
+        self._ck(self.lib.ambi_batch_path_align_device(self.h, None, None, None), "path_align_results")   # (the state check: a waited-for request of the last run)
+        head = np.zeros(getattr(self, "_n_aligned", 0), PATH_ALIGN_DTYPE)
+        runs = []
+        r, n = PathAlign(), C.c_int32()
+        for i in range(len(head)):
+            self._ck(self.lib.ambi_batch_path_align_result(self.h, i, C.byref(r)), "path_align_results")
+            head[i] = np.frombuffer(bytes(r), PATH_ALIGN_DTYPE)[0]
+            out = np.zeros(r.n_runs, ALIGN_RUN_DTYPE)
+            self._ck(self.lib.ambi_batch_path_align_runs(self.h, i, out.ctypes.data_as(_P(AlignRun)), len(out), C.byref(n)), "path_align_results")
+            runs.append(out)
+        return head, runs
+
+    def path_align_device(self):
+        """(address, bytes, runs_off) of the results in device memory (ambi_batch_path_align_device), for collectives: the headers,
+        then at runs_off max(dmax, 1) run slots per entry."""
+        p, n, o = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.ambi_batch_path_align_device(self.h, C.byref(p), C.byref(n), C.byref(o)), "path_align_device")
+        return p.value or 0, n.value, o.value
 
     def set_unit_sequences(self, u, bases, seg_off):
         """Bases of a unit added with add_unit (ambi_batch_set_unit_sequences): local segment i + 1 = bases[seg_off[i]:seg_off[i + 1]]."""

@@ -11,6 +11,7 @@
 #include "ambi_fold_profile.hpp"
 #include "ambi_frag_profile.hpp"
 #include "ambi_junc_profile.hpp"
+#include "ambi_path_align.hpp"
 #include "ambi_path_compare.hpp"
 #include "ambi_profile.hpp"
 #include "ambi_sequence.hpp"
@@ -96,13 +97,14 @@ class Backend {
     // profile (ambi_fold_profile.hpp: the palindrome arm of every fold, how the arms nest, per junction its folds), each a block
     // [summary[U]][per unit counts]; the evidence kind has a depth area and the fold kind two planes beside the block that stay where
     // they were computed.  A sixth kind shares the life cycle but not the shape: the path comparison (ambi_path_compare.hpp) takes a list
-    // of pairs and a cap with the request (compare() below) and its block is [PathCompare[n_pairs]].
+    // of pairs and a cap with the request (compare() below) and its block is [PathCompare[n_pairs]].  The seventh, the path alignment
+    // (ambi_path_align.hpp), does the same with triples (align() below): [PathAlign[n_pairs]] [AlignRun[n_pairs * dmax]].
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
     // simulation); the HIP engine overrides the virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4, kCompare = 5 };
-    static constexpr int kProfileKinds = 6;
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4, kCompare = 5, kAlign = 6 };
+    static constexpr int kProfileKinds = 7;
     void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
     virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
@@ -112,7 +114,8 @@ class Backend {
         ProfileState& P = prof_[kind];
         profile_layout(kind);
         P.blob.assign((size_t)P.bytes, 0);
-        if (kind == kCompare) host_compare(blob.data(), P);
+        if (kind == kAlign) host_align(blob.data(), P);
+        else if (kind == kCompare) host_compare(blob.data(), P);
         else if (kind == kFold) host_fold_profile(blob.data(), which, P);
         else if (kind == kEvidence) host_evidence_profile(blob.data(), which, P);
         else if (kind == kFragment) host_frag_profile(blob.data(), which, P);
@@ -270,6 +273,36 @@ class Backend {
         return 0;
     }
 
+    // ---- path alignment (ambi_path_align.hpp): kAlign ----
+    // align() keeps the whole request as compare() does -- the triples (A, B, orient), the cap and a copy of the given paths of its
+    // own (aln_given_: the two kinds never share a copy, so neither a new set nor the other kind's request reaches a queued one).
+    // A run area above kAlignRunAreaCap is refused here, in front of any allocation.
+    int align(const ComparePaths* given, const int32_t* triples, int n_pairs, int dmax, void* stream) {
+        if (!given || n_pairs < 0 || (n_pairs > 0 && !triples) || dmax < 0 || dmax > kCompareDmaxCap) return ST_ERR_BAD_INPUT;
+        for (int64_t i = 0; i < (int64_t)n_pairs; i++) {
+            for (int q = 0; q < 2; q++) if (triples[3 * i + q] < 0 && ~triples[3 * i + q] >= given->n()) return ST_ERR_BAD_INPUT;
+            if (triples[3 * i + 2] < 0 || triples[3 * i + 2] > 1) return ST_ERR_BAD_INPUT;
+        }
+        if (align_run_area_bytes(n_pairs, dmax) > kAlignRunAreaCap) return kAlignTooLarge;
+        if (aln_given_.version != given->version) aln_given_ = *given;
+        aln_dmax_ = dmax;
+        aln_triples_.assign(triples, triples + 3 * (size_t)n_pairs);
+        return profile(kAlign, 1, stream);
+    }
+    static constexpr int kAlignTooLarge = kSeqTooLarge;   // AMBI_ERR_TOO_LARGE, as the sequence request's refusal
+    int align_pairs() const { return (int)(aln_triples_.size() / 3); }
+    int align_result(int pair, PathAlign* out) const {
+        const ProfileState& P = prof_[kAlign];
+        if (!P.view || pair < 0 || pair >= align_pairs() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const PathAlign*>(P.view)[pair];
+        return 0;
+    }
+    const AlignRun* align_runs(int pair) const {   // the pair's align_stride(dmax) slots, nullptr without a waited-for request
+        const ProfileState& P = prof_[kAlign];
+        if (!P.view || pair < 0 || pair >= align_pairs()) return nullptr;
+        return reinterpret_cast<const AlignRun*>(P.view + align_runs_off(align_pairs())) + (int64_t)pair * align_stride(aln_dmax_);
+    }
+
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
     // sequence() runs pass 0 of the extents stage behind the last run and fetches its totals (count x {bytes, runs}: the one small
     // device-to-host trip of a request), sizes the extent arrays and the output block from them, and queues pass 1 and the fill
@@ -348,7 +381,8 @@ class Backend {
     ProfileState prof_[kProfileKinds];   // [ProfileKind]
     void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
         ProfileState& P = prof_[kind];
-        if (kind == kCompare) { P.bytes = compare_block_bytes(compare_pairs()); P.off.clear(); }
+        if (kind == kAlign) { P.bytes = align_block_bytes(align_pairs(), aln_dmax_); P.off.clear(); }
+        else if (kind == kCompare) { P.bytes = compare_block_bytes(compare_pairs()); P.off.clear(); }
         else if (kind == kFold) { P.bytes = fold_block_layout(prof_hb_->units, P.off); plane_bytes_ = fold_plane_layout(prof_hb_->units, plane_off_); }
         else if (kind == kEvidence) { P.bytes = evidence_block_layout(prof_hb_->units, P.off); depth_bytes_ = evidence_depth_layout(prof_hb_->units, depth_off_); }
         else if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
@@ -410,6 +444,11 @@ class Backend {
     std::vector<int32_t> cmp_pairs_;
     int cmp_dmax_ = kCompareDmaxDefault;
     int compare_grid() const { return capped_window(compare_pairs(), kCompareGridCap, env_int("AMBI_COMPARE_GRID")); }
+    // the align kind's request (align()); its workgroups, each with a history area: AMBI_ALIGN_GRID (tests) can only shrink them
+    ComparePaths aln_given_;
+    std::vector<int32_t> aln_triples_;
+    int aln_dmax_ = kCompareDmaxDefault;
+    int align_grid_of() const { return align_grid(align_pairs(), aln_dmax_, env_int("AMBI_ALIGN_GRID")); }
   private:
     void host_profile(const uint8_t* blob, int which, ProfileState& P) {
         const std::vector<UnitIn>& units = prof_hb_->units;
@@ -479,6 +518,17 @@ class Backend {
         HostGroup g;
         for (int i = 0; i < compare_pairs(); i++)
             compare_pair(g, prof_hb_->units.data(), blob, given, cmp_pairs_.data(), i, cmp_dmax_, V.data(), reinterpret_cast<PathCompare*>(P.blob.data()));
+    }
+    void host_align(const uint8_t* blob, ProfileState& P) {
+        std::vector<Seq16A> image((size_t)(aln_given_.image_bytes() / 16) + 1);
+        uint8_t* img = reinterpret_cast<uint8_t*>(image.data());
+        aln_given_.image(img);
+        const CompareGiven given = compare_given(img, aln_given_);
+        std::vector<int32_t> lds((size_t)(align_lds_bytes(aln_dmax_) / 4)), hist((size_t)align_history_ints(aln_dmax_));
+        HostGroup g;
+        for (int i = 0; i < align_pairs(); i++)
+            align_pair(g, prof_hb_->units.data(), blob, given, aln_triples_.data(), i, aln_dmax_, lds.data(), lds.data() + compare_lds_bytes(aln_dmax_) / 4, hist.data(),
+                       reinterpret_cast<PathAlign*>(P.blob.data()), reinterpret_cast<AlignRun*>(P.blob.data() + align_runs_off(align_pairs())));
     }
     std::vector<Seq16A> depth_;          // the default implementation's depth area (16-byte aligned)
     std::vector<Seq16A> planes_;         // the default implementation's fold and cover planes (16-byte aligned)

@@ -115,7 +115,7 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
     ComparePaths cmp;         // the given paths of ambi_batch_set_compare_paths (ambi_path_compare.hpp); not part of the batch image
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
@@ -152,7 +152,7 @@ const char* ambi_error_string(int code) {
         case AMBI_ERR_HIP: return "HIP runtime error";
         case AMBI_ERR_STATE: return "call order violated";
         case AMBI_ERR_ARG: return "bad argument";
-        case AMBI_ERR_TOO_LARGE: return "the sequences of the unit range exceed max_bytes, or a unit's evidence depth bound reaches 2^31";
+        case AMBI_ERR_TOO_LARGE: return "the sequences of the unit range exceed max_bytes, a unit's evidence depth bound reaches 2^31, or an alignment's run area exceeds 1 GiB";
         default: return lh_error_string(code);
     }
 }
@@ -897,7 +897,7 @@ int ambi_batch_set_compare_paths(ambi_batch_t* b, const int32_t* cells, const in
         while (C.cells.size() & 3) C.cells.push_back((rcell_t)0);
     }
     C.version++;
-    b->profiled[Backend::kCompare] = false;
+    b->profiled[Backend::kCompare] = false; b->profiled[Backend::kAlign] = false;
     return 0;
 }
 int ambi_batch_path_compare(ambi_batch_t* b, const int32_t* pairs, int32_t n_pairs, int32_t dmax, void* hip_stream) {
@@ -928,6 +928,55 @@ int ambi_batch_path_compare_result(const ambi_batch_t* b, int32_t pair, ambi_pat
     static_assert(sizeof(ambi_path_compare_t) == sizeof(PathCompare), "ambi_path_compare_t is ambi::PathCompare");
     static_assert(sizeof(ambi_path_compare_t) == 48, "a pair's result is 48 bytes");
     return b->be->compare_result(pair, reinterpret_cast<PathCompare*>(out)) ? AMBI_ERR_STATE : 0;
+}
+// ---- path alignment (ambi_path_align.hpp): the request carries its triples and its cap, the life cycle is the profiles' ----
+int ambi_batch_path_align(ambi_batch_t* b, const int32_t* triples, int32_t n_pairs, int32_t dmax, void* hip_stream) {
+    if (!b || n_pairs < 0 || (n_pairs > 0 && !triples)) return AMBI_ERR_ARG;
+    if (b->sharded_ready) return AMBI_ERR_UNSUPPORTED;   // (a pair may span shares)
+    if (!(b->uploaded && b->ran)) return AMBI_ERR_STATE;
+    if (dmax < 0 || dmax > kCompareDmaxCap) return AMBI_ERR_ARG;
+    static_assert(AMBI_ALIGN_DMAX_CAP == kCompareDmaxCap, "anything the comparison can measure can be aligned");
+    const int64_t U = (int64_t)b->hb.units.size(), T = b->cmp.n();
+    for (int64_t i = 0; i < (int64_t)n_pairs; i++) {
+        for (int q = 0; q < 2; q++) {
+            const int64_t side = triples[3 * i + q];
+            if (side >= 0 ? side >= 2 * U : ~side >= T) return AMBI_ERR_ARG;
+        }
+        if (triples[3 * i + 2] < 0 || triples[3 * i + 2] > 1) return AMBI_ERR_ARG;
+    }
+    b->profiled[Backend::kAlign] = false;
+    const int rc = b->be->align(&b->cmp, triples, n_pairs, dmax, hip_stream);
+    static_assert(Backend::kAlignTooLarge == AMBI_ERR_TOO_LARGE, "align()'s refusal");
+    return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc;
+}
+int ambi_batch_path_align_wait(ambi_batch_t* b) {
+    if (b && b->sharded_ready) return AMBI_ERR_UNSUPPORTED;
+    return profile_wait(b, Backend::kAlign);
+}
+int ambi_batch_path_align_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* runs_off) {
+    const int rc = profile_device(b, Backend::kAlign, dev_ptr, bytes);
+    if (rc == 0 && runs_off) *runs_off = align_runs_off(b->be->align_pairs());
+    return rc;
+}
+int ambi_batch_path_align_result(const ambi_batch_t* b, int32_t pair, ambi_path_align_t* out) {
+    if (!b || !out) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kAlign]) return AMBI_ERR_STATE;
+    if (pair < 0 || pair >= b->be->align_pairs()) return AMBI_ERR_ARG;
+    static_assert(sizeof(ambi_path_align_t) == sizeof(PathAlign) && sizeof(ambi_path_align_t) == 32, "ambi_path_align_t is ambi::PathAlign, 32 bytes");
+    return b->be->align_result(pair, reinterpret_cast<PathAlign*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_path_align_runs(const ambi_batch_t* b, int32_t pair, ambi_align_run_t* out, int32_t cap, int32_t* n_runs) {
+    if (!b || !n_runs || cap < 0) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kAlign]) return AMBI_ERR_STATE;
+    if (pair < 0 || pair >= b->be->align_pairs()) return AMBI_ERR_ARG;
+    static_assert(sizeof(ambi_align_run_t) == sizeof(AlignRun) && sizeof(ambi_align_run_t) == 16, "ambi_align_run_t is ambi::AlignRun, 16 bytes");
+    PathAlign h;
+    const AlignRun* r = b->be->align_runs(pair);
+    if (!r || b->be->align_result(pair, &h)) return AMBI_ERR_STATE;
+    *n_runs = h.n_runs;
+    if (cap < h.n_runs || (h.n_runs > 0 && !out)) return AMBI_ERR_ARG;
+    if (h.n_runs > 0) memcpy(out, r, sizeof(AlignRun) * (size_t)h.n_runs);
+    return 0;
 }
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
 int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {

@@ -35,6 +35,10 @@
 //   ambi_path_compare_kernel      1 block / pair   on request: common ends and indel distance of pairs of paths, both orientations:
 //                                                  trim by whole-group sweeps, then Myers' greedy rounds up to dmax, long snakes by
 //                                                  whole wavefronts (ambi_path_compare.hpp)        <- both paths twice when the trim ends it
+//   ambi_path_align_kernel        1 block / pair   on request: the edit script of pairs of paths in one orientation as maximal runs:
+//                                                  the comparison's trim and rounds with every round's V kept in the workgroup's
+//                                                  history area, a one-thread traceback, a whole-group run merge
+//                                                  (ambi_path_align.hpp)                           <- the history: D^2 / 2 ints a pair
 //                                                  (the profile kernels share unit prologue, chunked cell read and window rule --
 //                                                  profile_path, path_load_chunk, capped_window of ambi_profile.hpp -- and the two tables
 //                                                  their probe, lds_find / lds_claim of ambi_junc_profile.hpp; every reader of a unit's
@@ -690,6 +694,21 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_path_compare_kernel(Batc
         __syncthreads();
     }
 }
+// ---- path alignment (ambi_path_align.hpp; launched by HipBackend::profile_queue only) ----
+// One workgroup of 256 threads per pair, grid-stride over the pairs.  Group memory: 256 bytes for the group's reductions, the diagonal
+// array V (2 * dmax + 3 ints) and the edit list (2 * dmax ints): 16652 bytes at the cap of 1024.  hist: one history area of
+// hist_bytes per workgroup, written and read by that workgroup only.
+__global__ __launch_bounds__(kProfileThreads) void ambi_path_align_kernel(BatchArgs A, CompareGiven given, const int32_t* triples, int n_pairs, int dmax, uint8_t* hist,
+                                                                          int64_t hist_bytes, PathAlign* head, AlignRun* runs) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    int32_t* V = reinterpret_cast<int32_t*>(ambi_lds + kProfileScratchBytes);
+    int32_t* E = V + (2 * dmax + 3);
+    int32_t* H = reinterpret_cast<int32_t*>(hist + (int64_t)blockIdx.x * hist_bytes);
+    for (int i = (int)blockIdx.x; i < n_pairs; i += (int)gridDim.x) {
+        align_pair(g, A.units, A.results, given, triples, i, dmax, V, E, H, head, runs);
+        __syncthreads();
+    }
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -842,6 +861,13 @@ struct Lease {
     uint8_t* d_cmp_img = nullptr; int64_t d_cmp_img_bytes = 0;
     uint8_t* h_cmp = nullptr; int64_t h_cmp_bytes = 0;
     hipEvent_t ev_cmp_up = nullptr;
+    // the align kind's: its own image of the given paths (the request's copy of the set: a set replaced for one kind never reaches a
+    // queued request of the other), and the workgroups' history areas, allocated at the first request of the kind.  The kind's block
+    // prof[kAlign] is [PathAlign[n_pairs]] [AlignRun[n_pairs * dmax]] with the request's triples behind it
+    uint8_t* d_aln_img = nullptr; int64_t d_aln_img_bytes = 0;
+    uint8_t* h_aln = nullptr; int64_t h_aln_bytes = 0;
+    hipEvent_t ev_aln_up = nullptr;
+    uint8_t* d_aln_hist = nullptr; int64_t d_aln_hist_bytes = 0;
     // the batch's fragment image (HipBackend::fragment_image) [cells][frag_off][cell_off][pref_off][n_frag], its pinned twin and the
     // event behind its last upload (the host writes the twin again only behind it)
     uint8_t* d_frag_img = nullptr; int64_t d_frag_img_bytes = 0;
@@ -1212,6 +1238,9 @@ class HipBackend : public Backend {
             if (L->d_planes_bytes > kKeepCells) { (void)hipFree(L->d_planes); L->d_planes = nullptr; L->d_planes_bytes = 0; }
             if (L->d_cmp_img_bytes > kKeepProfile) { (void)hipFree(L->d_cmp_img); L->d_cmp_img = nullptr; L->d_cmp_img_bytes = 0; }
             if (L->h_cmp_bytes > kKeepProfile) { (void)hipHostFree(L->h_cmp); L->h_cmp = nullptr; L->h_cmp_bytes = 0; }
+            if (L->d_aln_img_bytes > kKeepProfile) { (void)hipFree(L->d_aln_img); L->d_aln_img = nullptr; L->d_aln_img_bytes = 0; }
+            if (L->h_aln_bytes > kKeepProfile) { (void)hipHostFree(L->h_aln); L->h_aln = nullptr; L->h_aln_bytes = 0; }
+            if (L->d_aln_hist_bytes > kKeepProfile) { (void)hipFree(L->d_aln_hist); L->d_aln_hist = nullptr; L->d_aln_hist_bytes = 0; }
             if (L->d_frag_img_bytes > kKeepProfile) { (void)hipFree(L->d_frag_img); L->d_frag_img = nullptr; L->d_frag_img_bytes = 0; }
             if (L->h_frag_bytes > kKeepProfile) { (void)hipHostFree(L->h_frag); L->h_frag = nullptr; L->h_frag_bytes = 0; }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
@@ -1223,7 +1252,7 @@ class HipBackend : public Backend {
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; aln_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
 
@@ -1289,7 +1318,7 @@ class HipBackend : public Backend {
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; aln_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
         hbp_ = &hb_in; cfg_ = cfg;
@@ -2287,25 +2316,30 @@ class HipBackend : public Backend {
     }
     // The given paths of the compare kind (ComparePaths, ambi_path_compare.hpp) in a device buffer of their own: they go up on the
     // request's stream when the device does not hold this version of them (pinned twin, one copy), as the fragment image does.  The
-    // batch image is not touched.
-    int64_t cmp_img_version_ = -1;
-    CompareGiven cmp_args_{};
-    int compare_image(hipStream_t s) {
+    // batch image is not touched.  The align kind has the same of its own (its request's copy of the set, its buffer, twin and event).
+    int64_t cmp_img_version_ = -1, aln_img_version_ = -1;
+    CompareGiven cmp_args_{}, aln_args_{};
+    int compare_image(ProfileKind kind, hipStream_t s) {
         Lease* L = lease_;
-        const ComparePaths& I = cmp_given_;
+        const bool aln = kind == kAlign;
+        const ComparePaths& I = aln ? aln_given_ : cmp_given_;
+        uint8_t*& d = aln ? L->d_aln_img : L->d_cmp_img; int64_t& d_bytes = aln ? L->d_aln_img_bytes : L->d_cmp_img_bytes;
+        uint8_t*& h = aln ? L->h_aln : L->h_cmp; int64_t& h_bytes = aln ? L->h_aln_bytes : L->h_cmp_bytes;
+        hipEvent_t& ev_up = aln ? L->ev_aln_up : L->ev_cmp_up;
+        int64_t& version = aln ? aln_img_version_ : cmp_img_version_;
         const int64_t total = I.image_bytes();
-        if (cmp_img_version_ != I.version || !L->d_cmp_img) {
-            if (req_[kCompare].queued) HIP_CK(hipEventSynchronize(L->prof[kCompare].ev_done));   // (its kernel reads the buffer)
-            if (!L->ev_cmp_up) HIP_CK(hipEventCreateWithFlags(&L->ev_cmp_up, hipEventDisableTiming));
-            else HIP_CK(hipEventSynchronize(L->ev_cmp_up));   // (an earlier upload still reads the twin)
-            if (int rc = lease_device_block(&L->d_cmp_img, &L->d_cmp_img_bytes, total)) return rc;
-            if (int rc = lease_pinned_block(&L->h_cmp, nullptr, &L->h_cmp_bytes, total)) return rc;
-            I.image(L->h_cmp);
-            HIP_CK(hipMemcpyAsync(L->d_cmp_img, L->h_cmp, (size_t)total, hipMemcpyHostToDevice, s));
-            HIP_CK(hipEventRecord(L->ev_cmp_up, s));
-            cmp_img_version_ = I.version;
-        } else HIP_CK(hipStreamWaitEvent(s, L->ev_cmp_up, 0));   // (the upload may have gone up on another stream)
-        cmp_args_ = compare_given(L->d_cmp_img, I);
+        if (version != I.version || !d) {
+            if (req_[kind].queued) HIP_CK(hipEventSynchronize(L->prof[kind].ev_done));   // (its kernel reads the buffer)
+            if (!ev_up) HIP_CK(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
+            else HIP_CK(hipEventSynchronize(ev_up));   // (an earlier upload still reads the twin)
+            if (int rc = lease_device_block(&d, &d_bytes, total)) return rc;
+            if (int rc = lease_pinned_block(&h, nullptr, &h_bytes, total)) return rc;
+            I.image(h);
+            HIP_CK(hipMemcpyAsync(d, h, (size_t)total, hipMemcpyHostToDevice, s));
+            HIP_CK(hipEventRecord(ev_up, s));
+            version = I.version;
+        } else HIP_CK(hipStreamWaitEvent(s, ev_up, 0));   // (the upload may have gone up on another stream)
+        (aln ? aln_args_ : cmp_args_) = compare_given(d, I);
         return 0;
     }
     // The profiles are instances of one on-request block (Lease::prof, req_, Backend::prof_); a kind has its own layout, its own
@@ -2324,16 +2358,19 @@ class HipBackend : public Backend {
             }
             if (int rc = fragment_image(s)) return rc;
         }
-        const bool cmp = kind == kCompare;
-        const int64_t n_pairs = compare_pairs();
+        const bool aln = kind == kAlign, cmp = kind == kCompare || aln;   // (cmp: the request brings its entries, two or three int32 each)
+        const int64_t n_pairs = aln ? align_pairs() : compare_pairs();
+        const int aln_grid = align_grid_of();
+        const int64_t hist_bytes = align_history_bytes(aln_dmax_);
         if (cmp) {   // (pairs and cap come with the request: laid out every time, once the last request's copy and upload have left block and twin)
             if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done));
             R.laid_out = false;
-            if (int rc = compare_image(s)) return rc;
+            if (int rc = compare_image(kind, s)) return rc;
         }
+        if (aln) { if (int rc = lease_device_block(&L->d_aln_hist, &L->d_aln_hist_bytes, aln_grid * hist_bytes)) return rc; }   // (no kernel of the kind is in flight: waited for above)
         if (!R.laid_out) {
             profile_layout(kind);
-            const int64_t n_off = cmp ? n_pairs : kind == kEvidence || kind == kFold ? 2 * U : U;   // (the evidence and fold kinds: the depth area's or the planes' offsets behind the block's; the compare kind: the pairs, two int32 each)
+            const int64_t n_off = aln ? (3 * n_pairs + 1) / 2 : cmp ? n_pairs : kind == kEvidence || kind == kFold ? 2 * U : U;   // (the evidence and fold kinds: the depth area's or the planes' offsets behind the block's; the compare kind: the pairs, two int32 each)
             const int64_t total = P.bytes + n_off * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
             if (kind == kEvidence) { if (int rc = lease_device_block(&L->d_depth, &L->d_depth_bytes, depth_bytes_ > 0 ? depth_bytes_ : 16)) return rc; }
             if (kind == kFold) { if (int rc = lease_device_block(&L->d_planes, &L->d_planes_bytes, plane_bytes_ > 0 ? 2 * plane_bytes_ : 16)) return rc; }
@@ -2342,7 +2379,8 @@ class HipBackend : public Backend {
             if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
             for (hipEvent_t* e : {&B.ev_src, &B.ev_packed, &B.ev_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
             // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
-            if (cmp) { if (n_pairs > 0) memcpy(B.h + P.bytes, cmp_pairs_.data(), (size_t)n_pairs * sizeof(int64_t)); }
+            if (aln) { if (n_pairs > 0) memcpy(B.h + P.bytes, aln_triples_.data(), (size_t)n_pairs * 3 * sizeof(int32_t)); }
+            else if (cmp) { if (n_pairs > 0) memcpy(B.h + P.bytes, cmp_pairs_.data(), (size_t)n_pairs * sizeof(int64_t)); }
             else memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
             if (kind == kEvidence) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), depth_off_.data(), (size_t)U * sizeof(int64_t));
             if (kind == kFold) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), plane_off_.data(), (size_t)U * sizeof(int64_t));
@@ -2352,7 +2390,8 @@ class HipBackend : public Backend {
         }
         if (int rc = behind_results(s, B.ev_src)) return rc;
         int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes, fslots = 0, lds_mark = kProfileScratchBytes, fwin = 0;
-        if (cmp) lds += (int)compare_lds_bytes(cmp_dmax_);
+        if (aln) lds += (int)align_lds_bytes(aln_dmax_);
+        else if (cmp) lds += (int)compare_lds_bytes(cmp_dmax_);
         else if (kind == kFold) { fold_windows(&fwin, &jwin, &slots); lds_mark += (int)fold_arm_lds_bytes(fwin); lds += (int)fold_scan_lds_bytes(slots); }
         else if (kind == kEvidence) {
             frag_profile_windows(&pwin, &fslots); lds_mark += (int)frag_profile_lds_bytes(fslots, pwin);
@@ -2362,7 +2401,10 @@ class HipBackend : public Backend {
         else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
         if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
         const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        if (cmp) {   // (a workgroup per pair; a request without pairs launches nothing)
+        if (aln) {   // (a workgroup and a history area per pair in flight; a request without pairs launches nothing)
+            if (n_pairs > 0) hipLaunchKernelGGL(ambi_path_align_kernel, dim3(aln_grid), dim3(kProfileThreads), lds, s, A_, aln_args_, (const int32_t*)R.d_off, (int)n_pairs, aln_dmax_, L->d_aln_hist,
+                                                hist_bytes, reinterpret_cast<PathAlign*>(B.d), reinterpret_cast<AlignRun*>(B.d + align_runs_off(n_pairs)));
+        } else if (cmp) {   // (a workgroup per pair; a request without pairs launches nothing)
             if (n_pairs > 0) hipLaunchKernelGGL(ambi_path_compare_kernel, dim3(compare_grid()), dim3(kProfileThreads), lds, s, A_, cmp_args_, (const int32_t*)R.d_off, (int)n_pairs, cmp_dmax_, reinterpret_cast<PathCompare*>(B.d));
         } else if (kind == kFold) {   // (the scan kernel behind the arm kernel on one stream, as below)
             hipLaunchKernelGGL(ambi_fold_arm_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, which, fwin, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U));

@@ -147,10 +147,16 @@ AMBI_HD int compare_first_mismatch(const G& g, const rcell_t* a, int la, int a0,
     return L;
 }
 
+// What compare_rounds does with the V of a round that did not end the pair: nothing here; the alignment keeps it for its traceback
+// (AlignHistory, ambi_path_align.hpp).  row(g, d, klo, khi, Vk): whole group, behind the round's second barrier; Vk[k] is diagonal k.
+struct CompareNoHistory {
+    template <class G> AMBI_HD void row(const G&, int, int, int, const int32_t*) const {}
+};
+
 // The indel distance of the windows X[0..n) and Y[0..m), n > 0 and m > 0, if it is <= dmax, else -1.  V: 2 * dmax + 3 ints of group
 // memory.  Whole group.
-template <class G>
-AMBI_HD int compare_rounds(const G& g, const CompareSeq& X, int n, const CompareSeq& Y, int m, int dmax, int32_t* V) {
+template <class G, class H = CompareNoHistory>
+AMBI_HD int compare_rounds(const G& g, const CompareSeq& X, int n, const CompareSeq& Y, int m, int dmax, int32_t* V, const H& hist = H()) {
     const int tid = g.tid(), sz = g.size(), W = g.sub_size(), lane = g.sub_lane();
     const int off = dmax + 1, delta = n - m;
     g.sync();   // (V is read by the round that ended the pair or orientation before)
@@ -206,6 +212,7 @@ AMBI_HD int compare_rounds(const G& g, const CompareSeq& X, int n, const Compare
         }
         g.sync();
         if ((delta < 0 ? -delta : delta) <= d && ((delta + d) & 1) == 0 && V[off + delta] == n) return d;   // (uniform: read behind the barrier)
+        hist.row(g, d, klo, khi, V + off);
     }
     return -1;
 }

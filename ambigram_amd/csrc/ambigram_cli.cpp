@@ -4,6 +4,7 @@
 // the external `cbc`, appended simulation_sv.txt and time.csv), same exit codes for unreadable .lh / missing .sol.
 // The per-chromosome stages run on the GPU through libambigram_hip.so; the ILP model is built on the host
 // (ambi_ilp_build) and solved by whatever `cbc` is on PATH, exactly as the reference shells out (localhap.cpp:179-181).
+#include <algorithm>
 #include <cctype>
 #include <chrono>
 #include <cstdint>
@@ -282,6 +283,11 @@ int run_sc_bfb(Args& A) {
 // truth file has one line per chromosome in printing order: a path as it is printed here (`|` is ignored, ids are global), or `.`
 // for none; an id outside the chromosome, a missing line or a line that is no path is an error found when the sample is read, in front of the run.  N: 0 .. 1024, default 64; a distance above it is -1.  stdout and the side
 // files are unchanged.
+// --path_align <file> (with --path_compare; where do the two paths differ?): behind the comparison every P and T row is aligned on the
+// device (ambi_batch_path_align, one request, the cap of --compare_dmax) in the orientation with the smaller dist, ties as is.  Per
+// row a header line -- A, the row's tag, chromosome index, orient, dist, n_runs -- then one line per run: D or I, a_pos, b_pos, len
+// and the run's cells (of a for D, of Bo for I) as a printed path with global ids.  A row whose two dist are both -1 gets the header
+// alone, with orient -1, dist -1 and 0 runs.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -324,6 +330,8 @@ int run_bfb(Args& A) {
     const int compare_dmax = A.kv.count("compare_dmax") ? atoi(A.kv["compare_dmax"].c_str()) : AMBI_COMPARE_DMAX_DEFAULT;
     if (path_compare.empty() && (!truth.empty() || A.kv.count("compare_dmax"))) { std::cerr << "--truth and --compare_dmax go with --path_compare <file>" << std::endl; return 2; }
     if (!path_compare.empty() && (compare_dmax < 0 || compare_dmax > AMBI_COMPARE_DMAX_CAP)) { std::cerr << "--compare_dmax: 0 .. " << AMBI_COMPARE_DMAX_CAP << std::endl; return 2; }
+    const std::string path_align = A.kv.count("path_align") ? A.kv["path_align"] : "";
+    if (path_compare.empty() && !path_align.empty()) { std::cerr << "--path_align goes with --path_compare <file>" << std::endl; return 2; }
     if (!path_compare.empty() && A.kv.count("devices")) { std::cerr << "--path_compare: not available with --devices (a pair may span shares)" << std::endl; return 2; }
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
@@ -692,6 +700,51 @@ int run_bfb(Args& A) {
                     r.prefix[0], r.prefix[1], r.suffix[0], r.suffix[1], r.dist[0], r.dist[1], r.lcs[0], r.lcs[1]);
         }
         fclose(pf);
+        if (!path_align.empty()) {
+            // every row in the orientation with the smaller dist (ties as is), one request; a row with both dist -1 is not aligned
+            std::vector<int32_t> triples;
+            std::vector<int> entry(rows.size(), -1);   // row -> entry of the request
+            for (size_t i = 0; i < rows.size(); i++) {
+                ambi_path_compare_t r;
+                if ((rc = ambi_batch_path_compare_result(b, (int32_t)i, &r)) != 0) return die(std::string("engine: ") + ambi_error_string(rc));
+                if (r.dist[0] < 0 && r.dist[1] < 0) continue;
+                entry[i] = (int)(triples.size() / 3);
+                triples.insert(triples.end(), {pairs[2 * i], pairs[2 * i + 1], r.dist[0] < 0 || (r.dist[1] >= 0 && r.dist[1] < r.dist[0]) ? 1 : 0});
+            }
+            if ((rc = ambi_batch_path_align(b, triples.data(), (int32_t)(triples.size() / 3), compare_dmax, nullptr)) != 0 || (rc = ambi_batch_path_align_wait(b)) != 0)
+                return die(std::string("engine: ") + ambi_error_string(rc));
+            FILE* af = fopen(path_align.c_str(), "w");
+            if (!af) return die("Cannot open file " + path_align);
+            auto fail = [&](int code) { fclose(af); return die(std::string("engine: ") + ambi_error_string(code)); };
+            for (size_t i = 0; i < rows.size(); i++) {
+                const Row& W = rows[i];
+                Sample& S = samples[W.si];
+                if (entry[i] < 0) { fprintf(af, "A\t%c\t%d\t-1\t-1\t0\n", W.tag, W.c); continue; }
+                ambi_path_align_t h;
+                if ((rc = ambi_batch_path_align_result(b, entry[i], &h)) != 0) return fail(rc);
+                fprintf(af, "A\t%c\t%d\t%d\t%d\t%d\n", W.tag, W.c, h.orient, h.dist, h.n_runs);
+                if (h.n_runs == 0) continue;
+                std::vector<ambi_align_run_t> runs((size_t)h.n_runs);
+                int32_t nr = 0;
+                if ((rc = ambi_batch_path_align_runs(b, entry[i], runs.data(), h.n_runs, &nr)) != 0) return fail(rc);
+                // the two sides in global ids: a, and Bo (b, or its reverse complement)
+                int32_t s0, e0;
+                ambi_graph_chromosome(S.g, W.c, &s0, &e0);
+                ambi_unit_result_t ur; ambi_batch_unit_result(b, S.unit[W.c], &ur);
+                std::vector<int32_t> pa((size_t)(W.tag == 'P' ? ur.path_len : ur.path_indel_len)), pb;
+                ambi_batch_unit_path(b, S.unit[W.c], W.tag == 'P' ? 0 : 1, pa.data(), (int32_t)pa.size());
+                if (W.tag == 'P') { pb.resize((size_t)ur.path_indel_len); ambi_batch_unit_path(b, S.unit[W.c], 1, pb.data(), (int32_t)pb.size()); }
+                else for (int32_t v : truth_cells[(size_t)W.c]) pb.push_back(v > 0 ? v + s0 - 1 : v - s0 + 1);
+                if (h.orient) { std::reverse(pb.begin(), pb.end()); for (int32_t& v : pb) v = -v; }
+                for (const ambi_align_run_t& q : runs) {
+                    const std::vector<int32_t>& from = q.kind ? pb : pa;
+                    const int32_t at = q.kind ? q.b_pos : q.a_pos;
+                    if (at < 0 || q.len < 1 || (size_t)at + (size_t)q.len > from.size()) return fail(AMBI_ERR_STATE);
+                    fprintf(af, "%c\t%d\t%d\t%d\t%s\n", q.kind ? 'I' : 'D', q.a_pos, q.b_pos, q.len, path_text(S.g, std::vector<int32_t>(from.begin() + at, from.begin() + at + q.len)).c_str());
+                }
+            }
+            fclose(af);
+        }
     }
     if (!out_fasta.empty()) {
         FILE* ff = fopen(out_fasta.c_str(), "w");
@@ -881,7 +934,7 @@ int main(int argc, char** argv) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
                      "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--evidence_profile <file>] [--evidence_depth <file>] [--fold_profile <file>] [--fold_arms <file>] "
-                     "[--path_compare <file> [--truth <file>] [--compare_dmax N]] [--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--path_compare <file> [--truth <file>] [--compare_dmax N] [--path_align <file>]] [--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
@@ -908,6 +961,10 @@ int main(int argc, char** argv) {
                      "orientation as is and for the reverse complement (dist: insertions plus deletions, -1 above N; N 0..1024, default 64); with --truth a T row "
                      "per chromosome, the final path against that chromosome's line of the truth file (a printed path with global ids, or `.`; one sample only) "
                      "(PROP I1 / C1 / I2 / C2 samples and --devices are refused, exit status 2)\n"
+                     "  --path_align <file> (with --path_compare): where the two paths of every P and T row differ, aligned on the device in the orientation with "
+                     "the smaller dist (ties as is) at the cap of --compare_dmax: per row a header line A, tag, chromosome index, orient, dist, n_runs, then one "
+                     "line per maximal run of insertions or deletions: D or I, a_pos, b_pos, len and the run's cells as a printed path (a row with both dist -1: "
+                     "the header alone, orient -1, dist -1, 0 runs)\n"
                      "  --ref_fasta <file> --out_fasta <file> (--op bfb): the nucleotide sequence of every chromosome's final path, one record per chromosome "
                      "(>BFBPATH, or >BFBPATH_<chromosome> when the sample has several), from the segments' bases chrom[start..end) of the reference FASTA "
                      "(0-based, half-open); PROP I1 / C1 / I2 / C2 samples are refused, exit status 2; --fasta_chunk_bytes <n>: bytes assembled per request\n";

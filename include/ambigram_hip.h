@@ -60,7 +60,7 @@ extern "C" {
 #define AMBI_ERR_HIP (-31)
 #define AMBI_ERR_STATE (-32)      /* call order violated (e.g. run before upload) */
 #define AMBI_ERR_ARG (-33)
-#define AMBI_ERR_TOO_LARGE (-34)  /* ambi_batch_sequence: the unit range's sequences exceed max_bytes; ambi_batch_evidence_profile: a depth bound of 2^31 */
+#define AMBI_ERR_TOO_LARGE (-34)  /* ambi_batch_sequence: the unit range's sequences exceed max_bytes; ambi_batch_evidence_profile: a depth bound of 2^31; ambi_batch_path_align: a run area above 1 GiB */
 /* ambi_graph_read_fasta */
 #define AMBI_ERR_FASTA_OPEN (-40)   /* cannot open the FASTA file */
 #define AMBI_ERR_FASTA_CHROM (-41)  /* a segment's chromosome is not a record of the file */
@@ -580,6 +580,56 @@ int ambi_batch_path_compare_result(const ambi_batch_t* b, int32_t pair, ambi_pat
 /* The results in DEVICE memory, for collectives: ambi_path_compare_t[n_pairs], padded to 16 bytes.  Valid after
  * ambi_batch_path_compare_wait until the next ambi_batch_path_compare. */
 int ambi_batch_path_compare_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes);
+
+/* Path alignment ON THE DEVICE (ambi_path_align_kernel): WHERE do two paths differ, and by which cells -- a canonical shortest
+ * insert / delete script of every pair, in ONE orientation per pair, as maximal runs.  An entry is a triple (A, B, orient): A and B
+ * are sides as in the path comparison (AMBI_COMPARE_UNIT / AMBI_COMPARE_GIVEN over the set of ambi_batch_set_compare_paths), orient
+ * is 0 (as is) or 1 (against the reverse complement Bo[i] = -b[lb-1-i]).  A caller who does not know the orientation asks the
+ * comparison first and takes the smaller dist.  prefix, suffix and dist are the comparison's for that orientation.  The script is
+ * the traceback of Myers' greedy rounds over the windows between the common ends, ties to the insertion; a unit edit either deletes
+ * a[a_pos] (kind 0; b_pos: the cell of Bo in front of which it would stand) or inserts Bo[b_pos] in front of a[a_pos] (kind 1), in
+ * the coordinates of the whole a and the whole Bo.  Consecutive unit edits of one kind with no matched cell between them form one
+ * maximal run: a_pos advances through a deletion run and b_pos stays; the other way round for insertions.  A deletion directly
+ * followed by an insertion stays two runs.  Applying the runs to a in order gives Bo; the lengths sum to dist; a pair has at most
+ * dist runs. */
+#define AMBI_ALIGN_DMAX_CAP 1024
+typedef struct {
+    int32_t status;      /* as ambi_path_compare_t: 0, or the first failing side's status (never 0 for a failure); prefix and suffix
+                            are then 0, dist is -1 and n_runs 0 */
+    int32_t len_a;       /* la (0 for a side that failed) */
+    int32_t len_b;       /* lb */
+    int32_t orient;      /* the entry's orientation */
+    int32_t prefix;
+    int32_t suffix;
+    int32_t dist;        /* insertions plus deletions if that is <= dmax, otherwise -1 */
+    int32_t n_runs;      /* 0 when dist is -1 */
+} ambi_path_align_t;
+typedef struct {
+    int32_t a_pos;       /* the first cell of a the run deletes / the cell of a in front of which it inserts */
+    int32_t b_pos;       /* the cell of Bo in front of which the deleted cells would stand / the first cell of Bo it inserts */
+    int32_t len;
+    int32_t kind;        /* 0: deletion, 1: insertion */
+} ambi_align_run_t;
+/* Queues the alignment of n_pairs entries (triples[3 i .. 3 i + 3) = A, B, orient) over the LAST run's results behind that run on
+ * hip_stream, as ambi_batch_path_compare queues its pairs: the given paths if the device does not hold them, the triples, one kernel
+ * (a workgroup per pair, each with a history area of (dmax + 1)(dmax + 2) / 2 ints in device memory), then one device-to-host copy of
+ * the block on the engine's copy stream.  dmax: 0 .. AMBI_ALIGN_DMAX_CAP (AMBI_COMPARE_DMAX_DEFAULT is a good default).  The request
+ * keeps the set of given paths it was made with.  AMBI_ERR_STATE before any run; AMBI_ERR_ARG for a side that names no unit, no
+ * `which` or no given path, an orientation other than 0 and 1, or another dmax; AMBI_ERR_TOO_LARGE when the run area,
+ * 16 * n_pairs * max(dmax, 1) bytes, exceeds 1 GiB (nothing is queued); AMBI_ERR_UNSUPPORTED after ambi_batch_run_sharded. */
+int ambi_batch_path_align(ambi_batch_t* b, const int32_t* triples, int32_t n_pairs, int32_t dmax, void* hip_stream);
+/* Blocks until the results are in host memory.  Makes the run's results final first (ambi_batch_wait) and aligns once more if that
+ * changed them after the request was queued. */
+int ambi_batch_path_align_wait(ambi_batch_t* b);
+/* The header of entry `pair` of the last request; AMBI_ERR_STATE without a waited-for alignment of the last run. */
+int ambi_batch_path_align_result(const ambi_batch_t* b, int32_t pair, ambi_path_align_t* out);
+/* The runs of entry `pair`: *n_runs = their number; out[0 .. n_runs) are written when cap >= n_runs (AMBI_ERR_ARG for a smaller
+ * cap with *n_runs set, so a caller can ask with cap = 0 first; out may be NULL then). */
+int ambi_batch_path_align_runs(const ambi_batch_t* b, int32_t pair, ambi_align_run_t* out, int32_t cap, int32_t* n_runs);
+/* The results in DEVICE memory, for collectives: ambi_path_align_t[n_pairs] padded to 16 bytes, then at *runs_off
+ * ambi_align_run_t[n_pairs * max(dmax, 1)] -- a fixed stride of max(dmax, 1) runs per entry, so the layout does not depend on the
+ * results; the slots at and behind n_runs are zero.  Valid after ambi_batch_path_align_wait until the next ambi_batch_path_align. */
+int ambi_batch_path_align_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* runs_off);
 
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
