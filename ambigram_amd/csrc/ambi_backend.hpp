@@ -4,6 +4,7 @@
 // in ambigram_amd/ and never selected at run time.
 #pragma once
 #include <stdint.h>
+#include <initializer_list>
 #include <vector>
 
 #include "ambi_pack.hpp"
@@ -90,15 +91,23 @@ class Backend {
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
 
     // ---- on-request profiles of every unit's path (which: 0 getBFB, 1 after indelBFB) ----
-    // Five kinds, one life cycle: the copy-number profile (ambi_profile.hpp: per-segment traversal counts per strand), the
-    // junction usage profile (ambi_junc_profile.hpp: per-junction traversal counts), the fragment support profile
-    // (ambi_frag_profile.hpp: occurrences of every .juncs fragment in either direction), the evidence depth profile
-    // (ambi_evidence_profile.hpp: fragment occurrences over every step, per junction its covered traversals) and the fold-back arm
-    // profile (ambi_fold_profile.hpp: the palindrome arm of every fold, how the arms nest, per junction its folds), each a block
-    // [summary[U]][per unit counts]; the evidence kind has a depth area and the fold kind two planes beside the block that stay where
-    // they were computed.  A sixth kind shares the life cycle but not the shape: the path comparison (ambi_path_compare.hpp) takes a list
-    // of pairs and a cap with the request (compare() below) and its block is [PathCompare[n_pairs]].  The seventh, the path alignment
-    // (ambi_path_align.hpp), does the same with triples (align() below): [PathAlign[n_pairs]] [AlignRun[n_pairs * dmax]].
+    // Seven kinds, one life cycle.  A kind is a block that travels to the host, a tail behind it that travels up once per layout (int64
+    // offsets per unit, or the request's entries), a side area that stays where it was computed, an image that goes up when the device
+    // holds another version of it, and its kernels (U: units; [..]: arrays padded to 16 bytes):
+    //   kind         block                                               tail                  side area                   image      kernels (ambi_*_kernel)
+    //   kCopyNumber  [UnitProfile[U]] per unit [fwd][rev]                off[U]                -                           -          path_profile
+    //   kJunction    [UnitJuncProfile[U]] per unit [count]               off[U]                -                           -          junc_profile
+    //   kFragment    [UnitFragProfile[U]] per unit [fwd][rev][first]     off[U]                -                           fragment   frag_profile
+    //   kEvidence    [UnitEvidenceProfile[U]] per unit [count][covered]  off[U], depth_off[U]  depth: int32 per cell of    fragment   evidence_mark, evidence_scan
+    //                [min_depth]                                                               every unit's path capacity
+    //   kFold        [UnitFoldProfile[U]] per unit [folds][max_arm]      off[U], plane_off[U]  fold plane, then cover      -          fold_arm, fold_scan
+    //                                                                                          plane, each as the depth
+    //   kCompare     [PathCompare[n]]                                    n pairs (A, B)        -                           its given  path_compare
+    //   kAlign       [PathAlign[n]] [AlignRun[n * dmax]]                 n triples (A, B, o)   a history area per          its given  path_align
+    //                                                                                          workgroup
+    // (stage code: ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp, ambi_evidence_profile.hpp, ambi_fold_profile.hpp,
+    // ambi_path_compare.hpp, ambi_path_align.hpp.)
+    // The last two bring their entries and a cap with the request (compare() and align() below) and are laid out with every request.
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
     // simulation); the HIP engine overrides the virtual entries with its kernels and never reaches it.
@@ -114,13 +123,15 @@ class Backend {
         ProfileState& P = prof_[kind];
         profile_layout(kind);
         P.blob.assign((size_t)P.bytes, 0);
-        if (kind == kAlign) host_align(blob.data(), P);
-        else if (kind == kCompare) host_compare(blob.data(), P);
-        else if (kind == kFold) host_fold_profile(blob.data(), which, P);
-        else if (kind == kEvidence) host_evidence_profile(blob.data(), which, P);
-        else if (kind == kFragment) host_frag_profile(blob.data(), which, P);
-        else if (kind == kJunction) host_junc_profile(blob.data(), which, P);
-        else host_profile(blob.data(), which, P);
+        switch (kind) {
+            case kCopyNumber: host_profile(blob.data(), which, P); break;
+            case kJunction: host_junc_profile(blob.data(), which, P); break;
+            case kFragment: host_frag_profile(blob.data(), which, P); break;
+            case kEvidence: host_evidence_profile(blob.data(), which, P); break;
+            case kFold: host_fold_profile(blob.data(), which, P); break;
+            case kCompare: host_compare(blob.data(), P); break;
+            case kAlign: host_align(blob.data(), P); break;
+        }
         P.view = nullptr;
         return 0;
     }
@@ -138,73 +149,39 @@ class Backend {
         if (bytes) *bytes = P.bytes;
         return 0;
     }
-    int profile_summary(int unit, UnitProfile* out) const {
-        const ProfileState& P = prof_[kCopyNumber];
+    // The typed getters: a unit's summary, and `n` int32 values from each of the unit's arrays (arr_bytes apart) to every destination
+    // that is not nullptr; counts_of returns n, and refuses n < 0 (unit_n: the bound batch has no such unit) and cap < n.
+    template <class T> int summary_of(ProfileKind kind, int unit, T* out) const {
+        const ProfileState& P = prof_[kind];
         if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitProfile*>(P.view)[unit];
+        *out = reinterpret_cast<const T*>(P.view)[unit];
         return 0;
     }
+    int counts_of(ProfileKind kind, int unit, int n, int cap, int64_t arr_bytes, std::initializer_list<int32_t*> to) const {
+        const ProfileState& P = prof_[kind];
+        if (!P.view || unit < 0 || unit >= (int)P.off.size() || n < 0 || cap < n) return ST_ERR_BAD_INPUT;
+        const uint8_t* p = P.view + P.off[(size_t)unit];
+        for (int32_t* dst : to) { if (dst && n > 0) memcpy(dst, p, sizeof(int32_t) * (size_t)n); p += arr_bytes; }
+        return n;
+    }
+    int unit_n(int unit, int32_t UnitIn::*what, int more = 0) const { return prof_hb_ && unit >= 0 && (size_t)unit < prof_hb_->units.size() ? prof_hb_->units[(size_t)unit].*what + more : -1; }
+    int unit_frags(int unit) const { return prof_hb_ && unit >= 0 && (size_t)unit < prof_hb_->frag.n_frag.size() ? prof_hb_->frag.n_frag[(size_t)unit] : -1; }
+    int profile_summary(int unit, UnitProfile* out) const { return summary_of(kCopyNumber, unit, out); }
     int profile_counts(int unit, int32_t* fwd, int32_t* rev, int cap) const {   // n + 1 counts each; returns n + 1
-        const ProfileState& P = prof_[kCopyNumber];
-        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
-        const int n = prof_hb_->units[(size_t)unit].n_seg;
-        if (cap < n + 1) return ST_ERR_BAD_INPUT;
-        const uint8_t* p = P.view + P.off[(size_t)unit];
-        if (fwd) memcpy(fwd, p, sizeof(int32_t) * (size_t)(n + 1));
-        if (rev) memcpy(rev, p + profile_rev_off(n), sizeof(int32_t) * (size_t)(n + 1));
-        return n + 1;
+        const int n1 = unit_n(unit, &UnitIn::n_seg, 1);
+        return counts_of(kCopyNumber, unit, n1, cap, profile_rev_off(n1 - 1), {fwd, rev});
     }
-    int junc_profile_summary(int unit, UnitJuncProfile* out) const {
-        const ProfileState& P = prof_[kJunction];
-        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitJuncProfile*>(P.view)[unit];
-        return 0;
-    }
-    int junc_profile_counts(int unit, int32_t* count, int cap) const {   // m counts; returns m
-        const ProfileState& P = prof_[kJunction];
-        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
-        const int m = prof_hb_->units[(size_t)unit].n_junc;
-        if (cap < m) return ST_ERR_BAD_INPUT;
-        if (count && m > 0) memcpy(count, P.view + P.off[(size_t)unit], sizeof(int32_t) * (size_t)m);
-        return m;
-    }
-
-    int frag_profile_summary(int unit, UnitFragProfile* out) const {
-        const ProfileState& P = prof_[kFragment];
-        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitFragProfile*>(P.view)[unit];
-        return 0;
-    }
+    int junc_profile_summary(int unit, UnitJuncProfile* out) const { return summary_of(kJunction, unit, out); }
+    int junc_profile_counts(int unit, int32_t* count, int cap) const { return counts_of(kJunction, unit, unit_n(unit, &UnitIn::n_junc), cap, 0, {count}); }   // m counts; returns m
+    int frag_profile_summary(int unit, UnitFragProfile* out) const { return summary_of(kFragment, unit, out); }
     int frag_profile_counts(int unit, int32_t* fwd, int32_t* rev, int32_t* first, int cap) const {   // F values each; returns F
-        const ProfileState& P = prof_[kFragment];
-        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size() || (size_t)unit >= prof_hb_->frag.n_frag.size()) return ST_ERR_BAD_INPUT;
-        const int F = prof_hb_->frag.n_frag[(size_t)unit];
-        if (cap < F) return ST_ERR_BAD_INPUT;
-        const uint8_t* p = P.view + P.off[(size_t)unit];
-        const int64_t arr = frag_profile_arr_bytes(F);
-        if (fwd && F > 0) memcpy(fwd, p, sizeof(int32_t) * (size_t)F);
-        if (rev && F > 0) memcpy(rev, p + arr, sizeof(int32_t) * (size_t)F);
-        if (first && F > 0) memcpy(first, p + 2 * arr, sizeof(int32_t) * (size_t)F);
-        return F;
+        const int F = unit_frags(unit);
+        return counts_of(kFragment, unit, F, cap, frag_profile_arr_bytes(F), {fwd, rev, first});
     }
-
-    int evidence_summary(int unit, UnitEvidenceProfile* out) const {
-        const ProfileState& P = prof_[kEvidence];
-        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitEvidenceProfile*>(P.view)[unit];
-        return 0;
-    }
+    int evidence_summary(int unit, UnitEvidenceProfile* out) const { return summary_of(kEvidence, unit, out); }
     int evidence_counts(int unit, int32_t* count, int32_t* covered, int32_t* min_depth, int cap) const {   // m values each; returns m
-        const ProfileState& P = prof_[kEvidence];
-        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
-        const int m = prof_hb_->units[(size_t)unit].n_junc;
-        if (cap < m) return ST_ERR_BAD_INPUT;
-        const uint8_t* p = P.view + P.off[(size_t)unit];
-        const int64_t arr = evidence_arr_bytes(m);
-        if (count && m > 0) memcpy(count, p, sizeof(int32_t) * (size_t)m);
-        if (covered && m > 0) memcpy(covered, p + arr, sizeof(int32_t) * (size_t)m);
-        if (min_depth && m > 0) memcpy(min_depth, p + 2 * arr, sizeof(int32_t) * (size_t)m);
-        return m;
+        const int m = unit_n(unit, &UnitIn::n_junc);
+        return counts_of(kEvidence, unit, m, cap, evidence_arr_bytes(m), {count, covered, min_depth});
     }
     // the depths of the steps [first, first + n) of a unit to host memory (nothing else of the depth area travels), and the area where
     // it was computed (device memory of the HIP engine) with every unit's byte offset in it; valid after profile_wait(kEvidence)
@@ -220,21 +197,10 @@ class Backend {
         return evidence_depth_offsets(bytes, unit_off, cap);
     }
 
-    int fold_summary(int unit, UnitFoldProfile* out) const {
-        const ProfileState& P = prof_[kFold];
-        if (!P.view || unit < 0 || unit >= (int)P.off.size() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const UnitFoldProfile*>(P.view)[unit];
-        return 0;
-    }
+    int fold_summary(int unit, UnitFoldProfile* out) const { return summary_of(kFold, unit, out); }
     int fold_counts(int unit, int32_t* folds, int32_t* max_arm, int cap) const {   // m values each; returns m
-        const ProfileState& P = prof_[kFold];
-        if (!P.view || !prof_hb_ || unit < 0 || unit >= (int)P.off.size()) return ST_ERR_BAD_INPUT;
-        const int m = prof_hb_->units[(size_t)unit].n_junc;
-        if (cap < m) return ST_ERR_BAD_INPUT;
-        const uint8_t* p = P.view + P.off[(size_t)unit];
-        if (folds && m > 0) memcpy(folds, p, sizeof(int32_t) * (size_t)m);
-        if (max_arm && m > 0) memcpy(max_arm, p + fold_arr_bytes(m), sizeof(int32_t) * (size_t)m);
-        return m;
+        const int m = unit_n(unit, &UnitIn::n_junc);
+        return counts_of(kFold, unit, m, cap, fold_arr_bytes(m), {folds, max_arm});
     }
     // the entries [first, first + n) of a unit's plane (0: fold, 1: cover) to host memory (nothing else of the plane area travels),
     // and the area where it was computed (device memory of the HIP engine: both planes, `bytes` in all, plane p of unit u at
@@ -251,56 +217,32 @@ class Backend {
         return fold_plane_offsets(bytes, unit_off, cap);
     }
 
-    // ---- path comparison (ambi_path_compare.hpp): kCompare ----
-    // compare() keeps the WHOLE request -- the pairs' sides (2 * unit + which, or ~t for the t-th given path), the cap and a copy of
-    // the given paths as they were when it was made -- and queues it as the other kinds are queued (profile(kCompare)).  A request that
-    // profile_wait() has to queue again finds all of it here: the caller may replace its set of given paths between a request and
-    // its wait, and the request still compares what it named.  The copy is taken only when the caller's set has another version.
-    // A given side beyond the copied set is refused here as well, whatever the caller checked.
-    int compare(const ComparePaths* given, const int32_t* pairs, int n_pairs, int dmax, void* stream) {
-        if (!given || n_pairs < 0 || (n_pairs > 0 && !pairs) || dmax < 0 || dmax > kCompareDmaxCap) return ST_ERR_BAD_INPUT;
-        for (int64_t i = 0; i < 2 * (int64_t)n_pairs; i++) if (pairs[i] < 0 && ~pairs[i] >= given->n()) return ST_ERR_BAD_INPUT;
-        if (cmp_given_.version != given->version) cmp_given_ = *given;
-        cmp_dmax_ = dmax;
-        cmp_pairs_.assign(pairs, pairs + 2 * (size_t)n_pairs);
-        return profile(kCompare, 1, stream);
-    }
-    int compare_pairs() const { return (int)(cmp_pairs_.size() / 2); }
-    int compare_result(int pair, PathCompare* out) const {
-        const ProfileState& P = prof_[kCompare];
-        if (!P.view || pair < 0 || pair >= compare_pairs() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const PathCompare*>(P.view)[pair];
-        return 0;
-    }
-
-    // ---- path alignment (ambi_path_align.hpp): kAlign ----
-    // align() keeps the whole request as compare() does -- the triples (A, B, orient), the cap and a copy of the given paths of its
-    // own (aln_given_: the two kinds never share a copy, so neither a new set nor the other kind's request reaches a queued one).
-    // A run area above kAlignRunAreaCap is refused here, in front of any allocation.
-    int align(const ComparePaths* given, const int32_t* triples, int n_pairs, int dmax, void* stream) {
-        if (!given || n_pairs < 0 || (n_pairs > 0 && !triples) || dmax < 0 || dmax > kCompareDmaxCap) return ST_ERR_BAD_INPUT;
-        for (int64_t i = 0; i < (int64_t)n_pairs; i++) {
-            for (int q = 0; q < 2; q++) if (triples[3 * i + q] < 0 && ~triples[3 * i + q] >= given->n()) return ST_ERR_BAD_INPUT;
-            if (triples[3 * i + 2] < 0 || triples[3 * i + 2] > 1) return ST_ERR_BAD_INPUT;
-        }
-        if (align_run_area_bytes(n_pairs, dmax) > kAlignRunAreaCap) return kAlignTooLarge;
-        if (aln_given_.version != given->version) aln_given_ = *given;
-        aln_dmax_ = dmax;
-        aln_triples_.assign(triples, triples + 3 * (size_t)n_pairs);
-        return profile(kAlign, 1, stream);
-    }
+    // ---- the requests that bring their entries: path comparison (ambi_path_compare.hpp, kCompare) and alignment (ambi_path_align.hpp, kAlign) ----
+    // A PairRequest is the WHOLE request -- the entries (compare: pairs of sides, 2 * unit + which or ~t for the t-th given path;
+    // align: triples (A, B, orient)), the cap and a copy of the given paths as they were when it was made -- queued as the other
+    // kinds are queued (profile(kind)).  A request that profile_wait() has to queue again finds all of it here: the caller may replace
+    // its set of given paths between a request and its wait, and the request still works on what it named.  The copy is taken only
+    // when the caller's set has another version, and each kind has a copy of its own: the two never share one, so neither a new set
+    // nor the other kind's request reaches a queued one.  A given side beyond the copied set is refused here as well, whatever the
+    // caller checked.
+    struct PairRequest {
+        ComparePaths given;              // (version 0: the empty set, as the caller's before its first set)
+        std::vector<int32_t> entries;
+        int width;                       // int32 per entry: 2 (compare) or 3 (align)
+        int dmax = kCompareDmaxDefault;
+        int n() const { return (int)(entries.size() / (size_t)width); }
+    };
+    int compare(const ComparePaths* given, const int32_t* pairs, int n_pairs, int dmax, void* stream) { return pair_request(kCompare, given, pairs, n_pairs, dmax, stream); }
+    int align(const ComparePaths* given, const int32_t* triples, int n_pairs, int dmax, void* stream) { return pair_request(kAlign, given, triples, n_pairs, dmax, stream); }
     static constexpr int kAlignTooLarge = kSeqTooLarge;   // AMBI_ERR_TOO_LARGE, as the sequence request's refusal
-    int align_pairs() const { return (int)(aln_triples_.size() / 3); }
-    int align_result(int pair, PathAlign* out) const {
-        const ProfileState& P = prof_[kAlign];
-        if (!P.view || pair < 0 || pair >= align_pairs() || !out) return ST_ERR_BAD_INPUT;
-        *out = reinterpret_cast<const PathAlign*>(P.view)[pair];
-        return 0;
-    }
+    int compare_pairs() const { return pair_of(kCompare).n(); }
+    int align_pairs() const { return pair_of(kAlign).n(); }
+    int compare_result(int pair, PathCompare* out) const { return pair_result(kCompare, pair, out); }
+    int align_result(int pair, PathAlign* out) const { return pair_result(kAlign, pair, out); }
     const AlignRun* align_runs(int pair) const {   // the pair's align_stride(dmax) slots, nullptr without a waited-for request
         const ProfileState& P = prof_[kAlign];
         if (!P.view || pair < 0 || pair >= align_pairs()) return nullptr;
-        return reinterpret_cast<const AlignRun*>(P.view + align_runs_off(align_pairs())) + (int64_t)pair * align_stride(aln_dmax_);
+        return reinterpret_cast<const AlignRun*>(P.view + align_runs_off(align_pairs())) + (int64_t)pair * align_stride(pair_of(kAlign).dmax);
     }
 
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
@@ -381,12 +323,16 @@ class Backend {
     ProfileState prof_[kProfileKinds];   // [ProfileKind]
     void profile_layout(ProfileKind kind) {   // off and bytes of the bound batch's block
         ProfileState& P = prof_[kind];
-        if (kind == kAlign) { P.bytes = align_block_bytes(align_pairs(), aln_dmax_); P.off.clear(); }
-        else if (kind == kCompare) { P.bytes = compare_block_bytes(compare_pairs()); P.off.clear(); }
-        else if (kind == kFold) { P.bytes = fold_block_layout(prof_hb_->units, P.off); plane_bytes_ = fold_plane_layout(prof_hb_->units, plane_off_); }
-        else if (kind == kEvidence) { P.bytes = evidence_block_layout(prof_hb_->units, P.off); depth_bytes_ = evidence_depth_layout(prof_hb_->units, depth_off_); }
-        else if (kind == kFragment) P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), prof_hb_->units.size(), P.off);   // (sealed: the C-ABI layer does it before a request)
-        else P.bytes = kind == kJunction ? junc_profile_block_layout(prof_hb_->units, P.off) : profile_block_layout(prof_hb_->units, P.off);
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        switch (kind) {
+            case kCopyNumber: P.bytes = profile_block_layout(units, P.off); break;
+            case kJunction: P.bytes = junc_profile_block_layout(units, P.off); break;
+            case kFragment: P.bytes = frag_profile_block_layout(prof_hb_->frag.n_frag.data(), units.size(), P.off); break;   // (sealed: the C-ABI layer does it before a request)
+            case kEvidence: P.bytes = evidence_block_layout(units, P.off); depth_bytes_ = evidence_depth_layout(units, depth_off_); break;
+            case kFold: P.bytes = fold_block_layout(units, P.off); plane_bytes_ = fold_plane_layout(units, plane_off_); break;
+            case kCompare: P.bytes = compare_block_bytes(compare_pairs()); P.off.clear(); break;
+            case kAlign: P.bytes = align_block_bytes(align_pairs(), pair_of(kAlign).dmax); P.off.clear(); break;
+        }
     }
     // The windows of the bound batch; the environment variables (tests) can only shrink them (capped_window).
     static int env_int(const char* name) { const char* e = ambi_env(name); return e ? atoi(e) : 0; }   // 0 when unset
@@ -439,17 +385,40 @@ class Backend {
     int seq_state_ = 0;                  // 0: no request; 1: lengths known; 2: sequence_wait() has returned, the getters answer
     bool seq_queued_ = false;            // the stages of the last request have been queued (false behind kSeqTooLarge)
     const HostBatch* prof_hb_ = nullptr;
-    // the compare kind's request (compare()); workgroups of a request: AMBI_COMPARE_GRID (tests) can only shrink it
-    ComparePaths cmp_given_;             // (version 0: the empty set, as the caller's before its first set)
-    std::vector<int32_t> cmp_pairs_;
-    int cmp_dmax_ = kCompareDmaxDefault;
+    // the last compare() and align(), [kind - kCompare]; the workgroups of a request (for the align kind each with a history area):
+    // AMBI_COMPARE_GRID and AMBI_ALIGN_GRID (tests) can only shrink them
+    PairRequest pair_[2] = {{{}, {}, 2}, {{}, {}, 3}};
+    const PairRequest& pair_of(ProfileKind kind) const { return pair_[kind - kCompare]; }
     int compare_grid() const { return capped_window(compare_pairs(), kCompareGridCap, env_int("AMBI_COMPARE_GRID")); }
-    // the align kind's request (align()); its workgroups, each with a history area: AMBI_ALIGN_GRID (tests) can only shrink them
-    ComparePaths aln_given_;
-    std::vector<int32_t> aln_triples_;
-    int aln_dmax_ = kCompareDmaxDefault;
-    int align_grid_of() const { return align_grid(align_pairs(), aln_dmax_, env_int("AMBI_ALIGN_GRID")); }
+    int align_grid_of() const { return align_grid(align_pairs(), pair_of(kAlign).dmax, env_int("AMBI_ALIGN_GRID")); }
   private:
+    int pair_request(ProfileKind kind, const ComparePaths* given, const int32_t* entries, int n, int dmax, void* stream) {
+        PairRequest& Q = pair_[kind - kCompare];
+        if (!given || n < 0 || (n > 0 && !entries) || dmax < 0 || dmax > kCompareDmaxCap) return ST_ERR_BAD_INPUT;
+        for (int64_t i = 0; i < (int64_t)n; i++)
+            for (int q = 0; q < 2; q++) if (entries[Q.width * i + q] < 0 && ~entries[Q.width * i + q] >= given->n()) return ST_ERR_BAD_INPUT;
+        if (kind == kAlign) {   // (its own two, behind the shared ones: the orientation, and a run area above kAlignRunAreaCap, refused in front of any allocation)
+            for (int64_t i = 0; i < (int64_t)n; i++) if (entries[3 * i + 2] < 0 || entries[3 * i + 2] > 1) return ST_ERR_BAD_INPUT;
+            if (align_run_area_bytes(n, dmax) > kAlignRunAreaCap) return kAlignTooLarge;
+        }
+        if (Q.given.version != given->version) Q.given = *given;
+        Q.dmax = dmax;
+        Q.entries.assign(entries, entries + (size_t)Q.width * (size_t)n);
+        return profile(kind, 1, stream);
+    }
+    template <class T> int pair_result(ProfileKind kind, int pair, T* out) const {
+        const ProfileState& P = prof_[kind];
+        if (!P.view || pair < 0 || pair >= pair_of(kind).n() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const T*>(P.view)[pair];
+        return 0;
+    }
+    // a request's given set as the stages read it (ComparePaths::image), in host memory
+    static CompareGiven host_given(const PairRequest& Q, std::vector<Seq16A>& image) {
+        image.resize((size_t)(Q.given.image_bytes() / 16) + 1);
+        uint8_t* img = reinterpret_cast<uint8_t*>(image.data());
+        Q.given.image(img);
+        return compare_given(img, Q.given);
+    }
     void host_profile(const uint8_t* blob, int which, ProfileState& P) {
         const std::vector<UnitIn>& units = prof_hb_->units;
         const int window = profile_window_of();
@@ -510,25 +479,23 @@ class Backend {
             fold_scan_unit(g, units.data(), prof_hb_->junc_ends.data(), blob, (int)u, which, jwin, T, area, plane_bytes_, plane_off_.data(), P.blob.data(), P.off.data());
     }
     void host_compare(const uint8_t* blob, ProfileState& P) {
-        std::vector<Seq16A> image((size_t)(cmp_given_.image_bytes() / 16) + 1);
-        uint8_t* img = reinterpret_cast<uint8_t*>(image.data());
-        cmp_given_.image(img);
-        const CompareGiven given = compare_given(img, cmp_given_);
-        std::vector<int32_t> V((size_t)(compare_lds_bytes(cmp_dmax_) / 4));
+        const PairRequest& Q = pair_of(kCompare);
+        std::vector<Seq16A> image;
+        const CompareGiven given = host_given(Q, image);
+        std::vector<int32_t> V((size_t)(compare_lds_bytes(Q.dmax) / 4));
         HostGroup g;
-        for (int i = 0; i < compare_pairs(); i++)
-            compare_pair(g, prof_hb_->units.data(), blob, given, cmp_pairs_.data(), i, cmp_dmax_, V.data(), reinterpret_cast<PathCompare*>(P.blob.data()));
+        for (int i = 0; i < Q.n(); i++)
+            compare_pair(g, prof_hb_->units.data(), blob, given, Q.entries.data(), i, Q.dmax, V.data(), reinterpret_cast<PathCompare*>(P.blob.data()));
     }
     void host_align(const uint8_t* blob, ProfileState& P) {
-        std::vector<Seq16A> image((size_t)(aln_given_.image_bytes() / 16) + 1);
-        uint8_t* img = reinterpret_cast<uint8_t*>(image.data());
-        aln_given_.image(img);
-        const CompareGiven given = compare_given(img, aln_given_);
-        std::vector<int32_t> lds((size_t)(align_lds_bytes(aln_dmax_) / 4)), hist((size_t)align_history_ints(aln_dmax_));
+        const PairRequest& Q = pair_of(kAlign);
+        std::vector<Seq16A> image;
+        const CompareGiven given = host_given(Q, image);
+        std::vector<int32_t> lds((size_t)(align_lds_bytes(Q.dmax) / 4)), hist((size_t)align_history_ints(Q.dmax));
         HostGroup g;
-        for (int i = 0; i < align_pairs(); i++)
-            align_pair(g, prof_hb_->units.data(), blob, given, aln_triples_.data(), i, aln_dmax_, lds.data(), lds.data() + compare_lds_bytes(aln_dmax_) / 4, hist.data(),
-                       reinterpret_cast<PathAlign*>(P.blob.data()), reinterpret_cast<AlignRun*>(P.blob.data() + align_runs_off(align_pairs())));
+        for (int i = 0; i < Q.n(); i++)
+            align_pair(g, prof_hb_->units.data(), blob, given, Q.entries.data(), i, Q.dmax, lds.data(), lds.data() + compare_lds_bytes(Q.dmax) / 4, hist.data(),
+                       reinterpret_cast<PathAlign*>(P.blob.data()), reinterpret_cast<AlignRun*>(P.blob.data() + align_runs_off(Q.n())));
     }
     std::vector<Seq16A> depth_;          // the default implementation's depth area (16-byte aligned)
     std::vector<Seq16A> planes_;         // the default implementation's fold and cover planes (16-byte aligned)

@@ -819,16 +819,60 @@ struct PinnedWords {                    // what kernels write into host memory (
     uint32_t guard_hi[16];
 };
 struct TimingEvents { const char* name; hipEvent_t a, b; };
-// The lease's part of one on-request profile (HipBackend::profile_queue): the block [summary[U]][per unit counts] with the units'
-// offsets behind it, its pinned twin, and three events (the run's stream reached / kernel done / block arrived)
+// grow-only block of the lease (device memory, or pinned host memory with its device address)
+static int lease_device_block(uint8_t** p, int64_t* have, int64_t want) {
+    if (*have >= want && *p) return 0;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
+    want = (want + 4095) & ~int64_t(4095);
+    HIP_CK(hipMalloc((void**)p, (size_t)want));
+    *have = want;
+    return 0;
+}
+static int lease_pinned_block(uint8_t** p, uint8_t** dp, int64_t* have, int64_t want) {
+    if (*have >= want && *p) return 0;
+    if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
+    want = (want + 4095) & ~int64_t(4095);
+    HIP_CK(hipHostMalloc((void**)p, (size_t)want));
+    if (dp) HIP_CK(hipHostGetDevicePointer((void**)dp, *p, 0));
+    *have = want;
+    return 0;
+}
+static void trim_device_block(uint8_t*& p, int64_t& have, int64_t keep) { if (have > keep) { (void)hipFree(p); p = nullptr; have = 0; } }   // what is larger than `keep` goes back when the batch is destroyed
+static void trim_pinned_block(uint8_t*& p, int64_t& have, int64_t keep) { if (have > keep) { (void)hipHostFree(p); p = nullptr; have = 0; } }
+// The lease's part of one on-request result (HipBackend::profile_queue; the kinds' table: Backend::ProfileKind): the block with its
+// tail behind it, its pinned twin, the kind's side area, which stays on the device, and three events (the run's stream reached /
+// kernel done / block arrived)
 struct RequestBlock {
     uint8_t* d = nullptr; int64_t d_bytes = 0;
     uint8_t* h = nullptr; int64_t h_bytes = 0;
+    uint8_t* side = nullptr; int64_t side_bytes = 0;
     hipEvent_t ev_src = nullptr, ev_packed = nullptr, ev_done = nullptr;
-    void trim(int64_t keep) {   // a block larger than `keep` goes back to the device when the batch is destroyed
-        if (d_bytes > keep) { (void)hipFree(d); d = nullptr; d_bytes = 0; }
-        if (h_bytes > keep) { (void)hipHostFree(h); h = nullptr; h_bytes = 0; }
+    void trim(int64_t keep, int64_t keep_side) { trim_device_block(d, d_bytes, keep); trim_pinned_block(h, h_bytes, keep); trim_device_block(side, side_bytes, keep_side); }
+};
+// An input of the on-request kernels that does not travel with the batch: a device block of its own, the pinned twin that carries it
+// up, the event behind the last upload and the version the device holds (-1: nothing).  Which kernels still read the old image is
+// the caller's to know: it waits for them before it asks for another version.
+struct DeviceImage {
+    uint8_t* d = nullptr; int64_t d_bytes = 0;
+    uint8_t* h = nullptr; int64_t h_bytes = 0;
+    hipEvent_t ev_up = nullptr;
+    int64_t version = -1;
+    bool holds(int64_t want) const { return version == want && d; }
+    // `s` is ordered behind the upload of version `want` when this returns, whichever stream carried it: the image goes up on `s`
+    // (fill(twin), one copy of `total` bytes) when the device holds another version
+    template <class Fill> int upload(hipStream_t s, int64_t want, int64_t total, Fill fill) {
+        if (holds(want)) { HIP_CK(hipStreamWaitEvent(s, ev_up, 0)); return 0; }   // (the upload may have gone up on another stream)
+        if (!ev_up) HIP_CK(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
+        else HIP_CK(hipEventSynchronize(ev_up));   // (an earlier upload still reads the twin)
+        if (int rc = lease_device_block(&d, &d_bytes, total)) return rc;
+        if (int rc = lease_pinned_block(&h, nullptr, &h_bytes, total)) return rc;
+        fill(h);
+        HIP_CK(hipMemcpyAsync(d, h, (size_t)total, hipMemcpyHostToDevice, s));
+        HIP_CK(hipEventRecord(ev_up, s));
+        version = want;
+        return 0;
     }
+    void trim(int64_t keep) { trim_device_block(d, d_bytes, keep); trim_pinned_block(h, h_bytes, keep); }
 };
 struct Lease {
     int device = 0;
@@ -846,33 +890,11 @@ struct Lease {
     uint8_t* h_runs[2] = {nullptr, nullptr}; int64_t h_runs_bytes[2] = {0, 0};
     hipStream_t run_stream = nullptr;   // own_stream(): for callers without a stream (ambi_batch_run_sharded's shares)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_runs_packed[2] = {nullptr, nullptr}, ev_runs_done[2] = {nullptr, nullptr};
-    // [Backend::ProfileKind] copy-number profile [UnitProfile[U]][per unit fwd, rev], junction usage profile [UnitJuncProfile[U]][per unit count],
-    // fragment support profile [UnitFragProfile[U]][per unit fwd, rev, first], evidence depth profile [UnitEvidenceProfile[U]][per unit
-    // count, covered, min_depth], fold-back arm profile [UnitFoldProfile[U]][per unit folds, max_arm]
-    RequestBlock prof[Backend::kProfileKinds];
-    // the evidence kind's depth area: int32 per cell of every unit's path capacity; it never travels to the host as a whole
-    uint8_t* d_depth = nullptr; int64_t d_depth_bytes = 0;
-    // the fold kind's planes: the fold plane of every unit, then the cover plane, int32 per cell of path capacity each; allocated at
-    // the first request of the kind
-    uint8_t* d_planes = nullptr; int64_t d_planes_bytes = 0;
-    // the compare kind's given paths (ComparePaths::image: [off][len][cells]), a device buffer of their own beside the batch image,
-    // the pinned twin that carries them up and the event behind the last upload (the host writes the twin again only behind it).
-    // The kind's block prof[kCompare] is [PathCompare[n_pairs]] with the request's pairs behind it
-    uint8_t* d_cmp_img = nullptr; int64_t d_cmp_img_bytes = 0;
-    uint8_t* h_cmp = nullptr; int64_t h_cmp_bytes = 0;
-    hipEvent_t ev_cmp_up = nullptr;
-    // the align kind's: its own image of the given paths (the request's copy of the set: a set replaced for one kind never reaches a
-    // queued request of the other), and the workgroups' history areas, allocated at the first request of the kind.  The kind's block
-    // prof[kAlign] is [PathAlign[n_pairs]] [AlignRun[n_pairs * dmax]] with the request's triples behind it
-    uint8_t* d_aln_img = nullptr; int64_t d_aln_img_bytes = 0;
-    uint8_t* h_aln = nullptr; int64_t h_aln_bytes = 0;
-    hipEvent_t ev_aln_up = nullptr;
-    uint8_t* d_aln_hist = nullptr; int64_t d_aln_hist_bytes = 0;
-    // the batch's fragment image (HipBackend::fragment_image) [cells][frag_off][cell_off][pref_off][n_frag], its pinned twin and the
-    // event behind its last upload (the host writes the twin again only behind it)
-    uint8_t* d_frag_img = nullptr; int64_t d_frag_img_bytes = 0;
-    uint8_t* h_frag = nullptr; int64_t h_frag_bytes = 0;
-    hipEvent_t ev_frag_up = nullptr;
+    RequestBlock prof[Backend::kProfileKinds];   // [Backend::ProfileKind]
+    // the batch's fragment image (HipBackend::fragment_image: [cells][frag_off][cell_off][pref_off][n_frag]) and the given paths of
+    // the compare and of the align kind (ComparePaths::image: [off][len][cells]; each kind its request's own copy of the set)
+    enum { kFragImage = 0, kGivenImage = 1 };   // (the given sets: kGivenImage + kind - kCompare)
+    DeviceImage img[3];
     // path sequences (HipBackend::sequence): the batch's sequence image [bases][seg_pos][store_off][pos_off], the working block of a
     // request [totals][ext_off, out_off, tile_off][ext_src][ext_out] and the output block; the pinned twin carries the image up, the
     // totals down and the three offset tables up.  Events: the run's stream reached / all queued work done / timing pairs
@@ -1045,25 +1067,6 @@ int backend_stream_probe(void* a, void* b, float* us) {
     return stream_probe_us(*C, (hipStream_t)a, (hipStream_t)b, us);
 }
 
-// grow-only block of the lease (device memory, or pinned host memory with its device address)
-static int lease_device_block(uint8_t** p, int64_t* have, int64_t want) {
-    if (*have >= want && *p) return 0;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    want = (want + 4095) & ~int64_t(4095);
-    HIP_CK(hipMalloc((void**)p, (size_t)want));
-    *have = want;
-    return 0;
-}
-static int lease_pinned_block(uint8_t** p, uint8_t** dp, int64_t* have, int64_t want) {
-    if (*have >= want && *p) return 0;
-    if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
-    want = (want + 4095) & ~int64_t(4095);
-    HIP_CK(hipHostMalloc((void**)p, (size_t)want));
-    if (dp) HIP_CK(hipHostGetDevicePointer((void**)dp, *p, 0));
-    *have = want;
-    return 0;
-}
-
 // scoped device allocation / event pair for the helpers that allocate per call (freed on every return path)
 struct DevBuf {
     void* p = nullptr;
@@ -1233,16 +1236,8 @@ class HipBackend : public Backend {
                 if (L->d_runs_bytes[k] > kKeepRuns) { (void)hipFree(L->d_runs[k]); L->d_runs[k] = nullptr; L->d_runs_bytes[k] = 0; }
                 if (L->h_runs_bytes[k] > kKeepRuns) { (void)hipHostFree(L->h_runs[k]); L->h_runs[k] = nullptr; L->h_runs_bytes[k] = 0; }
             }
-            for (RequestBlock& B : L->prof) B.trim(kKeepProfile);
-            if (L->d_depth_bytes > kKeepCells) { (void)hipFree(L->d_depth); L->d_depth = nullptr; L->d_depth_bytes = 0; }
-            if (L->d_planes_bytes > kKeepCells) { (void)hipFree(L->d_planes); L->d_planes = nullptr; L->d_planes_bytes = 0; }
-            if (L->d_cmp_img_bytes > kKeepProfile) { (void)hipFree(L->d_cmp_img); L->d_cmp_img = nullptr; L->d_cmp_img_bytes = 0; }
-            if (L->h_cmp_bytes > kKeepProfile) { (void)hipHostFree(L->h_cmp); L->h_cmp = nullptr; L->h_cmp_bytes = 0; }
-            if (L->d_aln_img_bytes > kKeepProfile) { (void)hipFree(L->d_aln_img); L->d_aln_img = nullptr; L->d_aln_img_bytes = 0; }
-            if (L->h_aln_bytes > kKeepProfile) { (void)hipHostFree(L->h_aln); L->h_aln = nullptr; L->h_aln_bytes = 0; }
-            if (L->d_aln_hist_bytes > kKeepProfile) { (void)hipFree(L->d_aln_hist); L->d_aln_hist = nullptr; L->d_aln_hist_bytes = 0; }
-            if (L->d_frag_img_bytes > kKeepProfile) { (void)hipFree(L->d_frag_img); L->d_frag_img = nullptr; L->d_frag_img_bytes = 0; }
-            if (L->h_frag_bytes > kKeepProfile) { (void)hipHostFree(L->h_frag); L->h_frag = nullptr; L->h_frag_bytes = 0; }
+            for (int k = 0; k < kProfileKinds; k++) L->prof[k].trim(kKeepProfile, k == kAlign ? kKeepProfile : kKeepCells);   // (side areas: depth and planes as the path areas)
+            for (DeviceImage& I : L->img) { I.version = -1; I.trim(kKeepProfile); }
             for (auto pb : {std::make_pair(&L->d_seq_img, &L->d_seq_img_bytes), std::make_pair(&L->d_seq_work, &L->d_seq_work_bytes), std::make_pair(&L->d_seq_out, &L->d_seq_out_bytes)})
                 if (*pb.second > kKeepSeq) { (void)hipFree(*pb.first); *pb.first = nullptr; *pb.second = 0; }
             if (L->h_seq_bytes > kKeepSeq) { (void)hipHostFree(L->h_seq); L->h_seq = nullptr; L->h_seq_bytes = 0; }
@@ -1252,7 +1247,7 @@ class HipBackend : public Backend {
         stage_big_.clear(); stage_big_.shrink_to_fit();
         mail_valid_ = false;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; aln_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         device_ = -1;
     }
 
@@ -1318,7 +1313,7 @@ class HipBackend : public Backend {
         if (uploaded_) { free_all(); uploaded_ = false; }   // a second upload replaces the first (every stream idle first)
         ran_ = false; general_path_ = -1; timed_runs_ = 0; tuned_ = false; late_refusal_ = false; last_needed_ = 0;
         requests_reset();
-        sequence_reset(); seq_img_version_ = -1; frag_img_version_ = -1; cmp_img_version_ = -1; aln_img_version_ = -1; seq_busy_ = false;
+        sequence_reset(); seq_img_version_ = -1; seq_busy_ = false;
         express_ = false;
         shared_units_ = -1;
         hbp_ = &hb_in; cfg_ = cfg;
@@ -2286,138 +2281,140 @@ class HipBackend : public Backend {
         return 0;
     }
     // The fragment image of the batch (FragImage, ambi_pack.hpp) on the device: nothing of it travels with the batch; it goes up on
-    // the request's stream when the device does not hold this version of it (pinned twin, one copy), as the sequence image does.
-    int64_t frag_img_version_ = -1;
+    // the request's stream when the device does not hold this version of it (DeviceImage::upload).
     FragArgs frag_args_{};
     int fragment_image(hipStream_t s) {
-        Lease* L = lease_;
+        DeviceImage& D = lease_->img[Lease::kFragImage];
         const FragImage& I = hb().frag;
         const int64_t U = (int64_t)hb().units.size();
         if ((int64_t)I.pref_off.size() != U || (int64_t)I.cell_off.size() != U || (int64_t)I.n_frag.size() != U) return ST_ERR_BAD_INPUT;   // (not sealed)
         const int64_t b0 = pad16(2 * (int64_t)I.cells.size()), b1 = b0 + pad16(4 * (int64_t)I.frag_off.size()), b2 = b1 + 8 * U, b3 = b2 + 8 * U, total = b3 + pad16(4 * U);
-        if (frag_img_version_ != I.version || !L->d_frag_img) {
-            if (!L->ev_frag_up) HIP_CK(hipEventCreateWithFlags(&L->ev_frag_up, hipEventDisableTiming));
-            else HIP_CK(hipEventSynchronize(L->ev_frag_up));   // (an earlier upload still reads the twin)
-            if (int rc = lease_device_block(&L->d_frag_img, &L->d_frag_img_bytes, total)) return rc;
-            if (int rc = lease_pinned_block(&L->h_frag, nullptr, &L->h_frag_bytes, total)) return rc;
-            if (!I.cells.empty()) memcpy(L->h_frag, I.cells.data(), 2 * I.cells.size());
-            memcpy(L->h_frag + b0, I.frag_off.data(), 4 * I.frag_off.size());
-            memcpy(L->h_frag + b1, I.cell_off.data(), (size_t)(8 * U));
-            memcpy(L->h_frag + b2, I.pref_off.data(), (size_t)(8 * U));
-            memcpy(L->h_frag + b3, I.n_frag.data(), (size_t)(4 * U));
-            HIP_CK(hipMemcpyAsync(L->d_frag_img, L->h_frag, (size_t)total, hipMemcpyHostToDevice, s));
-            HIP_CK(hipEventRecord(L->ev_frag_up, s));
-            frag_img_version_ = I.version;
-        }
-        frag_args_ = FragArgs{reinterpret_cast<const rcell_t*>(L->d_frag_img), reinterpret_cast<const int32_t*>(L->d_frag_img + b0),
-                              reinterpret_cast<const int64_t*>(L->d_frag_img + b1), reinterpret_cast<const int64_t*>(L->d_frag_img + b2),
-                              reinterpret_cast<const int32_t*>(L->d_frag_img + b3)};
+        if (int rc = D.upload(s, I.version, total, [&](uint8_t* h) {
+                if (!I.cells.empty()) memcpy(h, I.cells.data(), 2 * I.cells.size());
+                memcpy(h + b0, I.frag_off.data(), 4 * I.frag_off.size());
+                memcpy(h + b1, I.cell_off.data(), (size_t)(8 * U));
+                memcpy(h + b2, I.pref_off.data(), (size_t)(8 * U));
+                memcpy(h + b3, I.n_frag.data(), (size_t)(4 * U));
+            })) return rc;
+        frag_args_ = FragArgs{reinterpret_cast<const rcell_t*>(D.d), reinterpret_cast<const int32_t*>(D.d + b0), reinterpret_cast<const int64_t*>(D.d + b1),
+                              reinterpret_cast<const int64_t*>(D.d + b2), reinterpret_cast<const int32_t*>(D.d + b3)};
         return 0;
     }
-    // The given paths of the compare kind (ComparePaths, ambi_path_compare.hpp) in a device buffer of their own: they go up on the
-    // request's stream when the device does not hold this version of them (pinned twin, one copy), as the fragment image does.  The
-    // batch image is not touched.  The align kind has the same of its own (its request's copy of the set, its buffer, twin and event).
-    int64_t cmp_img_version_ = -1, aln_img_version_ = -1;
-    CompareGiven cmp_args_{}, aln_args_{};
-    int compare_image(ProfileKind kind, hipStream_t s) {
-        Lease* L = lease_;
-        const bool aln = kind == kAlign;
-        const ComparePaths& I = aln ? aln_given_ : cmp_given_;
-        uint8_t*& d = aln ? L->d_aln_img : L->d_cmp_img; int64_t& d_bytes = aln ? L->d_aln_img_bytes : L->d_cmp_img_bytes;
-        uint8_t*& h = aln ? L->h_aln : L->h_cmp; int64_t& h_bytes = aln ? L->h_aln_bytes : L->h_cmp_bytes;
-        hipEvent_t& ev_up = aln ? L->ev_aln_up : L->ev_cmp_up;
-        int64_t& version = aln ? aln_img_version_ : cmp_img_version_;
-        const int64_t total = I.image_bytes();
-        if (version != I.version || !d) {
-            if (req_[kind].queued) HIP_CK(hipEventSynchronize(L->prof[kind].ev_done));   // (its kernel reads the buffer)
-            if (!ev_up) HIP_CK(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
-            else HIP_CK(hipEventSynchronize(ev_up));   // (an earlier upload still reads the twin)
-            if (int rc = lease_device_block(&d, &d_bytes, total)) return rc;
-            if (int rc = lease_pinned_block(&h, nullptr, &h_bytes, total)) return rc;
-            I.image(h);
-            HIP_CK(hipMemcpyAsync(d, h, (size_t)total, hipMemcpyHostToDevice, s));
-            HIP_CK(hipEventRecord(ev_up, s));
-            version = I.version;
-        } else HIP_CK(hipStreamWaitEvent(s, ev_up, 0));   // (the upload may have gone up on another stream)
-        (aln ? aln_args_ : cmp_args_) = compare_given(d, I);
+    // The given paths of a pair request (PairRequest::given: the request's copy of the set) in a device buffer of the kind's own, in
+    // the same way.  The batch image is not touched.
+    CompareGiven given_args_[2] = {};   // [kind - kCompare]
+    int given_image(ProfileKind kind, hipStream_t s) {
+        DeviceImage& D = lease_->img[Lease::kGivenImage + kind - kCompare];
+        const ComparePaths& I = pair_of(kind).given;
+        if (int rc = D.upload(s, I.version, I.image_bytes(), [&](uint8_t* h) { I.image(h); })) return rc;
+        given_args_[kind - kCompare] = compare_given(D.d, I);
         return 0;
     }
-    // The profiles are instances of one on-request block (Lease::prof, req_, Backend::prof_); a kind has its own layout, its own
-    // kernel with its LDS size, and nothing else -- but for the fragment kind's image, which goes up in front of its kernel.
-    // profile() queues the kind's kernel behind the run, then ONE device-to-host copy of the block on the lease's copy stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes
-    // the results final (wait(): the first run done again with a larger arena, units finished by the parallel search) and, if that
-    // moved the results' epoch after the kernel was queued, queues kernel and copy once more.
+    // The on-request results are instances of one block (Lease::prof, req_, Backend::prof_); a kind has its own inputs, its own layout,
+    // its own kernels with their LDS sizes, and nothing else: each of these is one switch below, and the table of the kinds is above
+    // Backend::ProfileKind.  profile() queues the kind's kernels behind the run, then ONE device-to-host copy of the block on the
+    // lease's copy stream, as runs_to_host does it: `stream` is free for the next run at once.  profile_wait() makes the results final
+    // (wait(): the first run done again with a larger arena, units finished by the parallel search) and, if that moved the results'
+    // epoch after the kernels were queued, queues kernels and copy once more.
     int profile_queue(ProfileKind kind, int which, hipStream_t s) {
         Lease* L = lease_;
         RequestBlock& B = L->prof[kind]; Request& R = req_[kind]; ProfileState& P = prof_[kind];
         const int64_t U = (int64_t)hb().units.size();
-        if (kind == kFragment || kind == kEvidence) {   // (the image can change between requests, and with it the fragment kind's layout)
-            if (frag_img_version_ != hb().frag.version) {
-                for (ProfileKind k : {kFragment, kEvidence}) if (req_[k].queued) HIP_CK(hipEventSynchronize(L->prof[k].ev_done));   // (their kernels read the image)
-                req_[kFragment].laid_out = false; R.laid_out = false;
-            }
-            if (int rc = fragment_image(s)) return rc;
+        // 1. inputs: the kind's image, behind the kernels that still read another version of it
+        switch (kind) {
+            case kCopyNumber: case kJunction: case kFold: break;
+            case kFragment: case kEvidence:   // (the image can change between requests, and with it the fragment kind's layout)
+                if (!L->img[Lease::kFragImage].holds(hb().frag.version)) {
+                    for (ProfileKind k : {kFragment, kEvidence}) if (req_[k].queued) HIP_CK(hipEventSynchronize(L->prof[k].ev_done));
+                    req_[kFragment].laid_out = false; R.laid_out = false;
+                }
+                if (int rc = fragment_image(s)) return rc;
+                break;
+            case kCompare: case kAlign:   // (entries and cap come with the request: laid out every time, once the last request's kernel, copy and upload have left image, block and twin)
+                if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done));
+                R.laid_out = false;
+                if (int rc = given_image(kind, s)) return rc;
+                break;
         }
-        const bool aln = kind == kAlign, cmp = kind == kCompare || aln;   // (cmp: the request brings its entries, two or three int32 each)
-        const int64_t n_pairs = aln ? align_pairs() : compare_pairs();
-        const int aln_grid = align_grid_of();
-        const int64_t hist_bytes = align_history_bytes(aln_dmax_);
-        if (cmp) {   // (pairs and cap come with the request: laid out every time, once the last request's copy and upload have left block and twin)
-            if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done));
-            R.laid_out = false;
-            if (int rc = compare_image(kind, s)) return rc;
-        }
-        if (aln) { if (int rc = lease_device_block(&L->d_aln_hist, &L->d_aln_hist_bytes, aln_grid * hist_bytes)) return rc; }   // (no kernel of the kind is in flight: waited for above)
+        // 2. layout: the block and its twin, the tail that travels up behind the block once per layout (the block's copies never touch
+        // it), and the side area
         if (!R.laid_out) {
             profile_layout(kind);
-            const int64_t n_off = aln ? (3 * n_pairs + 1) / 2 : cmp ? n_pairs : kind == kEvidence || kind == kFold ? 2 * U : U;   // (the evidence and fold kinds: the depth area's or the planes' offsets behind the block's; the compare kind: the pairs, two int32 each)
+            struct { const void* p; int64_t bytes; } tail[2] = {{P.off.data(), 8 * U}, {nullptr, 0}};
+            int64_t side_bytes = 0;
+            switch (kind) {
+                case kCopyNumber: case kJunction: case kFragment: break;
+                case kEvidence: tail[1] = {depth_off_.data(), 8 * U}; side_bytes = depth_bytes_ > 0 ? depth_bytes_ : 16; break;
+                case kFold: tail[1] = {plane_off_.data(), 8 * U}; side_bytes = plane_bytes_ > 0 ? 2 * plane_bytes_ : 16; break;
+                case kCompare: tail[0] = {pair_of(kind).entries.data(), 8 * (int64_t)compare_pairs()}; break;
+                case kAlign: tail[0] = {pair_of(kind).entries.data(), 12 * (int64_t)align_pairs()}; side_bytes = align_grid_of() * align_history_bytes(pair_of(kind).dmax); break;
+            }
+            const int64_t n_off = (tail[0].bytes + tail[1].bytes + 7) / 8;
             const int64_t total = P.bytes + n_off * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
-            if (kind == kEvidence) { if (int rc = lease_device_block(&L->d_depth, &L->d_depth_bytes, depth_bytes_ > 0 ? depth_bytes_ : 16)) return rc; }
-            if (kind == kFold) { if (int rc = lease_device_block(&L->d_planes, &L->d_planes_bytes, plane_bytes_ > 0 ? 2 * plane_bytes_ : 16)) return rc; }
+            if (side_bytes > 0) { if (int rc = lease_device_block(&B.side, &B.side_bytes, side_bytes)) return rc; }   // (no kernel of the kind is in flight that the layout would move it under)
             if (int rc = lease_device_block(&B.d, &B.d_bytes, total)) return rc;
             if (int rc = lease_pinned_block(&B.h, nullptr, &B.h_bytes, total)) return rc;
             if (!L->copy_stream) HIP_CK(hipStreamCreateWithFlags(&L->copy_stream, hipStreamNonBlocking));
             for (hipEvent_t* e : {&B.ev_src, &B.ev_packed, &B.ev_done}) if (!*e) HIP_CK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-            // the units' offsets travel once per batch, from the tail of the pinned twin (the block's copies never touch the tail)
-            if (aln) { if (n_pairs > 0) memcpy(B.h + P.bytes, aln_triples_.data(), (size_t)n_pairs * 3 * sizeof(int32_t)); }
-            else if (cmp) { if (n_pairs > 0) memcpy(B.h + P.bytes, cmp_pairs_.data(), (size_t)n_pairs * sizeof(int64_t)); }
-            else memcpy(B.h + P.bytes, P.off.data(), (size_t)U * sizeof(int64_t));
-            if (kind == kEvidence) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), depth_off_.data(), (size_t)U * sizeof(int64_t));
-            if (kind == kFold) memcpy(B.h + P.bytes + U * (int64_t)sizeof(int64_t), plane_off_.data(), (size_t)U * sizeof(int64_t));
+            if (tail[0].bytes > 0) memcpy(B.h + P.bytes, tail[0].p, (size_t)tail[0].bytes);
+            if (tail[1].bytes > 0) memcpy(B.h + P.bytes + tail[0].bytes, tail[1].p, (size_t)tail[1].bytes);
             R.d_off = reinterpret_cast<int64_t*>(B.d + P.bytes);
             if (n_off > 0) HIP_CK(hipMemcpyAsync(R.d_off, B.h + P.bytes, (size_t)n_off * sizeof(int64_t), hipMemcpyHostToDevice, s));
             R.laid_out = true;
         }
+        // 3. ordering: behind the results, and behind an earlier request nobody waited for (its copy still reads the block)
         if (int rc = behind_results(s, B.ev_src)) return rc;
-        int window = 0, jwin = 0, slots = 0, swin = 0, pwin = 0, lds = kProfileScratchBytes, fslots = 0, lds_mark = kProfileScratchBytes, fwin = 0;
-        if (aln) lds += (int)align_lds_bytes(aln_dmax_);
-        else if (cmp) lds += (int)compare_lds_bytes(cmp_dmax_);
-        else if (kind == kFold) { fold_windows(&fwin, &jwin, &slots); lds_mark += (int)fold_arm_lds_bytes(fwin); lds += (int)fold_scan_lds_bytes(slots); }
-        else if (kind == kEvidence) {
-            frag_profile_windows(&pwin, &fslots); lds_mark += (int)frag_profile_lds_bytes(fslots, pwin);
-            evidence_windows(&jwin, &slots); lds += (int)evidence_scan_lds_bytes(slots, kProfileThreads);
-        } else if (kind == kFragment) { frag_profile_windows(&pwin, &slots); lds += (int)frag_profile_lds_bytes(slots, pwin); }
-        else if (kind == kJunction) { junc_profile_windows(&jwin, &slots, &swin); lds += (int)junc_profile_lds_bytes(slots, swin); }
-        else { window = profile_window_of(); lds += (int)profile_bins_bytes(window); }
-        if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));   // (an earlier request nobody waited for: its copy still reads the block)
-        const int grid = (int)(U < 16384 ? U : 16384);   // (A_: units and result blob as the last run bound them)
-        if (aln) {   // (a workgroup and a history area per pair in flight; a request without pairs launches nothing)
-            if (n_pairs > 0) hipLaunchKernelGGL(ambi_path_align_kernel, dim3(aln_grid), dim3(kProfileThreads), lds, s, A_, aln_args_, (const int32_t*)R.d_off, (int)n_pairs, aln_dmax_, L->d_aln_hist,
-                                                hist_bytes, reinterpret_cast<PathAlign*>(B.d), reinterpret_cast<AlignRun*>(B.d + align_runs_off(n_pairs)));
-        } else if (cmp) {   // (a workgroup per pair; a request without pairs launches nothing)
-            if (n_pairs > 0) hipLaunchKernelGGL(ambi_path_compare_kernel, dim3(compare_grid()), dim3(kProfileThreads), lds, s, A_, cmp_args_, (const int32_t*)R.d_off, (int)n_pairs, cmp_dmax_, reinterpret_cast<PathCompare*>(B.d));
-        } else if (kind == kFold) {   // (the scan kernel behind the arm kernel on one stream, as below)
-            hipLaunchKernelGGL(ambi_fold_arm_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, which, fwin, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U));
-            HIP_CK(hipGetLastError());
-            hipLaunchKernelGGL(ambi_fold_scan_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, L->d_planes, plane_bytes_, (const int64_t*)(R.d_off + U), B.d, (const int64_t*)R.d_off);
-        } else if (kind == kEvidence) {   // (the scan kernel behind the mark kernel on one stream: the boundary orders atomics and loads)
-            hipLaunchKernelGGL(ambi_evidence_mark_kernel, dim3(grid), dim3(kProfileThreads), lds_mark, s, A_, frag_args_, which, pwin, fslots, L->d_depth, (const int64_t*)(R.d_off + U));
-            HIP_CK(hipGetLastError());
-            hipLaunchKernelGGL(ambi_evidence_scan_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, L->d_depth, (const int64_t*)(R.d_off + U), B.d, (const int64_t*)R.d_off);
-        } else if (kind == kFragment) hipLaunchKernelGGL(ambi_frag_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, frag_args_, which, pwin, slots, B.d, (const int64_t*)R.d_off);
-        else if (kind == kJunction) hipLaunchKernelGGL(ambi_junc_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, jwin, slots, swin, B.d, (const int64_t*)R.d_off);
-        else hipLaunchKernelGGL(ambi_path_profile_kernel, dim3(grid), dim3(kProfileThreads), lds, s, A_, which, window, B.d, (const int64_t*)R.d_off);
+        if (R.queued) HIP_CK(hipStreamWaitEvent(s, B.ev_done, 0));
+        // 4. launch: the kind's windows, LDS sizes and kernels (A_: units and result blob as the last run bound them)
+        const dim3 grid((unsigned)(U < 16384 ? U : 16384)), threads(kProfileThreads);
+        const int64_t* off = R.d_off; const int64_t* side_off = R.d_off + U;
+        const int scratch = kProfileScratchBytes;
+        switch (kind) {
+            case kCopyNumber: {
+                const int window = profile_window_of();
+                hipLaunchKernelGGL(ambi_path_profile_kernel, grid, threads, scratch + (int)profile_bins_bytes(window), s, A_, which, window, B.d, off);
+                break;
+            }
+            case kJunction: {
+                int jwin, slots, swin; junc_profile_windows(&jwin, &slots, &swin);
+                hipLaunchKernelGGL(ambi_junc_profile_kernel, grid, threads, scratch + (int)junc_profile_lds_bytes(slots, swin), s, A_, which, jwin, slots, swin, B.d, off);
+                break;
+            }
+            case kFragment: {
+                int pwin, slots; frag_profile_windows(&pwin, &slots);
+                hipLaunchKernelGGL(ambi_frag_profile_kernel, grid, threads, scratch + (int)frag_profile_lds_bytes(slots, pwin), s, A_, frag_args_, which, pwin, slots, B.d, off);
+                break;
+            }
+            case kEvidence: {   // (the scan kernel behind the mark kernel on one stream: the boundary orders atomics and loads)
+                int pwin, fslots, jwin, slots; frag_profile_windows(&pwin, &fslots); evidence_windows(&jwin, &slots);
+                hipLaunchKernelGGL(ambi_evidence_mark_kernel, grid, threads, scratch + (int)frag_profile_lds_bytes(fslots, pwin), s, A_, frag_args_, which, pwin, fslots, B.side, side_off);
+                HIP_CK(hipGetLastError());
+                hipLaunchKernelGGL(ambi_evidence_scan_kernel, grid, threads, scratch + (int)evidence_scan_lds_bytes(slots, kProfileThreads), s, A_, which, jwin, slots, B.side, side_off, B.d, off);
+                break;
+            }
+            case kFold: {   // (the scan kernel behind the arm kernel on one stream, as above)
+                int fwin, jwin, slots; fold_windows(&fwin, &jwin, &slots);
+                hipLaunchKernelGGL(ambi_fold_arm_kernel, grid, threads, scratch + (int)fold_arm_lds_bytes(fwin), s, A_, which, fwin, B.side, plane_bytes_, side_off);
+                HIP_CK(hipGetLastError());
+                hipLaunchKernelGGL(ambi_fold_scan_kernel, grid, threads, scratch + (int)fold_scan_lds_bytes(slots), s, A_, which, jwin, slots, B.side, plane_bytes_, side_off, B.d, off);
+                break;
+            }
+            case kCompare: {   // (a workgroup per pair; a request without pairs launches nothing)
+                const PairRequest& Q = pair_of(kind);
+                if (Q.n() > 0) hipLaunchKernelGGL(ambi_path_compare_kernel, dim3(compare_grid()), threads, scratch + (int)compare_lds_bytes(Q.dmax), s, A_, given_args_[kind - kCompare],
+                                                  reinterpret_cast<const int32_t*>(off), Q.n(), Q.dmax, reinterpret_cast<PathCompare*>(B.d));
+                break;
+            }
+            case kAlign: {   // (a workgroup and a history area per pair in flight; a request without pairs launches nothing)
+                const PairRequest& Q = pair_of(kind);
+                if (Q.n() > 0) hipLaunchKernelGGL(ambi_path_align_kernel, dim3(align_grid_of()), threads, scratch + (int)align_lds_bytes(Q.dmax), s, A_, given_args_[kind - kCompare],
+                                                  reinterpret_cast<const int32_t*>(off), Q.n(), Q.dmax, B.side, align_history_bytes(Q.dmax), reinterpret_cast<PathAlign*>(B.d),
+                                                  reinterpret_cast<AlignRun*>(B.d + align_runs_off(Q.n())));
+                break;
+            }
+        }
         HIP_CK(hipGetLastError());
+        // 5. copy: the block to its twin on the lease's copy stream
         HIP_CK(hipEventRecord(B.ev_packed, s));
         HIP_CK(hipStreamWaitEvent(L->copy_stream, B.ev_packed, 0));
         HIP_CK(hipMemcpyAsync(B.h, B.d, (size_t)P.bytes, hipMemcpyDeviceToHost, L->copy_stream));
@@ -2452,25 +2449,25 @@ class HipBackend : public Backend {
     // returned), and the area itself
     int evidence_depth_copy(int unit, int64_t first, int64_t n, int32_t* out) override {
         DeviceGuard dg_(device_);
-        if (!prof_[kEvidence].view || !lease_ || !lease_->d_depth || unit < 0 || unit >= (int)depth_off_.size() || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
-        if (n > 0) HIP_CK(hipMemcpy(out, lease_->d_depth + depth_off_[(size_t)unit] + 4 * first, (size_t)(4 * n), hipMemcpyDeviceToHost));
+        if (!prof_[kEvidence].view || !lease_ || !lease_->prof[kEvidence].side || unit < 0 || unit >= (int)depth_off_.size() || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) HIP_CK(hipMemcpy(out, lease_->prof[kEvidence].side + depth_off_[(size_t)unit] + 4 * first, (size_t)(4 * n), hipMemcpyDeviceToHost));
         return 0;
     }
     int evidence_depth_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) override {
         if (!prof_[kEvidence].view || !lease_) return ST_ERR_BAD_INPUT;
-        if (ptr) *ptr = lease_->d_depth;
+        if (ptr) *ptr = lease_->prof[kEvidence].side;
         return evidence_depth_offsets(bytes, unit_off, cap);
     }
     // the fold kind's planes: a range of one unit's plane to the host, and the area itself
     int fold_plane_copy(int unit, int plane, int64_t first, int64_t n, int32_t* out) override {
         DeviceGuard dg_(device_);
-        if (!prof_[kFold].view || !lease_ || !lease_->d_planes || unit < 0 || unit >= (int)plane_off_.size() || plane < 0 || plane > 1 || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
-        if (n > 0) HIP_CK(hipMemcpy(out, lease_->d_planes + plane * plane_bytes_ + plane_off_[(size_t)unit] + 4 * first, (size_t)(4 * n), hipMemcpyDeviceToHost));
+        if (!prof_[kFold].view || !lease_ || !lease_->prof[kFold].side || unit < 0 || unit >= (int)plane_off_.size() || plane < 0 || plane > 1 || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) HIP_CK(hipMemcpy(out, lease_->prof[kFold].side + plane * plane_bytes_ + plane_off_[(size_t)unit] + 4 * first, (size_t)(4 * n), hipMemcpyDeviceToHost));
         return 0;
     }
     int fold_planes_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) override {
         if (!prof_[kFold].view || !lease_) return ST_ERR_BAD_INPUT;
-        if (ptr) *ptr = lease_->d_planes;
+        if (ptr) *ptr = lease_->prof[kFold].side;
         return fold_plane_offsets(bytes, unit_off, cap);
     }
     // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----

@@ -468,6 +468,70 @@ def check_request_paths(lib, oracle, workdir, run_stream=None, req_stream=None):
     pc.close_all(graphs, b)
 
 
+# ---- case 9b: the fragment and the evidence request on two streams ------------------------------------------------------------
+QUIRKS2_UNITS = [(1, 4), (5, 8), (9, 10)]                 # SOURCE / SINK of tests/data/quirks2.lh
+
+
+def file_fragments(lib, lh, juncs, start, end):
+    """The lines of a .juncs file that lie inside [start, end], as chains of LOCAL signed ids."""
+    g = api.Graph(lib, lh); g.read_fragments(juncs)
+    lines, _ = g.fragments()
+    g.close()
+    return [jc.local_path(f, start - 1) for f in lines if len(f) >= 2 and all(start <= abs(v) <= end for v in f)]
+
+
+def check_two_request_streams(lib, oracle, run_stream=None, frag_stream=None, ev_stream=None):
+    """Both readers of the fragment image, each on a stream of its own and with nothing between them: the image goes up with the first
+    of the two requests, on ITS stream; then a moved version with the requests the other way round.  This checks the request logic --
+    who uploads, the layouts redone behind a new version, both kinds' results -- not the ordering behind the upload itself: an image
+    this small arrives before the other stream's kernel starts whether or not that stream waits for it.  The batch is the fixtures
+    that have a .juncs file: the README example (the oracle's path, the independent reference here) and the three chromosomes of quirks2
+    without a .sol (two refused units and a two-cell shortcut: the engine's own status and path, as for hand-built units -- they add
+    empty results and F = 0 to the batch, no second reference).  The fragments are attached after the run."""
+    readme, rsol, rjuncs = (os.path.join(cases.DATA, "readme6." + x) for x in ("lh", "sol", "juncs"))
+    q2, q2juncs = os.path.join(cases.DATA, "quirks2.lh"), os.path.join(cases.DATA, "quirks2.juncs")
+    oc = oracle.run_bfb(readme, [rsol])["chr"][0]
+    g1, g2 = api.Graph(lib, readme), api.Graph(lib, q2)
+    b = api.Batch(lib)
+    b.add_chromosome_sol(g1, 0, rsol)
+    for c in range(len(QUIRKS2_UNITS)):
+        b.add_chromosome(g2, c, [], [])
+    ranges = [(oc["start"], oc["end"])] + QUIRKS2_UNITS
+    frags = [file_fragments(lib, readme, rjuncs, *ranges[0])] + [file_fragments(lib, q2, q2juncs, s, e) for s, e in QUIRKS2_UNITS]
+    assert frags[0] == fc.README_JUNCS and [len(f) for f in frags[1:]] == [2, 2, 0], frags
+    juncs = [unit_ends(readme, g1, oc)] + [jc.unit_junctions(q2, g2, s, e)[:2] for s, e in QUIRKS2_UNITS]
+    b.upload(); b.run(0, run_stream)
+
+    def requests(order, tag):
+        for which in (0, 1):
+            for kind in order:
+                if kind == "fragment":
+                    b.frag_profile(which, frag_stream)
+                else:
+                    b.evidence_profile(which, ev_stream)
+            b.frag_profile_wait(); b.evidence_profile_wait()
+            b.download()
+            for u, (idx, ends) in enumerate(juncs):
+                status = b.unit_result(u)["status"]
+                path = jc.oracle_path(oc, which) if u == 0 else b.unit_path(u, which).tolist()
+                if u > 0 and path:
+                    path = jc.local_path(path, ranges[u][0] - 1)
+                assert status == (0 if u == 0 else (-11, -11, api.ST_SHORTCUT)[u - 1]), (tag, u, status)
+                fc.compare_unit(b, u, frags[u], path, status, (tag, "fragment", which, u))
+                compare_unit(b, u, frags[u], ends, path, status, (tag, "evidence", which, u), idx)
+
+    for u, f in enumerate(frags):
+        b.set_unit_fragments(u, f)
+    requests(("fragment", "evidence"), "image with the fragment request")
+    assert b.unit_evidence_depth(0).tolist() == README_DEPTH and b.unit_evidence_depth(3).tolist() == [0]
+    # another set for one unit while both kinds have been queued: the version moves, and the evidence request carries the image up
+    frags[0] = fc.README_JUNCS + [[1, 2, 3], [-6, -5], [6, -6]]
+    b.set_unit_fragments(0, frags[0])
+    requests(("evidence", "fragment"), "image with the evidence request")
+    assert b.unit_evidence_depth(0).tolist() != README_DEPTH
+    b.close(); g1.close(); g2.close()
+
+
 # ---- case 10: sharded ---------------------------------------------------------------------------------------------------
 def check_sharded(lib, oracle, workdir, devices):
     graphs, b, items = many_items(lib, oracle, workdir, 12)

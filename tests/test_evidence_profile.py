@@ -59,6 +59,11 @@ def test_request_paths(hostsim_lib, oracle, workdir):
     ec.check_request_paths(hostsim_lib, oracle, workdir)
 
 
+def test_two_request_streams(hostsim_lib, oracle):
+    """The request logic of the fragment and the evidence request side by side (the host simulation has no streams)."""
+    ec.check_two_request_streams(hostsim_lib, oracle)
+
+
 def test_sharded_evidence_profile(hostsim_lib, oracle, workdir):
     """After run_sharded the request goes to every share and the getters answer from the share that holds the unit."""
     ec.check_sharded(hostsim_lib, oracle, workdir, [0, 0, 0])
@@ -138,6 +143,16 @@ def test_gpu_request_paths(hip_lib, oracle, workdir):
     import torch
     run_s, req_s = torch.cuda.Stream(), torch.cuda.Stream()
     ec.check_request_paths(hip_lib, oracle, workdir, run_s.cuda_stream, req_s.cuda_stream)
+
+
+@pytest.mark.gpu
+def test_gpu_two_request_streams(hip_lib, oracle):
+    """The run, the fragment request and the evidence request on three streams, the image going up with either request: the request
+    logic and the new layout behind a moved version.  The image is a few hundred bytes and arrives long before the other stream's
+    kernel starts, so a missing wait for its upload would not show here; that ordering is read in DeviceImage::upload."""
+    import torch
+    run_s, frag_s, ev_s = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
+    ec.check_two_request_streams(hip_lib, oracle, run_s.cuda_stream, frag_s.cuda_stream, ev_s.cuda_stream)
 
 
 @pytest.mark.gpu
