@@ -123,6 +123,49 @@ def align_from_compare(pairs, results):
     return np.array(out, np.int32).reshape(-1, 3)
 
 
+class UnitCoords(C.Structure):      # ambi_unit_coords_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "cells", "runs", "empty_cells")] + [(k, C.c_int64) for k in ("bp_len", "bp_minus")]
+
+
+class LiftQuery(C.Structure):       # ambi_lift_query_t
+    _fields_ = [("unit", C.c_int32), ("reserved", C.c_int32), ("pos", C.c_int64)]
+
+
+class Lift(C.Structure):            # ambi_lift_t
+    _fields_ = [(k, C.c_int32) for k in ("status", "cell", "seg", "reserved")] + [(k, C.c_int64) for k in ("seg_off", "cell_start")]
+
+
+# the same as structured numpy dtypes (Batch.path_coords, path_coords_summaries, path_coords_results), 32, 16 and 32 bytes
+UNIT_COORDS_DTYPE = np.dtype([(k, np.int32) for k in ("status", "cells", "runs", "empty_cells")] + [(k, np.int64) for k in ("bp_len", "bp_minus")])
+LIFT_QUERY_DTYPE = np.dtype([("unit", np.int32), ("reserved", np.int32), ("pos", np.int64)])
+LIFT_DTYPE = np.dtype([(k, np.int32) for k in ("status", "cell", "seg", "reserved")] + [(k, np.int64) for k in ("seg_off", "cell_start")])
+
+
+def lift_queries(units, pos):
+    """A LIFT_QUERY_DTYPE array for Batch.path_coords from unit indices and amplicon positions (scalars broadcast)."""
+    u, p = np.broadcast_arrays(np.asarray(units, np.int64), np.asarray(pos, np.int64))
+    q = np.zeros(u.size, LIFT_QUERY_DTYPE)
+    q["unit"], q["pos"] = u.ravel(), p.ravel()
+    return q
+
+
+def lift_to_genome(graph, chr, results):
+    """Joins lift results (Batch.path_coords_results) of the unit built from chromosome `chr` of `graph` with the graph on the host:
+    a list of (chrom, genome_pos, strand, seg_id), one per result, None where the result names no cell.  seg_id is the segment's id
+    in the file, genome_pos = its start + seg_off (0-based, the convention of the sequences), strand '+' or '-'."""
+    seg = graph.segments()
+    first, _ = graph.chromosome(chr)
+    out = []
+    for r in results:
+        if int(r["cell"]) < 0:
+            out.append(None)
+            continue
+        c = int(r["seg"])
+        sid = first - 1 + abs(c)            # local id -> id in the file (ids are 1..N in file order)
+        out.append((graph.chrom_name(sid), int(seg["start"][sid - 1]) + int(r["seg_off"]), "+" if c > 0 else "-", sid))
+    return out
+
+
 class AmbiError(RuntimeError):
     def __init__(self, lib, code, what=""):
         self.code = code
@@ -231,6 +274,14 @@ def _declare(L):
         "ambi_batch_path_align_result": (C.c_int, [vp, i32, _P(PathAlign)]),
         "ambi_batch_path_align_runs": (C.c_int, [vp, i32, _P(AlignRun), i32, pi32]),
         "ambi_batch_path_align_device": (C.c_int, [vp, _P(vp), pi64, pi64]),
+        "ambi_batch_set_unit_seg_lengths": (C.c_int, [vp, i32, pi64, i32]),
+        "ambi_batch_path_coords": (C.c_int, [vp, i32, vp, i32, vp]),
+        "ambi_batch_path_coords_wait": (C.c_int, [vp]),
+        "ambi_batch_path_coords_summary": (C.c_int, [vp, i32, _P(UnitCoords)]),
+        "ambi_batch_path_coords_result": (C.c_int, [vp, i32, _P(Lift)]),
+        "ambi_batch_path_coords_copy": (C.c_int, [vp, i32, i64, i64, pi64]),
+        "ambi_batch_path_coords_plane_device": (C.c_int, [vp, _P(vp), pi64, pi64, i32]),
+        "ambi_batch_path_coords_device": (C.c_int, [vp, _P(vp), pi64, pi64]),
         "ambi_graph_sequences": (i64, [vp, vp, i64, pi64]),
         "ambi_batch_set_unit_sequences": (C.c_int, [vp, i32, vp, pi64]),
         "ambi_batch_sequence": (C.c_int, [vp, i32, i32, i32, i64, vp]),
@@ -929,6 +980,65 @@ class Batch:
         then at runs_off max(dmax, 1) run slots per entry."""
         p, n, o = C.c_void_p(), C.c_int64(), C.c_int64()
         self._ck(self.lib.ambi_batch_path_align_device(self.h, C.byref(p), C.byref(n), C.byref(o)), "path_align_device")
+        return p.value or 0, n.value, o.value
+
+    def set_unit_seg_lengths(self, u, lengths):
+        """Segment lengths in base pairs of a unit (ambi_batch_set_unit_seg_lengths): local segment i + 1 is lengths[i] long,
+        0 .. 2^31 - 1 each, n_seg of them.  Units built from a graph have end - start of their SEG lines already."""
+        a, p = _arr(lengths, np.int64)
+        self._ck(self.lib.ambi_batch_set_unit_seg_lengths(self.h, u, p, len(a)), "set_unit_seg_lengths")
+
+    def path_coords(self, which=1, queries=None, stream=None):
+        """Queues the scan of every unit's path into base-pair offsets and, behind it, the lift-over queries (a LIFT_QUERY_DTYPE
+        array, lift_queries makes one; None: just the coordinates) over the last run's paths behind that run
+        (ambi_batch_path_coords); `stream` is not blocked."""
+        q = np.zeros(0, LIFT_QUERY_DTYPE) if queries is None else np.ascontiguousarray(queries, LIFT_QUERY_DTYPE).ravel()
+        self._ck(self.lib.ambi_batch_path_coords(self.h, which, C.c_void_p(q.ctypes.data if len(q) else 0), len(q), C.c_void_p(stream or 0)), "path_coords")
+        self._n_lifted = len(q)                         # (of the request the engine took)
+
+    def path_coords_wait(self):
+        """Waits for summaries and answers in host memory (the run's results are final first); the readers below answer afterwards."""
+        self._ck(self.lib.ambi_batch_path_coords_wait(self.h), "path_coords_wait")
+
+    def path_coords_summaries(self):
+        """Every unit's summary as a structured array (UNIT_COORDS_DTYPE): status, cells, runs, empty_cells, bp_len, bp_minus."""
+        out = np.zeros(self.size(), UNIT_COORDS_DTYPE)
+        for u in range(len(out)):
+            self._ck(self.lib.ambi_batch_path_coords_summary(self.h, u, C.cast(out.ctypes.data + u * UNIT_COORDS_DTYPE.itemsize, _P(UnitCoords))), "path_coords_summaries")
+        return out
+
+    def path_coords_results(self):
+        """The answers of the last request as a structured array (LIFT_DTYPE): status, cell, seg, seg_off, cell_start per query."""
+        self._ck(self.lib.ambi_batch_path_coords_device(self.h, None, None, None), "path_coords_results")   # (the state check: a waited-for request of the last run)
+        out = np.zeros(getattr(self, "_n_lifted", 0), LIFT_DTYPE)
+        for i in range(len(out)):
+            self._ck(self.lib.ambi_batch_path_coords_result(self.h, i, C.cast(out.ctypes.data + i * LIFT_DTYPE.itemsize, _P(Lift))), "path_coords_results")
+        return out
+
+    def path_coords_copy(self, u, first=0, n=None):
+        """The entries [first, first + n) of unit u's plane (all cells + 1 of them by default) as an int64 array: entry k is the
+        base pairs in front of cell k, the last one the amplicon's length (ambi_batch_path_coords_copy)."""
+        if n is None:
+            s = UnitCoords()
+            self._ck(self.lib.ambi_batch_path_coords_summary(self.h, u, C.byref(s)), "path_coords_copy")
+            n = s.cells + 1 - first
+        out = np.zeros(max(n, 0), np.int64)
+        self._ck(self.lib.ambi_batch_path_coords_copy(self.h, u, first, n, out.ctypes.data_as(_P(C.c_int64))), "path_coords_copy")
+        return out
+
+    def path_coords_plane_device(self):
+        """(address, bytes, unit_off) of the plane area in device memory (ambi_batch_path_coords_plane_device): unit u's int64
+        slice starts at unit_off[u]."""
+        U = self.size()
+        p, n, off = C.c_void_p(), C.c_int64(), np.zeros(U, np.int64)
+        self._ck(self.lib.ambi_batch_path_coords_plane_device(self.h, C.byref(p), C.byref(n), off.ctypes.data_as(_P(C.c_int64)), U), "path_coords_plane_device")
+        return p.value or 0, n.value, off
+
+    def path_coords_device(self):
+        """(address, bytes, results_off) of the block in device memory (ambi_batch_path_coords_device), for collectives: the
+        units' summaries, then at results_off the answers."""
+        p, n, o = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.ambi_batch_path_coords_device(self.h, C.byref(p), C.byref(n), C.byref(o)), "path_coords_device")
         return p.value or 0, n.value, o.value
 
     def set_unit_sequences(self, u, bases, seg_off):

@@ -14,6 +14,7 @@
 #include "ambi_junc_profile.hpp"
 #include "ambi_path_align.hpp"
 #include "ambi_path_compare.hpp"
+#include "ambi_path_coords.hpp"
 #include "ambi_profile.hpp"
 #include "ambi_sequence.hpp"
 
@@ -91,7 +92,7 @@ class Backend {
     virtual int all_paths(int unit, int pass, int64_t first, int64_t count, int32_t* lengths, int32_t* cells, int64_t stride) = 0;
 
     // ---- on-request profiles of every unit's path (which: 0 getBFB, 1 after indelBFB) ----
-    // Seven kinds, one life cycle.  A kind is a block that travels to the host, a tail behind it that travels up once per layout (int64
+    // Eight kinds, one life cycle.  A kind is a block that travels to the host, a tail behind it that travels up once per layout (int64
     // offsets per unit, or the request's entries), a side area that stays where it was computed, an image that goes up when the device
     // holds another version of it, and its kernels (U: units; [..]: arrays padded to 16 bytes):
     //   kind         block                                               tail                  side area                   image      kernels (ambi_*_kernel)
@@ -105,15 +106,18 @@ class Backend {
     //   kCompare     [PathCompare[n]]                                    n pairs (A, B)        -                           its given  path_compare
     //   kAlign       [PathAlign[n]] [AlignRun[n * dmax]]                 n triples (A, B, o)   a history area per          its given  path_align
     //                                                                                          workgroup
+    //   kCoords      [UnitCoords[U]] [PathLift[n]]                       plane_off[U],         plane: int64 per cell of    length     path_coords, path_lift
+    //                                                                    n queries             every unit's path capacity
+    //                                                                                          plus one
     // (stage code: ambi_profile.hpp, ambi_junc_profile.hpp, ambi_frag_profile.hpp, ambi_evidence_profile.hpp, ambi_fold_profile.hpp,
-    // ambi_path_compare.hpp, ambi_path_align.hpp.)
-    // The last two bring their entries and a cap with the request (compare() and align() below) and are laid out with every request.
+    // ambi_path_compare.hpp, ambi_path_align.hpp, ambi_path_coords.hpp.)
+    // The last three bring their entries with the request (compare(), align() and coords() below) and are laid out with every request.
     // profile() queues the block of the last run's results behind that run, profile_wait() waits for it in host memory; the typed
     // getters below then answer from that copy.  The default runs the stage on the host over the downloaded blob (the host
     // simulation); the HIP engine overrides the virtual entries with its kernels and never reaches it.
     // profile_bind: the packed inputs the backend was (or will be) uploaded with; they outlive the backend.
-    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4, kCompare = 5, kAlign = 6 };
-    static constexpr int kProfileKinds = 7;
+    enum ProfileKind { kCopyNumber = 0, kJunction = 1, kFragment = 2, kEvidence = 3, kFold = 4, kCompare = 5, kAlign = 6, kCoords = 7 };
+    static constexpr int kProfileKinds = 8;
     void profile_bind(const HostBatch* hb) { prof_hb_ = hb; for (ProfileState& P : prof_) P.view = nullptr; }
     virtual int profile(ProfileKind kind, int which, void* stream) {
         (void)stream;
@@ -131,6 +135,7 @@ class Backend {
             case kFold: host_fold_profile(blob.data(), which, P); break;
             case kCompare: host_compare(blob.data(), P); break;
             case kAlign: host_align(blob.data(), P); break;
+            case kCoords: host_coords(blob.data(), which, P); break;
         }
         P.view = nullptr;
         return 0;
@@ -138,6 +143,9 @@ class Backend {
     virtual int profile_wait(ProfileKind kind) {
         ProfileState& P = prof_[kind];
         if (P.blob.empty()) return ST_ERR_BAD_INPUT;
+        // (the coords kind promises the LAST run's paths whatever ran between request and wait: the engine queues it again when the
+        // results' epoch has moved; here, where nothing counts epochs, the request is simply answered once more from its own copy)
+        if (kind == kCoords) { if (int rc = profile(kCoords, coords_which_, nullptr)) return rc; }
         P.view = P.blob.data();
         return 0;
     }
@@ -245,6 +253,44 @@ class Backend {
         return reinterpret_cast<const AlignRun*>(P.view + align_runs_off(align_pairs())) + (int64_t)pair * align_stride(pair_of(kAlign).dmax);
     }
 
+    // ---- path coordinates (ambi_path_coords.hpp, kCoords): every request scans every unit's path into the plane and answers its queries ----
+    // The request owns a copy of its queries, as a PairRequest owns its entries: a request that profile_wait() has to queue again
+    // answers what it was asked.  A unit index outside the bound batch is refused here, never on the device.  n = 0 is "just the
+    // coordinates".  The bound batch's length image (HostBatch::len) must be sealed.
+    int coords(int which, const LiftQuery* queries, int n, void* stream) {
+        if (!prof_hb_ || n < 0 || (n > 0 && !queries)) return ST_ERR_BAD_INPUT;
+        for (int i = 0; i < n; i++) if (queries[i].unit < 0 || (size_t)queries[i].unit >= prof_hb_->units.size()) return ST_ERR_BAD_INPUT;
+        lift_.assign(queries, queries + n);
+        coords_which_ = which;
+        return profile(kCoords, which, stream);
+    }
+    int coords_queries() const { return (int)lift_.size(); }
+    int coords_summary(int unit, UnitCoords* out) const {
+        const ProfileState& P = prof_[kCoords];
+        if (!P.view || unit < 0 || unit >= (int)cplane_off_.size() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const UnitCoords*>(P.view)[unit];
+        return 0;
+    }
+    int coords_result(int query, PathLift* out) const {
+        const ProfileState& P = prof_[kCoords];
+        if (!P.view || query < 0 || query >= coords_queries() || !out) return ST_ERR_BAD_INPUT;
+        *out = reinterpret_cast<const PathLift*>(P.view + coords_results_off((int64_t)cplane_off_.size()))[query];
+        return 0;
+    }
+    // the entries [first, first + n) of a unit's plane to host memory (nothing else of the plane area travels), and the area where it
+    // was computed (device memory of the HIP engine) with every unit's byte offset in it; valid after profile_wait(kCoords)
+    virtual int coords_copy(int unit, int64_t first, int64_t n, int64_t* out) {
+        const ProfileState& P = prof_[kCoords];
+        if (!P.view || unit < 0 || unit >= (int)cplane_off_.size() || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) memcpy(out, reinterpret_cast<const uint8_t*>(cplanes_.data()) + cplane_off_[(size_t)unit] + 8 * first, (size_t)(8 * n));
+        return 0;
+    }
+    virtual int coords_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) {
+        if (!prof_[kCoords].view) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = cplanes_.data();
+        return coords_plane_offsets(bytes, unit_off, cap);
+    }
+
     // ---- nucleotide sequence of every unit's path (ambi_sequence.hpp; which as above) over the units [first, first + count) ----
     // sequence() runs pass 0 of the extents stage behind the last run and fetches its totals (count x {bytes, runs}: the one small
     // device-to-host trip of a request), sizes the extent arrays and the output block from them, and queues pass 1 and the fill
@@ -332,6 +378,7 @@ class Backend {
             case kFold: P.bytes = fold_block_layout(units, P.off); plane_bytes_ = fold_plane_layout(units, plane_off_); break;
             case kCompare: P.bytes = compare_block_bytes(compare_pairs()); P.off.clear(); break;
             case kAlign: P.bytes = align_block_bytes(align_pairs(), pair_of(kAlign).dmax); P.off.clear(); break;
+            case kCoords: P.bytes = coords_block_bytes((int64_t)units.size(), coords_queries()); P.off.clear(); cplane_bytes_ = coords_plane_layout(units, cplane_off_); break;
         }
     }
     // The windows of the bound batch; the environment variables (tests) can only shrink them (capped_window).
@@ -371,6 +418,18 @@ class Backend {
         if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
         if (bytes) *bytes = 2 * plane_bytes_;
         if (unit_off) for (int u = 0; u < U; u++) unit_off[u] = plane_off_[(size_t)u];
+        return 0;
+    }
+    std::vector<int64_t> cplane_off_;    // the coords kind's plane: every unit's byte offset and the size (profile_layout)
+    int64_t cplane_bytes_ = 0;
+    std::vector<LiftQuery> lift_;        // the queries of the last coords(), and its `which`
+    int coords_which_ = 1;
+    int lift_grid_of(int threads) const { return lift_grid(coords_queries(), threads, env_int("AMBI_LIFT_GRID")); }
+    int coords_plane_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
+        const int U = (int)cplane_off_.size();
+        if (unit_off && cap < U) return ST_ERR_BAD_INPUT;
+        if (bytes) *bytes = cplane_bytes_;
+        if (unit_off) for (int u = 0; u < U; u++) unit_off[u] = cplane_off_[(size_t)u];
         return 0;
     }
     int sequence_offsets(int64_t* bytes, int64_t* unit_off, int cap) const {
@@ -497,7 +556,19 @@ class Backend {
             align_pair(g, prof_hb_->units.data(), blob, given, Q.entries.data(), i, Q.dmax, lds.data(), lds.data() + compare_lds_bytes(Q.dmax) / 4, hist.data(),
                        reinterpret_cast<PathAlign*>(P.blob.data()), reinterpret_cast<AlignRun*>(P.blob.data() + align_runs_off(Q.n())));
     }
+    void host_coords(const uint8_t* blob, int which, ProfileState& P) {
+        const std::vector<UnitIn>& units = prof_hb_->units;
+        const LenImage& I = prof_hb_->len;
+        const LenArgs A{I.len.data(), I.len_off.data()};
+        cplanes_.resize((size_t)(cplane_bytes_ / 16) + 1);   // (kept between requests as the device keeps its area: stale values behind it)
+        uint8_t* area = reinterpret_cast<uint8_t*>(cplanes_.data());
+        HostGroup g;
+        for (size_t u = 0; u < units.size(); u++) coords_unit(g, units.data(), blob, A, (int)u, which, area, cplane_off_.data(), P.blob.data());
+        PathLift* out = reinterpret_cast<PathLift*>(P.blob.data() + coords_results_off((int64_t)units.size()));
+        for (int64_t i = 0; i < (int64_t)lift_.size(); i++) lift_query(units.data(), blob, A, which, area, cplane_off_.data(), P.blob.data(), lift_.data(), i, out);
+    }
     std::vector<Seq16A> depth_;          // the default implementation's depth area (16-byte aligned)
+    std::vector<Seq16A> cplanes_;        // the default implementation's coordinate plane (16-byte aligned)
     std::vector<Seq16A> planes_;         // the default implementation's fold and cover planes (16-byte aligned)
     std::vector<Seq16A> seq_out_;        // the default implementation's output block (16-byte aligned)
 };

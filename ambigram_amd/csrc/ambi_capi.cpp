@@ -115,7 +115,7 @@ struct ambi_batch {
     bool uploaded = false, downloaded = false;
     bool sharded_ready = false;   // ambi_batch_run_sharded has run: results are read where the shares left them (headers + run-length paths; a share's blob on demand)
     bool ran = false;         // a run has been queued since the upload (ambi_batch_profile needs results to profile)
-    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
+    bool profiled[Backend::kProfileKinds] = {false, false, false, false, false, false, false, false};   // [Backend::ProfileKind] its wait has returned for the last run: the kind's getters answer
     ComparePaths cmp;         // the given paths of ambi_batch_set_compare_paths (ambi_path_compare.hpp); not part of the batch image
     bool sequenced = false;   // ambi_batch_sequence_wait has returned for the last run: the sequence getters answer
     int seq_first = 0, seq_count = 0;   // the units of the last ambi_batch_sequence
@@ -977,6 +977,69 @@ int ambi_batch_path_align_runs(const ambi_batch_t* b, int32_t pair, ambi_align_r
     if (cap < h.n_runs || (h.n_runs > 0 && !out)) return AMBI_ERR_ARG;
     if (h.n_runs > 0) memcpy(out, r, sizeof(AlignRun) * (size_t)h.n_runs);
     return 0;
+}
+// ---- path coordinates (ambi_path_coords.hpp): the request carries its queries, the life cycle is the profiles' ----
+int ambi_batch_set_unit_seg_lengths(ambi_batch_t* b, int32_t unit, const int64_t* len, int32_t n) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size() || n != b->hb.units[unit].n_seg || (n > 0 && !len)) return AMBI_ERR_ARG;
+    if (!b->shards.empty()) return AMBI_ERR_STATE;
+    std::vector<int32_t> bp((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (len[i] < 0 || len[i] > 0x7fffffffll) return AMBI_ERR_ARG;
+        bp[(size_t)i] = (int32_t)len[i];
+    }
+    b->hb.len.set((size_t)unit, n, bp.data());
+    b->profiled[Backend::kCoords] = false;
+    return 0;
+}
+int ambi_batch_path_coords(ambi_batch_t* b, int32_t which, const ambi_lift_query_t* q, int32_t n, void* hip_stream) {
+    if (!b || n < 0 || (n > 0 && !q)) return AMBI_ERR_ARG;
+    if (b->sharded_ready) return AMBI_ERR_UNSUPPORTED;   // (one plane per share, and a request's queries name units of every share)
+    if (!(b->uploaded && b->ran)) return AMBI_ERR_STATE;
+    if (which < 0 || which > 1) return AMBI_ERR_ARG;
+    static_assert(sizeof(ambi_lift_query_t) == sizeof(LiftQuery) && sizeof(ambi_lift_query_t) == 16, "ambi_lift_query_t is ambi::LiftQuery, 16 bytes");
+    const int U = (int)b->hb.units.size();
+    for (int i = 0; i < n; i++) if (q[i].unit < 0 || q[i].unit >= U) return AMBI_ERR_ARG;
+    b->hb.len.seal(b->hb.units);   // every unit has lengths from here on (zeros where nothing was attached)
+    b->profiled[Backend::kCoords] = false;
+    const int rc = b->be->coords(which, reinterpret_cast<const LiftQuery*>(q), n, hip_stream);
+    return rc == ST_ERR_BAD_INPUT ? AMBI_ERR_STATE : rc;
+}
+int ambi_batch_path_coords_wait(ambi_batch_t* b) {
+    if (b && b->sharded_ready) return AMBI_ERR_UNSUPPORTED;
+    return profile_wait(b, Backend::kCoords);
+}
+int ambi_batch_path_coords_summary(const ambi_batch_t* b, int32_t unit, ambi_unit_coords_t* out) {
+    if (!b || !out || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kCoords]) return AMBI_ERR_STATE;
+    static_assert(sizeof(ambi_unit_coords_t) == sizeof(UnitCoords) && sizeof(ambi_unit_coords_t) == 32, "ambi_unit_coords_t is ambi::UnitCoords, 32 bytes");
+    return b->be->coords_summary(unit, reinterpret_cast<UnitCoords*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_path_coords_result(const ambi_batch_t* b, int32_t query, ambi_lift_t* out) {
+    if (!b || !out) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kCoords]) return AMBI_ERR_STATE;
+    if (query < 0 || query >= b->be->coords_queries()) return AMBI_ERR_ARG;
+    static_assert(sizeof(ambi_lift_t) == sizeof(PathLift) && sizeof(ambi_lift_t) == 32, "ambi_lift_t is ambi::PathLift, 32 bytes");
+    return b->be->coords_result(query, reinterpret_cast<PathLift*>(out)) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_path_coords_copy(ambi_batch_t* b, int32_t unit, int64_t first, int64_t n, int64_t* out) {
+    if (!b || unit < 0 || unit >= (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kCoords]) return AMBI_ERR_STATE;
+    UnitCoords s;
+    if (b->be->coords_summary(unit, &s)) return AMBI_ERR_STATE;
+    const int64_t entries = (int64_t)s.cells + 1;
+    if (first < 0 || n < 0 || first > entries || n > entries - first || (n > 0 && !out)) return AMBI_ERR_ARG;
+    return b->be->coords_copy(unit, first, n, out) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_path_coords_plane_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap) {
+    if (!b) return AMBI_ERR_ARG;
+    if (!b->profiled[Backend::kCoords] || b->sharded_ready) return AMBI_ERR_STATE;
+    if (unit_off && cap < (int)b->hb.units.size()) return AMBI_ERR_ARG;
+    return b->be->coords_device(dev_ptr, bytes, unit_off, cap) ? AMBI_ERR_STATE : 0;
+}
+int ambi_batch_path_coords_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* results_off) {
+    const int rc = profile_device(b, Backend::kCoords, dev_ptr, bytes);
+    if (rc == 0 && results_off) *results_off = coords_results_off((int64_t)b->hb.units.size());
+    return rc;
 }
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; script/main.py:537-588, :709-740) ----
 int ambi_batch_set_unit_sequences(ambi_batch_t* b, int32_t unit, const uint8_t* bases, const int64_t* seg_off) {

@@ -39,6 +39,11 @@
 //                                                  the comparison's trim and rounds with every round's V kept in the workgroup's
 //                                                  history area, a one-thread traceback, a whole-group run merge
 //                                                  (ambi_path_align.hpp)                           <- the history: D^2 / 2 ints a pair
+//   ambi_path_coords_kernel       1 block / unit   on request: the base-pair offset of every cell of the path by a 64-bit scan, two cells
+//                                                  and one 16-byte store per thread and round, + summary
+//                                                  (ambi_path_coords.hpp)                          <- store-bound, 8 bytes / cell
+//   ambi_path_lift_kernel         1 thread / query on request, behind the scan: amplicon position -> cell, segment, offset in the
+//                                                  segment by a bisection over the unit's slice    <- 23 dependent loads at most
 //                                                  (the profile kernels share unit prologue, chunked cell read and window rule --
 //                                                  profile_path, path_load_chunk, capped_window of ambi_profile.hpp -- and the two tables
 //                                                  their probe, lds_find / lds_claim of ambi_junc_profile.hpp; every reader of a unit's
@@ -709,6 +714,23 @@ __global__ __launch_bounds__(kProfileThreads) void ambi_path_align_kernel(BatchA
         __syncthreads();
     }
 }
+// ---- path coordinates (ambi_path_coords.hpp; launched by HipBackend::profile_queue only) ----
+// The scan: one workgroup of 256 threads per unit, grid-stride over the units, 512 cells a round; 256 bytes of group memory for the
+// group's scans.  Store-bound: 8 bytes per cell out, as one 16-byte store per thread and round, for 2 bytes in.  The lift, behind it
+// on the same stream: one thread per query, grid-stride; a query costs a bisection over its unit's slice (23 dependent 8-byte loads
+// at most) -- latency-bound, and hidden by the number of queries in flight.
+__global__ __launch_bounds__(kProfileThreads) void ambi_path_coords_kernel(BatchArgs A, LenArgs I, int which, uint8_t* planes, const int64_t* plane_off, uint8_t* block) {
+    BlockGroup g(reinterpret_cast<int*>(ambi_lds));
+    for (int u = (int)blockIdx.x; u < A.n_units; u += (int)gridDim.x) {
+        coords_unit(g, A.units, A.results, I, u, which, planes, plane_off, block);
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(kProfileThreads) void ambi_path_lift_kernel(BatchArgs A, LenArgs I, int which, const uint8_t* planes, const int64_t* plane_off, const uint8_t* block,
+                                                                         const LiftQuery* queries, int64_t n, PathLift* out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        lift_query(A.units, A.results, I, which, planes, plane_off, block, queries, i, out);
+}
 // ---- nucleotide sequence of the paths (ambi_sequence.hpp; launched by HipBackend::sequence only) ----
 // Extents: one workgroup of 256 threads per unit of the request, grid-stride; 160 bytes of group memory for the group's
 // reductions and scans (read-bound: 2 bytes per cell, twice -- pass 0 counts, pass 1 writes the extents).
@@ -893,8 +915,9 @@ struct Lease {
     RequestBlock prof[Backend::kProfileKinds];   // [Backend::ProfileKind]
     // the batch's fragment image (HipBackend::fragment_image: [cells][frag_off][cell_off][pref_off][n_frag]) and the given paths of
     // the compare and of the align kind (ComparePaths::image: [off][len][cells]; each kind its request's own copy of the set)
-    enum { kFragImage = 0, kGivenImage = 1 };   // (the given sets: kGivenImage + kind - kCompare)
-    DeviceImage img[3];
+    // and the batch's length image (HipBackend::length_image: [len][len_off])
+    enum { kFragImage = 0, kGivenImage = 1, kLenImage = 3 };   // (the given sets: kGivenImage + kind - kCompare)
+    DeviceImage img[4];
     // path sequences (HipBackend::sequence): the batch's sequence image [bases][seg_pos][store_off][pos_off], the working block of a
     // request [totals][ext_off, out_off, tile_off][ext_src][ext_out] and the output block; the pinned twin carries the image up, the
     // totals down and the three offset tables up.  Events: the run's stream reached / all queued work done / timing pairs
@@ -2310,6 +2333,21 @@ class HipBackend : public Backend {
         given_args_[kind - kCompare] = compare_given(D.d, I);
         return 0;
     }
+    // The length image of the batch (LenImage, ambi_pack.hpp) on the device, in the same way.
+    LenArgs len_args_{};
+    int length_image(hipStream_t s) {
+        DeviceImage& D = lease_->img[Lease::kLenImage];
+        const LenImage& I = hb().len;
+        const int64_t U = (int64_t)hb().units.size();
+        if ((int64_t)I.len_off.size() != U) return ST_ERR_BAD_INPUT;   // (not sealed)
+        const int64_t b0 = pad16(4 * (int64_t)I.len.size()), total = b0 + pad16(8 * U) + 16;
+        if (int rc = D.upload(s, I.version, total, [&](uint8_t* h) {
+                if (!I.len.empty()) memcpy(h, I.len.data(), 4 * I.len.size());
+                if (U > 0) memcpy(h + b0, I.len_off.data(), (size_t)(8 * U));
+            })) return rc;
+        len_args_ = LenArgs{reinterpret_cast<const int32_t*>(D.d), reinterpret_cast<const int64_t*>(D.d + b0)};
+        return 0;
+    }
     // The on-request results are instances of one block (Lease::prof, req_, Backend::prof_); a kind has its own inputs, its own layout,
     // its own kernels with their LDS sizes, and nothing else: each of these is one switch below, and the table of the kinds is above
     // Backend::ProfileKind.  profile() queues the kind's kernels behind the run, then ONE device-to-host copy of the block on the
@@ -2335,6 +2373,11 @@ class HipBackend : public Backend {
                 R.laid_out = false;
                 if (int rc = given_image(kind, s)) return rc;
                 break;
+            case kCoords:   // (the queries come with the request: laid out every time, as above; nothing of the kind reads the image any more by then)
+                if (R.queued) HIP_CK(hipEventSynchronize(B.ev_done));
+                R.laid_out = false;
+                if (int rc = length_image(s)) return rc;
+                break;
         }
         // 2. layout: the block and its twin, the tail that travels up behind the block once per layout (the block's copies never touch
         // it), and the side area
@@ -2348,6 +2391,7 @@ class HipBackend : public Backend {
                 case kFold: tail[1] = {plane_off_.data(), 8 * U}; side_bytes = plane_bytes_ > 0 ? 2 * plane_bytes_ : 16; break;
                 case kCompare: tail[0] = {pair_of(kind).entries.data(), 8 * (int64_t)compare_pairs()}; break;
                 case kAlign: tail[0] = {pair_of(kind).entries.data(), 12 * (int64_t)align_pairs()}; side_bytes = align_grid_of() * align_history_bytes(pair_of(kind).dmax); break;
+                case kCoords: tail[0] = {cplane_off_.data(), 8 * U}; tail[1] = {lift_.data(), 16 * (int64_t)coords_queries()}; side_bytes = cplane_bytes_ > 0 ? cplane_bytes_ : 16; break;
             }
             const int64_t n_off = (tail[0].bytes + tail[1].bytes + 7) / 8;
             const int64_t total = P.bytes + n_off * (int64_t)sizeof(int64_t);   // (P.bytes is a multiple of 16)
@@ -2412,6 +2456,14 @@ class HipBackend : public Backend {
                                                   reinterpret_cast<AlignRun*>(B.d + align_runs_off(Q.n())));
                 break;
             }
+            case kCoords: {   // (the lift kernel behind the scan on one stream; a request without queries launches the scan alone)
+                const int64_t n = coords_queries();
+                hipLaunchKernelGGL(ambi_path_coords_kernel, grid, threads, scratch, s, A_, len_args_, which, B.side, off, B.d);
+                HIP_CK(hipGetLastError());
+                if (n > 0) hipLaunchKernelGGL(ambi_path_lift_kernel, dim3(lift_grid_of(kProfileThreads)), threads, 0, s, A_, len_args_, which, B.side, off, B.d,
+                                              reinterpret_cast<const LiftQuery*>(side_off), n, reinterpret_cast<PathLift*>(B.d + coords_results_off(U)));
+                break;
+            }
         }
         HIP_CK(hipGetLastError());
         // 5. copy: the block to its twin on the lease's copy stream
@@ -2469,6 +2521,18 @@ class HipBackend : public Backend {
         if (!prof_[kFold].view || !lease_) return ST_ERR_BAD_INPUT;
         if (ptr) *ptr = lease_->prof[kFold].side;
         return fold_plane_offsets(bytes, unit_off, cap);
+    }
+    // the coords kind's plane: a range of one unit's offsets to the host, and the area itself
+    int coords_copy(int unit, int64_t first, int64_t n, int64_t* out) override {
+        DeviceGuard dg_(device_);
+        if (!prof_[kCoords].view || !lease_ || !lease_->prof[kCoords].side || unit < 0 || unit >= (int)cplane_off_.size() || n < 0 || (n > 0 && !out)) return ST_ERR_BAD_INPUT;
+        if (n > 0) HIP_CK(hipMemcpy(out, lease_->prof[kCoords].side + cplane_off_[(size_t)unit] + 8 * first, (size_t)(8 * n), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int coords_device(void** ptr, int64_t* bytes, int64_t* unit_off, int cap) override {
+        if (!prof_[kCoords].view || !lease_) return ST_ERR_BAD_INPUT;
+        if (ptr) *ptr = lease_->prof[kCoords].side;
+        return coords_plane_offsets(bytes, unit_off, cap);
     }
     // ---- nucleotide sequence of the paths (ambi_sequence.hpp) ----
     // sequence() works on `stream` behind everything that writes the result blob in the last run (behind_results): the

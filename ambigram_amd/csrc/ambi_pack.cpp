@@ -128,6 +128,13 @@ int HostBatch::add_graph_chr(const LhGraph& g, int chr, const SolFile* sol, int 
     if (u >= 0) junc_global[u] = gidx;
     // the chromosome's bases, back to back in local id order (ambi_sequence.hpp), when the graph carries them
     if (u >= 0 && (int)g.seq_off.size() == g.n_seg() + 1) seq.set((size_t)u, n, g.seq_bases.data(), g.seq_off.data() + base);
+    // the chromosome's segment lengths in base pairs (ambi_path_coords.hpp): end - start, the convention of the sequences above
+    // (0-based, half-open); a segment that ends in front of its start, which read_fasta refuses, counts 0
+    if (u >= 0) {
+        std::vector<int32_t> bp((size_t)n);
+        for (int i = 0; i < n; i++) { const int64_t d = (int64_t)g.seg_end[base + i] - (int64_t)g.seg_start[base + i]; bp[(size_t)i] = d > 0 ? (int32_t)(d < 0x7fffffff ? d : 0x7fffffff) : 0; }
+        len.set((size_t)u, n, bp.data());
+    }
     // the chromosome's fragments as local ids (ambi_frag_profile.hpp), in the graph's order, with the way back to the graph's list
     if (u >= 0 && g.n_frag() > 0) {
         std::vector<rcell_t> fc; std::vector<int64_t> off(1, 0); std::vector<int32_t> fidx;

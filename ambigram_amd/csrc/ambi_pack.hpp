@@ -94,10 +94,34 @@ struct FragImage {
     }
 };
 
+// Length image of a batch (ambi_path_coords.hpp): per unit its n_seg segment lengths in base pairs, int32, in local id order.  Host
+// memory, with the life of the other two images: nothing of it travels with the batch; a backend takes it to the device at the first
+// path-coordinates request and again when its version has moved.  A unit nobody gave lengths has lengths of zero, as a unit without
+// bases has an empty store: its amplicon is 0 bp long.
+struct LenImage {
+    std::vector<int32_t> len;          // all units' lengths one after the other
+    std::vector<int64_t> len_off;      // [U] index of a unit's first length, -1: not set yet
+    int64_t version = 0;               // moves with every change
+    // the lengths of unit `unit`: local segment i + 1 is src[i] base pairs long (0 .. 2^31 - 1: the callers check); a second call replaces the first
+    void set(size_t unit, int n_seg, const int32_t* src) {
+        if (len_off.size() <= unit) len_off.resize(unit + 1, -1);
+        len_off[unit] = (int64_t)len.size();
+        len.insert(len.end(), src, src + n_seg);
+        version++;
+    }
+    // every unit has lengths afterwards (zeros where nothing was attached); idempotent
+    void seal(const std::vector<UnitIn>& units) {
+        if (len_off.size() < units.size()) len_off.resize(units.size(), -1);
+        for (size_t u = 0; u < units.size(); u++)
+            if (len_off[u] < 0) { len_off[u] = (int64_t)len.size(); len.insert(len.end(), (size_t)units[u].n_seg, 0); version++; }
+    }
+};
+
 struct HostBatch {
     std::vector<UnitIn> units;
     SeqImage seq;                      // bases of the units' segments (empty unless sequences were attached)
     FragImage frag;                    // .juncs fragments of the units (empty unless fragments were attached)
+    LenImage len;                      // base-pair lengths of the units' segments (zeros unless lengths were attached)
     std::vector<double> seg_cn;
     std::vector<Junction> juncs;
     std::vector<JuncEnds> junc_ends;   // junc_ends(juncs[i]) of every record

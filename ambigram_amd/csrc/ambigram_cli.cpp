@@ -288,6 +288,14 @@ int run_sc_bfb(Args& A) {
 // row a header line -- A, the row's tag, chromosome index, orient, dist, n_runs -- then one line per run: D or I, a_pos, b_pos, len
 // and the run's cells (of a for D, of Bo for I) as a printed path with global ids.  A row whose two dist are both -1 gets the header
 // alone, with orient -1, dist -1 and 0 runs.
+// --path_coords <file> / --lift <queries> --lift_out <file> (where in the genome does position p of the amplicon come from?): after the
+// run the device's path coordinates of the final paths (ambi_batch_path_coords, one request) give, in --path_coords, one tab-separated
+// row per chromosome -- cells, runs, cells of length 0, the amplicon's length in base pairs, the base pairs crossed on the '-' strand
+// --; and in --lift_out one row per line `<chromosome index> <pos>` of the query file, in its order -- pos, cell, segment id, strand,
+// the segment's chromosome name, genomic position (0-based: the segment's start + its offset) --, with `-1 0 . . -1` behind pos for
+// a position outside the amplicon.  pos is the 0-based position in the chromosome's record of --out_fasta.  One sample, one device;
+// a query file that cannot be read, a line that is no query or a chromosome index outside the sample is an error found when the
+// sample is read, in front of the run.  stdout and the side files are unchanged.
 // --ref_fasta <file> --out_fasta <file> (what script/main.py:537-588 bfb2fasta does with bedtools): the nucleotide sequence of every
 // chromosome's final path, assembled on the device (ambi_batch_sequence) from the segments' bases chrom[start .. end) of the
 // reference FASTA (0-based, half-open).  One record per chromosome that has a path, `>BFBPATH` when the sample has one chromosome
@@ -333,6 +341,10 @@ int run_bfb(Args& A) {
     const std::string path_align = A.kv.count("path_align") ? A.kv["path_align"] : "";
     if (path_compare.empty() && !path_align.empty()) { std::cerr << "--path_align goes with --path_compare <file>" << std::endl; return 2; }
     if (!path_compare.empty() && A.kv.count("devices")) { std::cerr << "--path_compare: not available with --devices (a pair may span shares)" << std::endl; return 2; }
+    const std::string path_coords = A.kv.count("path_coords") ? A.kv["path_coords"] : "", lift = A.kv.count("lift") ? A.kv["lift"] : "", lift_out = A.kv.count("lift_out") ? A.kv["lift_out"] : "";
+    const std::string coords_opt = !path_coords.empty() ? "--path_coords" : !lift.empty() ? "--lift" : !lift_out.empty() ? "--lift_out" : "";
+    if (lift.empty() != lift_out.empty()) { std::cerr << "--lift <queries> and --lift_out <file> go together" << std::endl; return 2; }
+    if (!coords_opt.empty() && A.kv.count("devices")) { std::cerr << coords_opt << ": not available with --devices (one plane per share)" << std::endl; return 2; }
     const std::string ref_fasta = A.kv.count("ref_fasta") ? A.kv["ref_fasta"] : "", out_fasta = A.kv.count("out_fasta") ? A.kv["out_fasta"] : "";
     if (ref_fasta.empty() != out_fasta.empty()) { std::cerr << "--ref_fasta and --out_fasta go together" << std::endl; return 2; }
     const int64_t fasta_chunk = A.kv.count("fasta_chunk_bytes") ? atoll(A.kv["fasta_chunk_bytes"].c_str()) : (256ll << 20);
@@ -355,6 +367,8 @@ int run_bfb(Args& A) {
         if (files.empty()) files.push_back(A.kv["in_lh"]);
     }
     if (!truth.empty() && files.size() > 1) { std::cerr << "--truth: one sample only (a truth file has one line per chromosome of one sample)" << std::endl; return 2; }
+    if (!coords_opt.empty() && files.size() > 1) { std::cerr << coords_opt << ": one sample only (a query names a chromosome of one sample)" << std::endl; return 2; }
+    std::vector<ambi_lift_query_t> lift_q;           // --lift: the queries in file order, unit = chromosome index until the units are known
     std::vector<std::vector<int32_t>> truth_cells;   // --truth: [chromosome] the line's path in local ids, empty for `.`
     int rc;
     std::vector<Sample> samples(files.size());
@@ -405,6 +419,26 @@ int run_bfb(Args& A) {
             if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
                 std::cerr << fold_opt << ": " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device profile" << std::endl;
                 return 2;
+            }
+        }
+        if (!coords_opt.empty()) {
+            ambi_graph_props(g, &S.ins_mode, &S.con_mode, S.main_chr, sizeof(S.main_chr));
+            if (ambi_graph_trx_before(g, nullptr, 0) > 0 || S.ins_mode == 2 || S.con_mode == 2) {
+                std::cerr << coords_opt << ": " << S.lh << " is a PROP I1 / C1 / I2 / C2 sample; its printed paths are rebuilt on the host and have no device coordinates" << std::endl;
+                return 2;
+            }
+            if (!lift.empty()) {   // the query file is read here, in front of anything printed or run: `<chromosome index> <pos>` per line
+                std::ifstream qf(lift);
+                if (!qf) return die("Cannot open file " + lift);
+                int32_t ns, nj, nc;
+                ambi_graph_sizes(g, &ns, &nj, &nc);
+                std::string line;
+                for (int ln = 1; std::getline(qf, line); ln++) {
+                    long long c = 0, pos = 0; char tail = 0;
+                    if (sscanf(line.c_str(), "%lld %lld %c", &c, &pos, &tail) != 2) { std::cerr << "--lift: line " << ln << " of " << lift << " is no query (<chromosome index> <pos>)" << std::endl; return 2; }
+                    if (c < 0 || c >= nc) { std::cerr << "--lift: chromosome " << c << " on line " << ln << " of " << lift << " lies outside the sample (0 .. " << nc - 1 << ")" << std::endl; return 2; }
+                    lift_q.push_back(ambi_lift_query_t{(int32_t)c, 0, (int64_t)pos});
+                }
             }
         }
         if (!path_compare.empty()) {
@@ -667,6 +701,38 @@ int run_bfb(Args& A) {
                     for (int k = 0; k < e.steps; k++)
                         if (fold[k]) fprintf(pf, "%s\t%d\t%d\t%d\t%d\t%d\n", S.lh.c_str(), c, k, AMBI_FOLD_ALIGN(fold[k]), AMBI_FOLD_ARM(fold[k]), cover[k] - 1);
                 }
+            fclose(pf);
+        }
+    }
+    if (!coords_opt.empty()) {
+        Sample& S = samples[0];
+        std::vector<int> chr_of_query(lift_q.size());
+        for (size_t i = 0; i < lift_q.size(); i++) { chr_of_query[i] = lift_q[i].unit; lift_q[i].unit = S.unit[(size_t)chr_of_query[i]]; }
+        if ((rc = ambi_batch_path_coords(b, 1, lift_q.empty() ? nullptr : lift_q.data(), (int32_t)lift_q.size(), nullptr)) != 0 || (rc = ambi_batch_path_coords_wait(b)) != 0)
+            return die(std::string("engine: ") + ambi_error_string(rc));
+        if (!path_coords.empty()) {
+            FILE* pf = fopen(path_coords.c_str(), "w");
+            if (!pf) return die("Cannot open file " + path_coords);
+            for (int c = 0; c < S.n_chr; c++) {
+                ambi_unit_coords_t e;
+                if ((rc = ambi_batch_path_coords_summary(b, S.unit[c], &e)) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                fprintf(pf, "%d\t%d\t%d\t%lld\t%lld\n", e.cells, e.runs, e.empty_cells, (long long)e.bp_len, (long long)e.bp_minus);
+            }
+            fclose(pf);
+        }
+        if (!lift_out.empty()) {
+            FILE* pf = fopen(lift_out.c_str(), "w");
+            if (!pf) return die("Cannot open file " + lift_out);
+            for (size_t i = 0; i < lift_q.size(); i++) {
+                ambi_lift_t r;
+                if ((rc = ambi_batch_path_coords_result(b, (int32_t)i, &r)) != 0) { fclose(pf); return die(std::string("engine: ") + ambi_error_string(rc)); }
+                if (r.cell < 0) { fprintf(pf, "%lld\t-1\t0\t.\t.\t-1\n", (long long)lift_q[i].pos); continue; }
+                int32_t s, e;
+                ambi_graph_chromosome(S.g, chr_of_query[i], &s, &e);
+                const int id = s - 1 + (r.seg < 0 ? -r.seg : r.seg);
+                char nm[256]; ambi_graph_chrom_name(S.g, id, nm, sizeof(nm));
+                fprintf(pf, "%lld\t%d\t%d\t%c\t%s\t%lld\n", (long long)lift_q[i].pos, r.cell, id, r.seg > 0 ? '+' : '-', nm, (long long)S.seg_start[id - 1] + (long long)r.seg_off);
+            }
             fclose(pf);
         }
     }
@@ -934,7 +1000,8 @@ int main(int argc, char** argv) {
         std::cout << "Local Haplotype constructer\nUsage:\n  Ambigram --op bfb|sc_bfb --in_lh <file[,file...]> --lp_prefix <name> [--juncdb <file> --junc_info true] "
                      "[--reversed true] [--all true] [--solver_timeout <seconds>] [--devices N|all|<ordinal,ordinal,...>] [--cn_profile <file>] "
                      "[--junc_profile <file>] [--frag_profile <file> [--frags <file>]] [--evidence_profile <file>] [--evidence_depth <file>] [--fold_profile <file>] [--fold_arms <file>] "
-                     "[--path_compare <file> [--truth <file>] [--compare_dmax N] [--path_align <file>]] [--ref_fasta <file> --out_fasta <file>]\n"
+                     "[--path_compare <file> [--truth <file>] [--compare_dmax N] [--path_align <file>]] [--path_coords <file>] [--lift <queries> --lift_out <file>] "
+                     "[--ref_fasta <file> --out_fasta <file>]\n"
                      "  --op bfb: --in_lh may list several samples; their chromosomes are reconstructed as one batch, over the devices named by --devices\n"
                      "  --cn_profile <file> (--op bfb): one tab-separated row per segment after the run: sample, chromosome, segment id, start, end, input CN, "
                      "target CN, forward count, reverse count, count - target (PROP I1 / C1 / I2 / C2 samples are refused, exit status 2)\n"
@@ -961,6 +1028,11 @@ int main(int argc, char** argv) {
                      "orientation as is and for the reverse complement (dist: insertions plus deletions, -1 above N; N 0..1024, default 64); with --truth a T row "
                      "per chromosome, the final path against that chromosome's line of the truth file (a printed path with global ids, or `.`; one sample only) "
                      "(PROP I1 / C1 / I2 / C2 samples and --devices are refused, exit status 2)\n"
+                     "  --path_coords <file> (--op bfb): one tab-separated row per chromosome after the run: cells, runs, cells of length 0, the amplicon's length "
+                     "in base pairs, base pairs on the '-' strand, from the device's path coordinates of the final paths\n"
+                     "  --lift <queries> --lift_out <file> (--op bfb): per line `<chromosome index> <pos>` of the query file one tab-separated row: pos, cell, segment id, "
+                     "strand, chromosome name, genomic position (0-based) of position pos of the chromosome's amplicon (its record of --out_fasta); "
+                     "`-1 0 . . -1` for a position outside it (one sample; PROP I1 / C1 / I2 / C2 samples and --devices are refused, exit status 2)\n"
                      "  --path_align <file> (with --path_compare): where the two paths of every P and T row differ, aligned on the device in the orientation with "
                      "the smaller dist (ties as is) at the cap of --compare_dmax: per row a header line A, tag, chromosome index, orient, dist, n_runs, then one "
                      "line per maximal run of insertions or deletions: D or I, a_pos, b_pos, len and the run's cells as a printed path (a row with both dist -1: "

@@ -631,6 +631,71 @@ int ambi_batch_path_align_runs(const ambi_batch_t* b, int32_t pair, ambi_align_r
  * results; the slots at and behind n_runs are zero.  Valid after ambi_batch_path_align_wait until the next ambi_batch_path_align. */
 int ambi_batch_path_align_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* runs_off);
 
+/* Path coordinates ON THE DEVICE (ambi_path_coords_kernel, ambi_path_lift_kernel): every other result speaks of a path in cells; this
+ * one speaks in base pairs.  With len(c) the length of segment |c|, a request scans every unit's path into a 64-bit plane,
+ *   plane[k] = base pairs in front of cell k, k = 0 .. P, plane[P] = the amplicon's length,
+ * which stays on the device, and answers a batch of lift-over queries from it: amplicon position -> cell, segment, offset in the
+ * segment.  Position p is byte p of ambi_batch_sequence's output for the same unit (the lengths follow its convention: 0-based,
+ * half-open, end - start), so this is also where byte p of an amplicon FASTA comes from.  It replaces downloading every path
+ * (ambi_batch_unit_path) and walking it on the host with a table of segment lengths, once per read when reads are aligned to the
+ * amplicon; 32 bytes per unit and 32 bytes per query travel to the host.  Limits: a length is 0 .. 2^31 - 1 and a path has at most
+ * 2^22 cells, so every offset is below 2^53. */
+typedef struct {
+    int32_t status;        /* the unit's status; for a unit with a negative status or without a path the status of a failed side of
+                              the path comparison (AMBI_ERR_BAD_INPUT when the unit's own status is not negative): cells and all
+                              that follows are then 0 */
+    int32_t cells;         /* P of the scanned path */
+    int32_t runs;          /* maximal stretches of cells counting up by one, as the sequence request counts them */
+    int32_t empty_cells;   /* cells of length 0 */
+    int64_t bp_len;        /* the amplicon's length, plane[P] */
+    int64_t bp_minus;      /* base pairs crossed on the '-' strand */
+} ambi_unit_coords_t;
+typedef struct {
+    int32_t unit;
+    int32_t reserved;      /* 0 */
+    int64_t pos;           /* position in the unit's amplicon, 0-based */
+} ambi_lift_query_t;
+typedef struct {
+    int32_t status;        /* 0, or the failed unit's ambi_unit_coords_t::status */
+    int32_t cell;          /* the LAST k in [0, P) with plane[k] <= pos: of cells of length 0 none is ever named; -1 for pos < 0,
+                              pos >= bp_len or a failed unit */
+    int32_t seg;           /* the signed LOCAL segment id of that cell (+: '+' strand), 0 where cell is -1 */
+    int32_t reserved;      /* 0 */
+    int64_t seg_off;       /* offset from the segment's start in GENOME orientation: pos - cell_start on a '+' cell,
+                              len - 1 - (pos - cell_start) on a '-' cell; the segment's start + seg_off is the genomic coordinate and
+                              the base there, complemented on '-', is byte pos of the sequence.  -1 where cell is -1 */
+    int64_t cell_start;    /* plane[cell], -1 where cell is -1 */
+} ambi_lift_t;
+/* A unit's segment lengths in base pairs, len[i] for local segment i + 1; n must be the unit's n_seg and every length 0 .. 2^31 - 1
+ * (what a .lh can express), otherwise AMBI_ERR_ARG.  A second call replaces the first.  Units built from a graph
+ * (ambi_batch_add_graph_chr) have end - start of their SEG lines already; a unit nobody gave lengths has lengths of 0: its bp_len is
+ * 0 and every query into it is out of range.  AMBI_ERR_STATE after ambi_batch_run_sharded. */
+int ambi_batch_set_unit_seg_lengths(ambi_batch_t* b, int32_t unit, const int64_t* len, int32_t n);
+/* Queues the scan of EVERY unit's path ambi_batch_unit_path(unit, which) of the LAST run and, behind it, the n queries q[0 .. n) on
+ * hip_stream: the length image if the device does not hold this version of it, the queries, two kernels, then one device-to-host
+ * copy of the block on the engine's copy stream; hip_stream is not blocked.  n = 0 is "just the coordinates" (q may be NULL).  The
+ * request keeps a copy of the queries; no request ever answers from the plane of another run or another `which`.  The plane
+ * (8 bytes per cell of every unit's path capacity plus one) is allocated at the first request; a failure to allocate it is this
+ * call's error.  AMBI_ERR_STATE before any run; AMBI_ERR_ARG for another `which`, n < 0 or a query whose unit is not in the batch;
+ * AMBI_ERR_UNSUPPORTED after ambi_batch_run_sharded. */
+int ambi_batch_path_coords(ambi_batch_t* b, int32_t which, const ambi_lift_query_t* q, int32_t n, void* hip_stream);
+/* Blocks until the results are in host memory.  Makes the run's results final first (ambi_batch_wait) and scans and lifts once more,
+ * with the request's own copy of the queries, if that changed them after the request was queued. */
+int ambi_batch_path_coords_wait(ambi_batch_t* b);
+/* A unit's summary / the answer to query i of the last request; AMBI_ERR_STATE without a waited-for request of the last run. */
+int ambi_batch_path_coords_summary(const ambi_batch_t* b, int32_t unit, ambi_unit_coords_t* out);
+int ambi_batch_path_coords_result(const ambi_batch_t* b, int32_t query, ambi_lift_t* out);
+/* The entries [first, first + n) of a unit's plane to host memory, first + n <= cells + 1; nothing else is downloaded.  Two reads
+ * turn a fold's arm (ambi_batch_unit_fold_plane) or an uncovered stretch (ambi_batch_unit_evidence_depth) into base pairs: it
+ * replaces a host-side prefix sum over the downloaded path.  AMBI_ERR_ARG for a range outside 0 .. cells + 1. */
+int ambi_batch_path_coords_copy(ambi_batch_t* b, int32_t unit, int64_t first, int64_t n, int64_t* out);
+/* The plane area where it was computed (DEVICE memory): *bytes in all, unit u's slice of int64 at unit_off[u] (a multiple of 16),
+ * entries 0 .. cells valid and stale values behind them; unit_off may be NULL, else cap >= the batch's units.  Valid after
+ * ambi_batch_path_coords_wait until the next ambi_batch_path_coords. */
+int ambi_batch_path_coords_plane_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* unit_off, int32_t cap);
+/* The block in DEVICE memory, for collectives: ambi_unit_coords_t[units], then at *results_off ambi_lift_t[n].  Valid as above. */
+int ambi_batch_path_coords_device(ambi_batch_t* b, void** dev_ptr, int64_t* bytes, int64_t* results_off);
+
 /* The nucleotide sequence of every unit's path, assembled ON THE DEVICE (ambi_seq_extents_kernel, ambi_seq_fill_kernel): the
  * reference's last step, which it leaves to scripts around bedtools (script/main.py:537-588 bfb2fasta: a BED line per path cell
  * through `bedtools getfasta -s`, all records joined).
